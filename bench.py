@@ -12,7 +12,12 @@ segment grids (the general path of pred_dist).  At N > 1 GPUs the workload is co
 4 096 rows per GPU at 8 GPUs), cluster state broadcast once from rank 0, scores returned by one all-gather
 (hdpgpc_amd.batch.emission_scores - the function the tests exercise is the function timed here).
 
-Prints ONE JSON line (rank 0).  Run: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either launch it under
+A plain run measures the headline only: set-up, W warm-up steps, K timed steps, one JSON line.  --full adds what takes runs
+of its own: the CPU baseline (before the first GPU call) and the secondary workloads (after the timed steps), each on the line
+under its own key.  --dump-outputs DIR writes what the last timed step returned (scores.npy [N, K] and info.npy, float64)
+for output-for-output comparison of two builds: the inputs are seeded, identical from run to run.
+
+Prints ONE JSON line (rank 0).  Run: python bench.py [--gpus N --steps K --warmup W --full --dump-outputs DIR].  For N > 1 either launch it under
 python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 or just run `python bench.py --gpus N`: without WORLD_SIZE in the environment the process starts that launcher itself as a
 CHILD process (before it has made any GPU call - nothing that touched the GPU is ever re-executed), relays rank 0's line
@@ -368,18 +373,42 @@ def secondary_matrix_terms(dev, ops, b=16384, T=90, reps=5):
                    "roofline": {"bound": "hbm", "achieved": gb9, "peak": 8000.0, "unit": "GB/s", "frac": gb9 / 8000.0}}}
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, out, info):
+    """What emission_scores returned in the last timed step: the score rows q [N, K] and this rank's info block, as float64
+    .npy files.  Above DUMP_MAX_BYTES in all, a fixed seeded sample of rows is written instead (rows.npy holds its indices)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {"scores": out.detach().cpu().numpy().astype(np.float64), "info": info.detach().cpu().numpy().astype(np.float64)}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        n = arrs["scores"].shape[0]
+        keep = max(1, int(n * DUMP_MAX_BYTES / (2 * total)))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrs = {k: a[rows[rows < a.shape[0]]] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline workload only (used for the PMC passes)")
-    ap.add_argument("--no-offline", action="store_true", help="skip the driver-level secondaries (include_batch on records 100 / 102, include_sample at T = 256: ~10^5 launches)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and the secondary workloads (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (scores.npy, info.npy; float64) to DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads (headline only)")
+    ap.add_argument("--no-offline", action="store_true", help="with --full: skip the driver-level secondaries (include_batch on records 100 / 102, include_sample at T = 256: ~10^5 launches)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) | gloo (rehearsal on a one-GPU box)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--segments", type=int, default=0, help="override the batch size (rehearsals only; 0 = the named config)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -389,7 +418,7 @@ def main():
     if args.gpus != world:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     # the CPU baseline (rank 0, N = 1 only) runs before this process touches the GPU
-    cpu = cpu_baseline() if (world == 1 and not args.no_cpu_baseline) else None
+    cpu = cpu_baseline() if (world == 1 and args.full and not args.no_cpu_baseline) else None
 
     import torch.distributed as dist
     if args.single_device:
@@ -490,7 +519,9 @@ def main():
             res["roofline"]["executed_flops_per_eval"] = ex
             res["roofline"]["executed_frac"] = achieved / FP64_MFMA_PEAK_TFLOPS * ex / algorithmic_flops_per_eval(t_len)
             res["roofline"]["frac_ceiling"] = algorithmic_flops_per_eval(t_len) / ex
-        if world == 1 and not args.no_secondary:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, info)
+        if world == 1 and args.full and not args.no_secondary:
             res["secondary"] = secondary_shared_grid(dev, ops)
             res["secondary_pairs_T90"] = secondary_pairs_t90(dev, ops, synth)
             res["secondary_pairs_generic"] = secondary_pairs_generic(dev, ops, synth)
