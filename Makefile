@@ -24,27 +24,10 @@ stamps: $(SRCS) $(HDR)
 	mkdir -p hdpgpc_amd/lib/ab
 	$(HIPCC) $(FLAGS) -DHGP_STAMPS -shared -o hdpgpc_amd/lib/ab/libhgp_stamps.so $(SRCS)
 
-# diagnostic builds for the cooperative-factor race (tile_f64.hpp, coop_factor): a delay injected in front of the
-# right-hand-side row update, with the pre-round-2 round-robin dealing (races) and with the owner dealing (immune)
-raceprobe: $(SRCS) $(HDR)
-	mkdir -p build/probe
-	$(HIPCC) $(FLAGS) -DHGP_RACE_PROBE_DELAY -DHGP_RACE_PROBE_ROUNDROBIN -shared -o build/probe/libhgp_race_old.so $(SRCS)
-	$(HIPCC) $(FLAGS) -DHGP_RACE_PROBE_DELAY -shared -o build/probe/libhgp_race_new.so $(SRCS)
-
 # every workgroup barrier followed by a pseudo-random per-wave delay: run the GPU tests with HGP_LIB pointing at it
 racestress: $(SRCS) $(HDR)
-	mkdir -p build/probe
+	mkdir -p hdpgpc_amd/lib/ab
 	$(HIPCC) $(FLAGS) -DHGP_RACE_STRESS -shared -o hdpgpc_amd/lib/ab/libhgp_race_stress.so $(SRCS)
-
-# in-situ knock-out builds of k_pairs (results wrong by construction, only the time matters; tools/knockout_time.py):
-# one component replaced by a stub each - what the component costs INSIDE the kernel, not in isolation
-KNOCKOUTS = NOEXP NODIAG NORHS NOFACTOR NOFILL NOAF SHARED_M
-knockouts: $(LIB)
-	mkdir -p build/probe
-	for v in $(KNOCKOUTS); do \
-	  $(HIPCC) $(FLAGS) -DHGP_EXP_$$v -c -o build/probe/hgp_pairs_$$v.o $(CSRC)/hgp_pairs.hip && \
-	  $(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/probe/libhgp_exp_$$v.so $(filter-out $(OBJDIR)/hgp_pairs.o,$(OBJS)) build/probe/hgp_pairs_$$v.o || exit 1; \
-	done
 
 clean:
 	rm -rf $(LIB) $(OBJDIR)

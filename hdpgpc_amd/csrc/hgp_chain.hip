@@ -518,16 +518,13 @@ int hgp_chol_inverse_rhs_batched_f64(const double* A, int T, int b, double jitte
   InvRhsArgs a{A, T, b, jitter_rel, add_diag, Linv, rhs, rhs_on, rhs_trans, rhs_out, info};
   hipStream_t st = (hipStream_t)stream;
   // few matrices (the member step of a few chains): one workgroup per (matrix, panel) - latency; many: one wave each - throughput
-  // (tools/time_inv_rhs.py; while the workgroups fit the chip in one round - beyond that the one-wave kernel wins.
-  // HGP_INV_COOP_MAX_WG overrides the round size, 0 = never.)
-  static const int coop_max_wg = getenv("HGP_INV_COOP_MAX_WG") ? atoi(getenv("HGP_INV_COOP_MAX_WG")) : 256;
+  // (tools/time_inv_rhs.py; while the workgroups fit the chip in one round - beyond that the one-wave kernel wins)
+  constexpr int coop_max_wg = 256;
   // T > 64: the dataflow form (T = 90: 21.7 us, barrier form 27.1, one wave per panel 30.3; T = 128: 28.0 / 30.6 / 51.5; two
   // workgroups per CU at NB = 6); 32 < T <= 64: the barrier form (T = 50: 13.1 us against 14.7 / 16.5); T <= 32 is one wave anyway
   const long wgs = (long)b * 2 * ((T + 15) >> 4);
   if (T > 64 && wgs <= (nb_for(T) == 6 ? 2 : 1) * (long)coop_max_wg) {
-    static const bool barrier_form = env_on("HGP_INV_COOP_BARRIER");
-    if (barrier_form && wgs <= coop_max_wg) return launch_coop_inv_rhs<8>(a, st);
-    if (!barrier_form) return nb_for(T) == 6 ? launch_cooph_inv_rhs<6>(a, st) : launch_cooph_inv_rhs<8>(a, st);
+    return nb_for(T) == 6 ? launch_cooph_inv_rhs<6>(a, st) : launch_cooph_inv_rhs<8>(a, st);
   } else if (T > 32 && T <= 64 && wgs <= coop_max_wg) {
     return launch_coop_inv_rhs<4>(a, st);
   }

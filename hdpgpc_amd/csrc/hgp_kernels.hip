@@ -218,7 +218,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_wave_score(ScoreArgs a) {
         R[K][r] = v;
       }
     if (base == 0) {
-      wave_factor<NB, 1, true>(U, R, scr, cnt > 16 ? Wl : nullptr, nullptr, lane, pa, nullptr, 0, T);
+      wave_factor<NB, 1>(U, R, scr, cnt > 16 ? Wl : nullptr, nullptr, lane, pa, nullptr, 0, T);
       ld = pa.logdet();
     } else {
       wave_fwd_solve<NB>(U, Wl, R, lane);
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(64 * WAVES, (NB <= 6) ? 2 : 1) void k_wave_score1(E
   __builtin_amdgcn_wave_barrier();
   PivotAcc pa;
   pa.init();
-  const double q = wave_factor<NB, 2, (NB >= 8), (NB < 8)>(U, Rnone, scr, nullptr, dv, lane, pa, nullptr, 0, T);
+  const double q = wave_factor<NB, 2, (NB < 8)>(U, Rnone, scr, nullptr, dv, lane, pa, nullptr, 0, T);
   if (lane == 0) {
     a.out_quad[seg] = q;
     if (a.out_logdet) a.out_logdet[seg] = pa.logdet();
@@ -653,7 +653,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm(GemmArgs a) {
   }
 }
 
-// Large products (M, N, Kd multiples of 32, Kd > 128, no transposes: the a8 / a9 compositions at 128 < T <= 256): one wave per
+// Large products (M, N, Kd multiples of 32, Kd > 128, no transposes: the a9 composition at 128 < T <= 256): one wave per
 // 32 x 32 block of C - four accumulator tiles fed by two A and two B fragments per k-step, i.e. half the L2 operand traffic per
 // MFMA of k_gemm (which is bound by exactly that traffic at these sizes: 14 TFLOP/s on the 2 T^3 product at T = 256).
 __global__ __launch_bounds__(64 * WAVES) void k_gemm22(GemmArgs a) {
@@ -716,7 +716,7 @@ int launch_gemm(const GemmArgs& a0, int batch, hipStream_t st) {
     // (only for launches that fill the chip: a single 256^3 product is 64 waves here against 256 in k_gemm - latency-bound,
     // 25.8 vs ~12 us in the member step of the online path at T = 256)
     if (!a.tA && !a.tB && a.M % 32 == 0 && a.N % 32 == 0 && a.Kd % 32 == 0 && a.Kd > 128 &&
-        (long)(a.M / 32) * (a.N / 32) * nb >= 2048 && !env_on("HGP_GEMM_PLAIN")) {
+        (long)(a.M / 32) * (a.N / 32) * nb >= 2048) {
       const int nt2 = (a.M / 32) * (a.N / 32);
       hipLaunchKernelGGL(k_gemm22, dim3((nt2 + WAVES - 1) / WAVES, nb), dim3(64 * WAVES), 0, st, a);
       continue;
@@ -777,19 +777,6 @@ __global__ void k_sub_batched(const double* __restrict__ A, const double* __rest
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)n) return;
   for (int m = blockIdx.y; m < b; m += gridDim.y) C[(size_t)m * n + i] = A[(size_t)m * sA + i] - B[(size_t)m * sB + i];
-}
-
-// r[b] = f_cur[b] - A[b] f_prev[b]   (a8 residual), one workgroup per item
-__global__ __launch_bounds__(256) void k_lat_resid(const double* __restrict__ f_cur, const double* __restrict__ f_prev,
-                                                    const double* __restrict__ A, int T, double* __restrict__ r) {
-  const int b = blockIdx.x;
-  const double* Ab = A + (size_t)b * T * T;
-  const double* fp = f_prev + (size_t)b * T;
-  for (int i = threadIdx.x; i < T; i += 256) {
-    double s = 0.0;
-    for (int k = 0; k < T; ++k) s = fma(Ab[(size_t)i * T + k], fp[k], s);
-    r[(size_t)b * T + i] = f_cur[(size_t)b * T + i] - s;
-  }
 }
 
 // a11: omega^2 exp(-0.5 dx^2 / rho^2) + diag_add I on the (optionally [0,1]-normalised) grid
@@ -1952,14 +1939,9 @@ static int tp_for(int n) {   // padded size: wave kernels {32,64,96,128}, cooper
   if (n <= HGP_MAX_T_WAVE) return 16 * nb_for(n);
   return n <= 192 ? 192 : 256;
 }
-// Diagnostic switch: HGP_PAIRS_COOP=1 (read when a plan is created) runs the cooperative kernels for T <= 128 too.
-static int tp_plan(int n) {
-  if (n <= HGP_MAX_T_WAVE && env_on("HGP_PAIRS_COOP")) return 128;   // (k_pairs_cooph<8>; a <4> instance spilled 316 VGPRs and had no use)
-  return tp_for(n);
-}
 
 static size_t plan_bytes(int T, int Ts_max, int K, size_t* offs /*[24]*/) {
-  const size_t TP = (size_t)tp_plan(std::max(T, Ts_max));
+  const size_t TP = (size_t)tp_for(std::max(T, Ts_max));
   const size_t mat = (size_t)K * TP * TP * sizeof(double);
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -1980,7 +1962,7 @@ static size_t plan_bytes(int T, int Ts_max, int K, size_t* offs /*[24]*/) {
   tmp[9] = take((size_t)K * TP * sizeof(double));  // ap
   tmp[10] = take((size_t)K * sizeof(int32_t));     // perm
   tmp[11] = take(TP * sizeof(double));             // x_basis copy
-  if (TP > HGP_MAX_T_WAVE || env_on("HGP_PAIRS_COOP")) {   // cooperative kernel: overflow areas for dense grids
+  if (TP > HGP_MAX_T_WAVE) {   // cooperative kernel: overflow areas for dense grids
     const int nb = (int)TP / 16;
     const size_t cap = (nb >= 12) ? 48 : (nb == 8 ? 24 : 16);
     const size_t over = (size_t)nb * nb > cap ? (size_t)nb * nb - cap : 0;
@@ -2085,9 +2067,9 @@ int hgp_pairs_plan_create(hgp_pairs_plan** plan, int T, int Ts_max, int K, const
   if (!p) return -1;
   p->T = T;
   p->K = K;
-  p->TP = tp_plan(std::max(T, Ts_max));
+  p->TP = tp_for(std::max(T, Ts_max));
   p->NB = p->TP / 16;
-  p->coop = p->TP > HGP_MAX_T_WAVE || env_on("HGP_PAIRS_COOP");
+  p->coop = p->TP > HGP_MAX_T_WAVE;
   p->theta.assign(theta_host, theta_host + 3 * (size_t)K);
   p->perm.resize(K);
   for (int k = 0; k < K; ++k) p->perm[k] = k;
@@ -2168,8 +2150,7 @@ int hgp_pairs_plan_update(hgp_pairs_plan* p, const double* x_basis, const double
     case 4: launch_wave_inv<4>(fa, st); break;
     case 6: launch_wave_inv<6>(fa, st); break;
     case 8:   // one workgroup per block column (the trailing updates split over its four waves) halves the latency at T = 128
-      if (env_on("HGP_PLAN_WAVE_INV")) launch_wave_inv<8>(fa, st);
-      else launch_coop_inv_only<8>(fa, st);
+      launch_coop_inv_only<8>(fa, st);
       break;
     case 12: launch_coop_potrf<12>(fa, st); break;
     default: launch_coop_potrf<16>(fa, st); break;
@@ -2249,33 +2230,8 @@ int hgp_lat_error_f64(const double* f_cur, const double* f_prev, const double* A
   if (T <= HGP_MAX_T_WAVE)   // fused: one wavefront per item, nothing goes through the workspace
     return hgp_internal_lat_error_wave(f_cur, f_prev, A, Gamma, covprev, T, b, out, info, (hipStream_t)stream);
   if (!ws || ws_bytes < hgp_matrix_lik_ws_bytes(T, b)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  if (!env_on("HGP_MATLIK_COMPOSE"))   // 128 < T <= 256: one fused cooperative kernel per item, Gram form (hgp_matlik_coop.hip)
-    return hgp_internal_lat_coop(f_cur, f_prev, A, Gamma, covprev, T, b, out, info, (double*)ws, st);
-  // (kept for A/B runs: the composition of the batched kernels)
-  const long tt = (long)T * T;
-  double* Gc = (double*)ws;          // copy of Gamma -> L
-  double* Z = Gc + (size_t)b * tt;   // L^{-1}
-  double* Y = Z + (size_t)b * tt;    // Z A
-  double* Y2 = Y + (size_t)b * tt;   // Y P  (and z = Z r in its first T entries per item afterwards)
-  double* r = Y2 + (size_t)b * tt;   // residuals [b,T]
-  if (hipMemcpyAsync(Gc, Gamma, sizeof(double) * b * tt, hipMemcpyDeviceToDevice, st) != hipSuccess) return launch_status();
-  int rc = hgp_potrf_batched_f64(Gc, T, b, 1e-8, 0.0, Z, nullptr, info, stream);   // _chol_spd(Gamma), GPI_model.py:312
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_lat_resid, dim3(b), dim3(256), 0, st, f_cur, f_prev, A, T, r);
-  GemmArgs g1{Z, A, Y, T, T, T, T, T, T, tt, tt, tt, 1.0, 0.0, 0, 0};
-  g1.triA = 1;                                                                       // Z = L^-1 is lower triangular
-  if ((rc = launch_gemm(g1, b, st))) return rc;
-  GemmArgs g2{Y, covprev, Y2, T, T, T, T, T, T, tt, tt, tt, 1.0, 0.0, 0, 0};
-  if ((rc = launch_gemm(g2, b, st))) return rc;
-  // trace(A^T Gamma^{-1} A P) = sum (Y P) o Y
-  hipLaunchKernelGGL(k_dot_batched, dim3(b), dim3(256), 0, st, Y2, Y, tt, tt, tt, -0.5, 0, out);
-  // mahal = || Z r ||^2 : z = Z r as a T x 1 GEMM into Y2
-  GemmArgs g3{Z, r, Y2, T, 1, T, T, 1, 1, tt, (long)T, tt, 1.0, 0.0, 0, 0};
-  g3.triA = 1;
-  if ((rc = launch_gemm(g3, b, st))) return rc;
-  hipLaunchKernelGGL(k_dot_batched, dim3(b), dim3(256), 0, st, Y2, Y2, tt, tt, (long)T, -0.5, 1, out);
-  return launch_status();
+  // 128 < T <= 256: one fused cooperative kernel per item, Gram form (hgp_matlik_coop.hip)
+  return hgp_internal_lat_coop(f_cur, f_prev, A, Gamma, covprev, T, b, out, info, (double*)ws, (hipStream_t)stream);
 }
 
 int hgp_mniw_loglik_f64(const double* M, const double* Sigma, const double* m_mean, const double* m_r_cov,
@@ -2289,7 +2245,7 @@ int hgp_mniw_loglik_f64(const double* M, const double* Sigma, const double* m_me
   if (!ws || ws_bytes < hgp_matrix_lik_ws_bytes(T, b)) return -1;
   hipStream_t st = (hipStream_t)stream;
   // the hot path's call (identity right covariance, diagonal prior scale): one fused cooperative kernel per item (hgp_matlik_coop.hip)
-  if (!m_r_cov && scale_is_diagonal && !env_on("HGP_MATLIK_COMPOSE"))
+  if (!m_r_cov && scale_is_diagonal)
     return hgp_internal_mniw_coop(M, Sigma, m_mean, scale, prior_stride, T, b, out, info, (double*)ws, st);
   // everything else at 128 < T <= 256: composition of the batched kernels
   const long tt = (long)T * T;
@@ -2340,9 +2296,9 @@ int hgp_chol_rank1_f64(double* L, const double* v, const double* alpha, const do
 #ifdef HGP_STAMPS
   a.stamps = hgp_internal_stamp_dev;
 #endif
-  if (T % 2 == 0 && !env_on("HGP_RANK1_DIRECT") && !env_on("HGP_RANK1_COAL") && (T >= 192 || env_on("HGP_RANK1_PIPE")))
+  if (T % 2 == 0 && T >= 192)
     hipLaunchKernelGGL(k_chol_rank1_pipe, dim3(b), dim3(64 * ((T + 63) / 64)), 0, (hipStream_t)stream, a);
-  else if (T % 2 == 0 && !env_on("HGP_RANK1_DIRECT"))
+  else if (T % 2 == 0)
     hipLaunchKernelGGL(k_chol_rank1<true>, dim3(b), dim3(64 * ((T + 63) / 64)), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(k_chol_rank1<false>, dim3(b), dim3(64 * ((T + 63) / 64)), 0, (hipStream_t)stream, a);

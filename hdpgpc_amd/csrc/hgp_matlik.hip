@@ -119,7 +119,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_wave_lat(LatArgs a) {
   }
   PivotAcc pa;
   pa.init();
-  wave_factor<NB, 0, (NB >= 8)>(U, R1, scr, Wl, nullptr, lane, pa, nullptr, 0, T);
+  wave_factor<NB, 0>(U, R1, scr, Wl, nullptr, lane, pa, nullptr, 0, T);
   double acc = 0.0;
   // vector panel: column 0 = r = f_cur - A f_prev (the product rides the matrix core with f_prev as a one-column operand)
   {
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(64 * WAVES, (NB <= 6 && !HASR && SDIAG) ? 2 : 1) vo
   add_diag<NB>(U, 1e-8, T, lane);                                  // chol(0.5 (S + S^T) + 1e-8 I), GPI_model.py:1353
   PivotAcc pa;
   pa.init();
-  wave_factor<NB, 0, (NB >= 8)>(U, R2, scr, Wl, nullptr, lane, pa, nullptr, 0, T);
+  wave_factor<NB, 0>(U, R2, scr, Wl, nullptr, lane, pa, nullptr, 0, T);
   double acc = 0.0;
 #pragma nounroll
   for (int J = 0; J < NB; ++J) {
@@ -384,7 +384,7 @@ int hgp_internal_lat_error_wave(const double* f_cur, const double* f_prev, const
   switch (nb_for(T)) {
     case 2: hipLaunchKernelGGL(k_wave_lat_gram<2>, grid, blk, 0, st, a); break;
     case 4: hipLaunchKernelGGL(k_wave_lat_gram<4>, grid, blk, 0, st, a); break;
-    case 6: hipLaunchKernelGGL(env_on("HGP_LAT_PANEL") ? k_wave_lat<6> : k_wave_lat_gram<6>, grid, blk, 0, st, a); break;
+    case 6: hipLaunchKernelGGL(k_wave_lat_gram<6>, grid, blk, 0, st, a); break;
     default: hipLaunchKernelGGL(k_wave_lat<8>, grid, blk, 0, st, a); break;   // 64 tiles of Y do not fit next to the factor: panel form
   }
   return launch_status();

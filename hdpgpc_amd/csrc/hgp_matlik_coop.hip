@@ -115,7 +115,8 @@ __device__ __forceinline__ void solve_panels(const double* __restrict__ Lp, cons
 
 // Which factorisation the two kernels run on (round 4, last session): DF = the eight-wave (NB / 2) dataflow factorisation of the
 // pair kernels with a packed output (cooph_factor_df<NB, 2>) instead of the four-wave barrier version - the factor was 146 of the
-// 385 / 515 us of a call, and the panel solves behind it are spread over twice the waves.  HGP_MATLIK_COOP4=1 keeps the four-wave kernels.
+// 385 / 515 us of a call, and the panel solves behind it are spread over twice the waves.  a9 runs the eight-wave kernel only;
+// a8 keeps the four-wave one for large batches (launch_coop_lat).
 template <int NB, bool DF>
 struct MatlikLds {
   static constexpr int NWK = DF ? CoopH<NB>::NW : WAVES;
@@ -255,17 +256,12 @@ __global__ __launch_bounds__((64 * MatlikLds<NB, DF>::NWK)) void k_coop_mniw(Mni
   }
 }
 
-template <int NB, bool DF>
-int launch_coop_mniw_v(const MniwCoopArgs& a, hipStream_t st) {
-  const size_t lds = sizeof(double) * (MatlikLds<NB, DF>::DOUBLES + 8);
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_mniw<NB, DF>), lds)) return rc_;
-  hipLaunchKernelGGL((k_coop_mniw<NB, DF>), dim3(a.b), dim3(64 * MatlikLds<NB, DF>::NWK), lds, st, a);
-  return launch_status();
-}
 template <int NB>
 int launch_coop_mniw(const MniwCoopArgs& a, hipStream_t st) {
-  static const bool four = env_on("HGP_MATLIK_COOP4");
-  return four ? launch_coop_mniw_v<NB, false>(a, st) : launch_coop_mniw_v<NB, true>(a, st);
+  const size_t lds = sizeof(double) * (MatlikLds<NB, true>::DOUBLES + 8);
+  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_mniw<NB, true>), lds)) return rc_;
+  hipLaunchKernelGGL((k_coop_mniw<NB, true>), dim3(a.b), dim3(64 * MatlikLds<NB, true>::NWK), lds, st, a);
+  return launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------------------ a8
@@ -481,8 +477,7 @@ template <int NB>
 int launch_coop_lat(const LatCoopArgs& a, hipStream_t st) {
   // the eight-wave form is the faster CALL (281 vs 341 us for a few items); with a workgroup on every CU the four-wave form's larger
   // register budget wins for a8 (0.515 vs 0.543 ms per 256 items at T = 256)
-  static const bool four = env_on("HGP_MATLIK_COOP4");
-  return (four || a.b >= 200) ? launch_coop_lat_v<NB, false>(a, st) : launch_coop_lat_v<NB, true>(a, st);
+  return (a.b >= 200) ? launch_coop_lat_v<NB, false>(a, st) : launch_coop_lat_v<NB, true>(a, st);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // a2 + a5, the per-pair kernels of hgp_loglik_pairs_f64 (explicit-operator evaluation of cov_f): k_pairs<NB> (T <= 128, one
-// wavefront per pair) and k_pairs_cooph<NB> (NB/2 waves per pair) for T <= 256.  (The 4-wave cooperative kernel of round 1,
+// wavefront per pair) and k_pairs_cooph<NB> (NB/2 waves per pair) for 128 < T <= 256.  (The 4-wave cooperative kernel of round 1,
 // k_pairs_coop, 1.28x slower, was removed in round 3.)
 // The plan (per-cluster operators) and the C-ABI live in hgp_kernels.hip; the solve-based kernel in hgp_pairs_acc.hip.
 #include <hip/hip_runtime.h>
@@ -13,16 +13,6 @@
 
 using namespace hgp;
 
-#ifndef HGP_PAIRS_DIAG_MFMA
-#define HGP_PAIRS_DIAG_MFMA 0   // 1 = the MFMA-blocked diag16 also at NB = 8: measured 1.5 % faster, but 43 spilled VGPRs turn into 59 MB of scratch writes per launch (WRITE_SIZE): not kept
-#endif
-// in-situ knock-out experiments (diagnostic builds only; results are wrong by construction)
-#ifdef HGP_EXP_NOEXP
-#define HGP_EXP4(h, o) _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) (o)[i_] = 1.0 / (1.0 + (h)[i_])
-#else
-#define HGP_EXP4(h, o) exp_neg4(h, o)
-#endif
-
 namespace {
 
 // -------------------------------------------------------------------------------------- a2 + a5
@@ -35,11 +25,9 @@ constexpr int PAIRS_DCOLS = 16;   // clusters whose d = y - E^T a' one pass of t
 // of LDS) allows one workgroup per CU from NB = 6 on, i.e. ONE wave per SIMD at four waves: every latency of the pair - the pivot
 // chain of the six diag16 first of all - is idle time.  The band kernel at NB = 6 (the records' T = 90) fits 256 registers once
 // the sweep-1 operand ring holds two half-blocks instead of eight, so EIGHT waves share the segment's E: two per SIMD.
-#ifndef HGP_PAIRS_W8_NB
-#define HGP_PAIRS_W8_NB 6   // the NB whose band kernel runs eight waves per workgroup (0: none)
-#endif
+constexpr int PAIRS_W8_NB = 6;   // the NB whose band kernel runs eight waves per workgroup
 template <int NB, bool BAND>
-constexpr int pairs_waves() { return (BAND && NB == HGP_PAIRS_W8_NB) ? 8 : WAVES; }
+constexpr int pairs_waves() { return (BAND && NB == PAIRS_W8_NB) ? 8 : WAVES; }
 template <int NB, int PW = WAVES>
 constexpr size_t pairs_lds_bytes() {
   return sizeof(double) * ((size_t)(16 * NB) * (16 * NB) + 3 * 16 * NB + PW * DIAG_SCR + PAIRS_DCOLS * 16 * NB) +
@@ -251,11 +239,9 @@ __device__ __forceinline__ void band_sweeps(d4 (&cov)[NB * (NB + 1) / 2], const 
 // mask-driven sweeps, launched right behind on the same grid) takes the listed segments; its other workgroups leave at once.  With both sweep codes in one
 // kernel the allocator spilled 126 VGPRs at NB = 8 (284 B of scratch per lane, 189 MB of scratch writes per launch, WRITE_SIZE);
 // apart they need none.  Without a list (a.fb == nullptr: NB < 6, HGP_PAIRS_GENERIC=1) the generic kernel takes every segment.
-#ifndef HGP_PAIRS_OCC2_NB
-#define HGP_PAIRS_OCC2_NB 4   // largest NB built for two workgroups per CU (<= 256 VGPRs)
-#endif
+constexpr int PAIRS_OCC2_NB = 4;   // largest NB built for two workgroups per CU (<= 256 VGPRs)
 template <int NB, bool BAND>
-__global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_OCC2_NB) ? 2 : 1)) void k_pairs(PairsArgs a) {   // T <= 64: two workgroups per CU (the kernel sat 3 registers above that limit)
+__global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_NB) ? 2 : 1)) void k_pairs(PairsArgs a) {   // T <= 64: two workgroups per CU (the kernel sat 3 registers above that limit)
   constexpr int PW = pairs_waves<NB, BAND>();
   constexpr int TP = 16 * NB;
   constexpr int NH = NB / 2;
@@ -325,7 +311,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_O
         }
         if (__any(near)) {   // entries below the cut-off are exact zeros: a k-step of the block made of zeros only can be skipped bit for bit
           double ev[4];
-          HGP_EXP4(h, ev);
+          exp_neg4(h, ev);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             E[(16 * Kt + g + 4 * r) * TP + j] = (h[r] < PAIRS_CUT) ? ev[r] : 0.0;
@@ -396,7 +382,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_O
         const double u = xs[16 * I + g + 4 * r] - xs[16 * J + c];
         hk[r] = 0.5 * (u * u);
       }
-      HGP_EXP4(hk, ev);
+      exp_neg4(hk, ev);
 #pragma unroll
       for (int r = 0; r < 4; ++r) E[(16 * Kh + g + 4 * r) * TP + 16 * J + c] = (hk[r] < PAIRS_CUT) ? ev[r] : 0.0;
     }
@@ -480,11 +466,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_O
     d4 cov[NB * (NB + 1) / 2];
     // cov[I][J] += sum_h E[rows h, I]^T (M'[rows h, :] E[:, J]) : the basis index is split in two halves
     // so the intermediate panel is 4 tiles; it feeds the second sweep straight from its accumulators.
-#ifdef HGP_EXP_SHARED_M   // experiment: every wave of the chip streams the SAME M' (wrong results; upper bound of M' locality)
-    const double* Mbase = a.Mp + (size_t)g * TP;
-#else
     const double* Mbase = a.Mp + (size_t)kc * TP * TP + (size_t)g * TP;   // + column offset inside HGP_FILL (interleaved)
-#endif
     if constexpr (BAND) {
       band_sweeps<NB, (PW > WAVES) ? 2 : ((NB <= 6) ? 8 : 4)>(cov, a.Mp + (size_t)kc * TP * TP, E, lane, cc, noise, Ts
 #ifdef HGP_STAMPS
@@ -505,13 +487,6 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_O
     for (int J = 1; J < NB; ++J) pm[J] = pm[J - 1] | msk[J];
     constexpr int HALF = (1 << NH) - 1;
     int kA = -1, kB = -1, m = (pm[0] & HALF) ? msk[0] : 0;
-#ifdef HGP_EXP_NOFILL   // knock-out: sweep-1 operands are constants (no global loads, no LDS reads, no address arithmetic)
-#define HGP_FILL(slot, half, blk, Mptr, Jcol)                                                               \
-  _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                        \
-    _Pragma("unroll") for (int P_ = 0; P_ < NH; ++P_) ra[slot][s_][P_] = 1e-3 * (double)(blk);              \
-    re[slot][s_] = 1e-3 * (double)(Jcol);                                                                   \
-  }
-#else
 #define HGP_FILL(slot, half, blk, Mptr, Jcol)                                                               \
   _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                        \
     const double* row_ = (Mptr) + (size_t)(16 * (blk) + 4 * (2 * (half) + s_)) * TP;                        \
@@ -523,7 +498,6 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_O
     if (NH & 1) ra[slot][s_][NH - 1] = row_[16 * (NH - 1) + c];                                             \
     re[slot][s_] = E[(16 * (blk) + 4 * (2 * (half) + s_) + g) * TP + 16 * (Jcol) + c];                      \
   }
-#endif
 #define HGP_MMA(slot)                                                                                       \
   _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                        \
     _Pragma("unroll") for (int I_ = 0; I_ < NH; ++I_) BJ[I_] = mfma(ra[slot][s_][I_], re[slot][s_], BJ[I_]); \
@@ -613,7 +587,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_O
                   const double u = xs[16 * I + (ln >> 4) + 4 * r] - xs[16 * J + (ln & 15)];
                   hk[r] = 0.5 * (u * u);
                 }
-                HGP_EXP4(hk, ev);
+                exp_neg4(hk, ev);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) kt[r] = (hk[r] < PAIRS_CUT) ? cc * ev[r] : 0.0;
               }
@@ -637,11 +611,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_O
             // the reads can then be issued ahead of the branch and overlap the previous block's MFMAs
             double af[4];
 #pragma unroll
-#ifdef HGP_EXP_NOAF   // knock-out: sweep-2 A operands are constants (no LDS reads, no address arithmetic)
-            for (int r = 0; r < 4; ++r) af[r] = 1e-3 * (double)(Kt + I + r);
-#else
             for (int r = 0; r < 4; ++r) af[r] = E[(16 * (NH * h + Kt) + 4 * r + g) * TP + 16 * I + c];
-#endif
             if (msk[I] & (1 << (NH * h + Kt))) {
 #pragma unroll
               for (int r = 0; r < 4; ++r) cov[tix(I, J, NB)] = mfma(af[r], BJ[Kt][r], cov[tix(I, J, NB)]);
@@ -663,16 +633,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= HGP_PAIRS_O
     pa.init();
     d4 Rnone[NB];
     HGP_ACC(4);
-#ifdef HGP_EXP_NORHS   // knock-out: factor only, no right-hand side (diagnostic builds only)
-    wave_factor<NB, 0, (NB >= 8)>(cov, Rnone, scr, nullptr, dv, lane, pa, nullptr, 0, Ts);
-    const double q = dv[lane];
-#elif defined(HGP_EXP_NOFACTOR)   // knock-out: no factorisation at all
-    double q = dv[lane];
-#pragma unroll
-    for (int i_ = 0; i_ < NB * (NB + 1) / 2; ++i_) q += cov[i_][0] + cov[i_][1] + cov[i_][2] + cov[i_][3];
-#else
-    const double q = wave_factor<NB, 2, (NB >= 8) && !HGP_PAIRS_DIAG_MFMA, BAND || (NB < 8)>(cov, Rnone, scr, nullptr, dv, lane, pa, nullptr, 0, Ts);
-#endif
+    const double q = wave_factor<NB, 2, BAND || (NB < 8)>(cov, Rnone, scr, nullptr, dv, lane, pa, nullptr, 0, Ts);
     if (lane == 0) {
       a.out_quad[oidx] = a.score_on ? fma(-0.5, q, a.score_add) : (q);
       if (a.out_logdet) a.out_logdet[oidx] = pa.logdet();
@@ -1075,13 +1036,9 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
   PivotAcc pa;
   pa.init();
   HGP_ACC(5);
-#ifdef HGP_COOPH_BARRIERS   // the barrier-synchronised factorisation of rounds 1-2 (A/B builds only)
-  double zq = cooph_factor<NB>(U, rowbuf, Wbuf, scr, wave, lane, pa, Ts, dvec);
-#else
   // dataflow-synchronised (tile_f64.hpp, cooph_factor_df): the E slots are dead now - second row buffer and the W of every step
   static_assert(CAP >= 3 * NB, "E slots too small for the factorisation's buffers");
   double zq = cooph_factor_df<NB>(U, rowbuf, Ec, Ec + NB * 256, Ec + 2 * NB * 256, scr, slotblk, wave, lane, pa, Ts, dvec);
-#endif
   int info;
   const double ld = cooph_logdet_info<NB>(pa, wave, lane, red, redi, info);
   zq = wave_sum(zq);
@@ -1156,7 +1113,6 @@ int launch_pairs(const PairsArgs& a0, hipStream_t st) {
 int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t st) {
   if (coop) {   // NB/2 waves per pair (CoopH)
     switch (NB) {
-      case 8: return launch_pairs_cooph<8>(a, st);
       case 12: return launch_pairs_cooph<12>(a, st);
       default: return launch_pairs_cooph<16>(a, st);
     }

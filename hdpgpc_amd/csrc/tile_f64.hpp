@@ -11,7 +11,7 @@
 // Hence  mfma(X.v[s], Y.v[s]) summed over s = X^T Y, which is exactly the trailing update of an
 // UPPER-form Cholesky  A = U^T U  (U_KJ tiles, K <= J):   A_IJ -= U_KI^T U_KJ.
 //
-// Only the 16x16 diagonal blocks need cross-lane work (diag16 below); every other flop is MFMA.
+// Only the 16x16 diagonal blocks need cross-lane work (diag16_acc below); every other flop is MFMA.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -196,187 +196,6 @@ __device__ __forceinline__ double lane_bcast(double v, int src) {
   return __hiloint2double(hi, lo);
 }
 
-// ---------------------------------------------------------------------------------------------
-// diag16: Cholesky of one 16x16 diagonal block AND the inverse of its factor, by one wave.
-//   in : X  (acc layout, the full symmetric block: the lower triangle must hold finite numbers)
-//   out: returns W = L^{-1} (L = U^T lower) in A-operand layout, w[s] = W[c][4s+g];
-//        if Lout != nullptr the wave writes L (zeros above the diagonal) for rows/cols < nvalid.
-// Blocked 4 x 4 inside the tile so that the O(16^3) part runs on the matrix core too.  Register r of an acc tile holds
-// rows 4r..4r+3 (row 4r+g in lane group g), which is at once the B operand "rows 4r.. of X" and the A operand
-// "columns 4r.. of X^T".  Round r:
-//   (1) the 10 upper entries of the 4x4 pivot block go to SGPRs (v_readlane); every lane factors it and lane group g
-//       solves column g of its inverse W4 = L44^{-1} (uniform instruction stream, 4 dependent rsqrt);
-//   (2) one MFMA per tile with A = W4 placed at rows 4r.. replaces rows 4r.. of X (and of Z, which starts as I) by
-//       the finished rows of U (of L^{-1});
-//   (3) one MFMA per tile subtracts the rank-4 product from the rows below (A operand masked to those rows).
-// 16 MFMA + 4 short scalar chains per block instead of 16 elimination steps of 15 v_readlane + 15 v_fma each:
-// 4.2k cycles per block in isolation (tools/probe_diag16.hip), bounded by the pivot chain (about 38 dependent fp64 ops per round).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ d4 diag16(const d4& Xin, double* scr, int lane, PivotAcc& pa, int col0,
-                                     double* Lout, int ldl, int nvalid) {
-  const int g = lane >> 4, c = lane & 15;
-#ifdef HGP_EXP_NODIAG   // in-situ knock-out experiment (diagnostic builds only): W = diag(1 / sqrt(x_ii)), no pivot chain
-  {
-    d4 w;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) w[s] = (4 * s + g == c) ? 1.0 / sqrt(fabs(Xin[s]) + 1.0) : 0.0;
-    pa.mant *= 1.0 + 1e-300 * Xin[0];
-    return w;
-  }
-#endif
-#ifdef HGP_STAMPS
-  const unsigned long long td0 = __builtin_readcyclecounter();
-#endif
-  d4 X = Xin, Z;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) Z[r] = (4 * r + g == c) ? 1.0 : 0.0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int b0 = 4 * r;
-    // X[4r+i][4r+j] lives in register r of lane 16 i + 4r + j
-    const double x00 = lane_bcast(X[r], b0), x01 = lane_bcast(X[r], b0 + 1), x02 = lane_bcast(X[r], b0 + 2),
-                 x03 = lane_bcast(X[r], b0 + 3), x11 = lane_bcast(X[r], 16 + b0 + 1), x12 = lane_bcast(X[r], 16 + b0 + 2),
-                 x13 = lane_bcast(X[r], 16 + b0 + 3), x22 = lane_bcast(X[r], 32 + b0 + 2),
-                 x23 = lane_bcast(X[r], 32 + b0 + 3), x33 = lane_bcast(X[r], 48 + b0 + 3);
-    const double p0 = x00;
-    const double r0 = rsqrt_nr(p0);
-    const double u01 = x01 * r0, u02 = x02 * r0, u03 = x03 * r0;
-    const double p1 = fma(-u01, u01, x11);
-    const double r1 = rsqrt_nr(p1);
-    const double u12 = fma(-u01, u02, x12) * r1, u13 = fma(-u01, u03, x13) * r1;
-    const double p2 = fma(-u12, u12, fma(-u02, u02, x22));
-    const double r2 = rsqrt_nr(p2);
-    const double u23 = fma(-u12, u13, fma(-u02, u03, x23)) * r2;
-    const double p3 = fma(-u23, u23, fma(-u13, u13, fma(-u03, u03, x33)));
-    const double r3 = rsqrt_nr(p3);
-    // (a division-free Bareiss form of this block - scaled Schur complements by multiplications only, the four 1/sqrt side by
-    // side - was measured in round 2: 5.6 k instead of 4.2 k cycles per block.  The block is bound by the NUMBER of fp64
-    // instructions, ~4.6 cycles each at one wave per SIMD, not by the latency of the pivot chain.)
-    // NaN compares false; a bad pivot then poisons the outputs with NaN, info says where
-    if (pa.info == 0) {
-      if (!(p0 > 0.0)) pa.info = col0 + b0 + 1;
-      else if (!(p1 > 0.0)) pa.info = col0 + b0 + 2;
-      else if (!(p2 > 0.0)) pa.info = col0 + b0 + 3;
-      else if (!(p3 > 0.0)) pa.info = col0 + b0 + 4;
-    }
-    pa.mant *= (p0 * p1) * (p2 * p3);   // four pivots between renormalisations: no over/underflow for |log2 piv| < 250
-    pa.renorm();
-    // column g of W4 = L44^{-1}: forward substitution of e_g (L44 = U44^T)
-    const double e0 = (g == 0) ? 1.0 : 0.0, e1 = (g == 1) ? 1.0 : 0.0, e2 = (g == 2) ? 1.0 : 0.0, e3 = (g == 3) ? 1.0 : 0.0;
-    const double w0 = e0 * r0;
-    const double w1 = fma(-u01, w0, e1) * r1;
-    const double w2 = fma(-u12, w1, fma(-u02, w0, e2)) * r2;
-    const double w3 = fma(-u23, w2, fma(-u13, w1, fma(-u03, w0, e3))) * r3;
-    // A operand: A[i][kk] = W4[i - 4r][kk] for 4r <= i < 4r + 4, else 0; lane (g, c) holds A[c][g]
-    const int ci = c & 3;
-    double aw = (ci == 0) ? w0 : (ci == 1) ? w1 : (ci == 2) ? w2 : w3;
-    aw = ((c >> 2) == r) ? aw : 0.0;
-    d4 tX = X, tZ = Z;
-    tX[r] = 0.0;
-    tZ[r] = 0.0;
-    tX = mfma(aw, X[r], tX);   // rows 4r.. := W4 * rows 4r..  (the other rows pass through)
-    tZ = mfma(aw, Z[r], tZ);
-    if (r < 3) {
-      const double am = (c >= b0 + 4) ? tX[r] : 0.0;   // rows below the pivot block only
-      X = mfma_sub(am, tX[r], tX);
-      Z = mfma_sub(am, tZ[r], tZ);
-    } else {
-      X = tX;
-      Z = tZ;
-    }
-  }
-  if (Lout != nullptr && c < nvalid) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 4 * r + g;                                  // L[c][i] = U[i][c]
-      if (i < nvalid) Lout[(size_t)c * ldl + i] = (i <= c) ? X[r] : 0.0;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) scr[(4 * r + g) * DIAG_LD + c] = Z[r];   // Z[i][j], i = 4r+g, j = c
-  __builtin_amdgcn_wave_barrier();
-  d4 w;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) w[s] = scr[c * DIAG_LD + 4 * s + g];                // W[c][4s+g]
-  __builtin_amdgcn_wave_barrier();
-#ifdef HGP_STAMPS
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  pa.diag_cycles += __builtin_readcyclecounter() - td0;
-#endif
-  return w;
-}
-
-// The all-VALU form of the same block (column j of U in lane j, column j of Z = L^{-1} in lane 16 + j, 16 elimination
-// steps of 15 v_readlane + 15 v_fma): the same ~4.2k cycles in isolation (tools/probe_diag16.hip) with ~20 fewer live
-// registers, which is what the T = 128 single-matrix kernel (k_wave_score1<8>, 36 resident tiles) needs to avoid spills.
-// Round 2 measured two rewrites of the elimination loop, both correct, neither faster (isolation 4.19 / 4.38 k cycles against
-// 4.27 k; inside k_pairs<8> 1.548 / 1.573 ms against 1.535 ms) and both removed: (a) the multiplier broadcast inside the
-// FMA (v_fmac_f64_dpp row_newbcast, the pivot row copied into row 1 of the wave by v_permlane16_swap): one instruction per
-// element instead of two v_readlane_b32 + one v_fma_f64, 35 % fewer instructions; (b) on top of it the division-free
-// (Bareiss) form with the sixteen 1/sqrt taken after the loop, one per lane.  The block costs ~260 cycles per pivot whatever
-// sits on the chain: a dependent fp64 VALU instruction issues ~25 cycles after its producer at one wave per SIMD.
-__device__ __forceinline__ d4 diag16_valu(const d4& X, double* scr, int lane, PivotAcc& pa, int col0,
-                                     double* Lout, int ldl, int nvalid) {
-  const int g = lane >> 4, c = lane & 15;
-#ifdef HGP_EXP_NODIAG   // in-situ knock-out experiment (diagnostic builds only)
-  {
-    d4 w;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) w[s] = (4 * s + g == c) ? 1.0 / sqrt(fabs(X[s]) + 1.0) : 0.0;
-    pa.mant *= 1.0 + 1e-300 * X[0];
-    return w;
-  }
-#endif
-#ifdef HGP_STAMPS
-  const unsigned long long td0 = __builtin_readcyclecounter();
-#endif
-#pragma unroll
-  for (int r = 0; r < 4; ++r) scr[(g + 4 * r) * DIAG_LD + c] = X[r];
-  __builtin_amdgcn_wave_barrier();
-  double v[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    double x = scr[i * DIAG_LD + c];                       // X[i][c]: column c (upper part is what matters)
-    double e = (c == i && lane < 32) ? 1.0 : 0.0;          // identity column for the Z lanes
-    v[i] = (lane < 16) ? x : e;
-  }
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const double piv = lane_bcast(v[k], k);                    // u_kk^2, fully updated
-    if (!(piv > 0.0) && pa.info == 0) pa.info = col0 + k + 1;  // NaN compares false; a bad pivot then poisons
-    pa.mant *= piv;                                            // the outputs with NaN, info says where
-    if ((k & 3) == 3) pa.renorm();       // four pivots between renormalisations: no over/underflow for |log2 piv| < 250
-    v[k] *= rsqrt_nr(piv);
-    // all broadcasts of the step first (distinct SGPR pairs), then the FMAs: the VALU->SGPR->VALU hazard of a
-    // readlane that feeds the very next instruction is paid once per step instead of once per element
-    double sb[16];
-#pragma unroll
-    for (int kp = k + 1; kp < 16; ++kp) sb[kp] = lane_bcast(v[k], kp);   // U[k][k'] (= L[k'][k])
-#pragma unroll
-    for (int kp = k + 1; kp < 16; ++kp) v[kp] = fma(-sb[kp], v[k], v[kp]);
-  }
-  if (Lout != nullptr && lane < 16 && lane < nvalid) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (i < nvalid) Lout[(size_t)lane * ldl + i] = (i <= lane) ? v[i] : 0.0;   // L[j][i] = U[i][j]
-  }
-  if (lane >= 16 && lane < 32) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) scr[i * DIAG_LD + c] = v[i];                     // Z[i][j], j = c
-  }
-  __builtin_amdgcn_wave_barrier();
-  d4 w;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) w[s] = scr[c * DIAG_LD + 4 * s + g];                // W[c][4s+g]
-  __builtin_amdgcn_wave_barrier();
-#ifdef HGP_STAMPS
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  pa.diag_cycles += __builtin_readcyclecounter() - td0;
-#endif
-  return w;
-}
-
 // 1/a (a != 0, normal range): v_rcp_f64 seed + ONE third-order step  y (1 + e + e^2),  e = 1 - a y  (seed error < 2^-22 ->
 // < 2^-66), three dependent operations after the seed instead of the four of two Newton steps.
 __device__ __forceinline__ double rcp_nr(double a) {
@@ -403,132 +222,28 @@ __device__ __forceinline__ int row16_sum_i32(int v) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// diag16_col (round 3): the column form of diag16_valu with a third of its instructions.  Measured first (tools/probe_lat.hip,
-// profiles/r03_probe_lat.txt): a dependent v_fma_f64 issues 9.5 cycles after its producer, v_rsq/v_rcp_f64 21, a v_readlane pair
-// feeding an FMA ~10, an LDS write -> read round trip 77; independent f64 VALU instructions issue every ~5 cycles.  The 4.2 k
-// cycles of diag16_valu are therefore its ~950 INSTRUCTIONS (two v_readlane_b32 per multiplier, a 7-instruction 1/sqrt, pivot
-// bookkeeping in every step), not its dependency chain (~100 cycles per pivot).  Here:
-//   * the rows stay UNSCALED Schur-complement rows S[k][.] during the elimination: step k publishes row k in LDS (one ds_write),
-//     multiplies the pivot row by 1/pivot (v_rcp + one third-order step: t = S[k][.] / p_k) and updates v[k'] -= S[k][k'] t with
-//     the multipliers S[k][k'] read back as LDS BROADCASTS (one ds_read2_b64 per two rows; only the multiplier of row k + 1,
-//     which carries the next pivot, comes through v_readlane so that the LDS round trip stays off the pivot chain);
-//   * the sixteen 1/sqrt(p_k) are ONE rsqrt sequence after the loop (lane c takes p_c = S[c][c] from the published rows), the row
-//     scaling of Z = L^{-1} happens in the final transposition (row c of W is lane-local), and the pivot product / the first bad
-//     pivot are one DPP reduction and one ballot instead of sixteen multiply / compare / renormalise groups.
-// Same interface and the same results up to rounding (the multipliers are S/p instead of (S/sqrt p)(S/sqrt p)).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ d4 diag16_col(const d4& X, double* scr, int lane, PivotAcc& pa, int col0,
-                                         double* Lout, int ldl, int nvalid) {
-  const int g = lane >> 4, c = lane & 15;
-#ifdef HGP_EXP_NODIAG   // in-situ knock-out experiment (diagnostic builds only)
-  {
-    d4 w;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) w[s] = (4 * s + g == c) ? 1.0 / sqrt(fabs(X[s]) + 1.0) : 0.0;
-    pa.mant *= 1.0 + 1e-300 * X[0];
-    return w;
-  }
-#endif
-#ifdef HGP_STAMPS
-  const unsigned long long td0 = __builtin_readcyclecounter();
-#endif
-  const bool zrole = (g & 1) != 0;   // lanes 16-31: column c of Z (starts as I); lanes 0-15: column c of X; 32-63 mirror 0-31
-#pragma unroll
-  for (int r = 0; r < 4; ++r) scr[(g + 4 * r) * DIAG_LD + c] = X[r];
-  if (lane < 16) scr[lane * DIAG_LD + 16] = 0.0;           // padding column 16 of the staging tile: what the Z lanes load
-  __builtin_amdgcn_wave_barrier();
-  double v[16];
-  {
-    const int cz = zrole ? 16 : c;                         // Z lanes read zeros, then get their 1.0 (one compare + one select per row)
-    const int ci = zrole ? c : -1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const double x = scr[i * DIAG_LD + cz];              // X[i][c]: column c (the upper part is what matters)
-      v[i] = __hiloint2double((ci == i) ? 0x3FF00000 : __double2hiint(x), __double2loint(x));
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  // the staging tile is dead: row k of the multipliers goes to scr[16 k ..] (LDS operations of one wave complete in order)
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    if (!zrole) scr[16 * k + c] = v[k];                    // S[k][c], unscaled
-    __builtin_amdgcn_wave_barrier();
-    const double piv = lane_bcast(v[k], k);
-    const double t = v[k] * rcp_nr(piv);
-    if (k + 1 < 16) {
-      const double m1 = lane_bcast(v[k], k + 1);           // the next pivot's row first, without the LDS round trip
-      v[k + 1] = fma(-m1, t, v[k + 1]);
-    }
-#pragma unroll
-    for (int kp = k + 2; kp < 16; ++kp) v[kp] = fma(-scr[16 * k + kp], t, v[kp]);
-  }
-  __builtin_amdgcn_wave_barrier();
-  const double pv = scr[16 * c + c];                       // p_c = S[c][c]
-  const double rc = rsqrt_nr(pv);                          // NaN for a pivot <= 0 (or NaN): poisons row c of W, info says where
-  {
-    const unsigned long long bad = __ballot(!(pv > 0.0)) & 0xffffull;
-    if (bad != 0 && pa.info == 0) pa.info = col0 + __ffsll((long long)bad);
-    pa.mant *= row16_prod(__builtin_amdgcn_frexp_mant(pv));      // sixteen mantissas in [0.5, 1): no underflow
-    pa.ex += row16_sum_i32(__builtin_amdgcn_frexp_exp(pv));
-    pa.renorm();
-  }
-  if (Lout != nullptr) {
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 16) scr[256 + lane] = rc;
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 16 && lane < nvalid) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-        if (i < nvalid) Lout[(size_t)lane * ldl + i] = (i <= lane) ? v[i] * scr[256 + i] : 0.0;   // L[j][i] = U[i][j] = r_i S[i][j]
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  if (lane >= 16 && lane < 32) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) scr[i * DIAG_LD + c] = v[i];                       // unscaled Z rows: Zs[i][j], j = c
-  }
-  __builtin_amdgcn_wave_barrier();
-  d4 w;
-#pragma unroll
-  for (int s = 0; s < 4; ++s) w[s] = scr[c * DIAG_LD + 4 * s + g] * rc;             // W[c][4s+g] = r_c Zs[c][4s+g]
-  __builtin_amdgcn_wave_barrier();
-#ifdef HGP_STAMPS
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  pa.diag_cycles += __builtin_readcyclecounter() - td0;
-#endif
-  return w;
-}
-
-// ---------------------------------------------------------------------------------------------
-// diag16_acc (round 3, third session): the elimination IN the accumulator layout, all 64 lanes busy.  The other VALU forms hold one
+// diag16_acc (round 3, third session): Cholesky of one 16x16 diagonal block AND the inverse of its factor, by one wave.
+//   in : X  (acc layout, the full symmetric block: the lower triangle must hold finite numbers)
+//   out: returns W = L^{-1} (L = U^T lower) in A-operand layout, w[s] = W[c][4s+g];
+//        if Lout != nullptr the wave writes L (zeros above the diagonal) for rows/cols < nvalid.
+// The elimination runs IN the accumulator layout, all 64 lanes busy.  The earlier VALU forms (removed) held one
 // column per lane (16 + 16 lanes, sixteen registers, 15 multiplier broadcasts + 15 FMAs per step: ~950 instructions per block, which
-// is what their ~4.2 k cycles are).  Here lane (g, c) keeps S[4r + g][c] in register r exactly as the MFMA left it - no staging
+// is what their ~4.2 k cycles were).  Here lane (g, c) keeps S[4r + g][c] in register r exactly as the MFMA left it - no staging
 // through LDS on the way in - and step k is a rank-1 update of the whole tile in (4 - k/4) FMAs:
 //   * the pivot p_k = S[k][k] goes through v_readlane (uniform, SGPR pair), 1/p_k by v_rcp_f64 + one third-order step;
-//   * row k is copied to the four 16-lane rows of the wave by v_permlane16_swap + v_permlane32_swap (s_k[c] in every lane (., c));
+//   * row k is copied to the four 16-lane rows of the wave through the wave's LDS scratch (s_k[c] in every lane (., c)): one
+//     ds_write2_b64, one ds_read2_b64, one ds_read_b64 (round 4; six ds_bpermute_b32 of round 3 were 3 088 against 2 811 cycles
+//     per block, k_pairs<8> 1.004 -> 0.991 ms); pinned instruction orders of the step were measured no faster and removed;
 //   * the multipliers S[i][k] of the rows below come from v_mov_dpp row_newbcast:k of the tile registers themselves (the Schur
 //     complement stays symmetric, so column k IS the multiplier column); rows of the pivot's own register that are already done
 //     get a zero multiplier through the DPP row mask;
 //   * Z (= I at the start) takes the same row operations with the same multipliers: Z[i][.] -= (S[i][k] / p_k) Z[k][.];
-//   * rows stay UNSCALED during the elimination (as in diag16_col): the sixteen 1/sqrt(p_k) are one rsqrt sequence at the end
+//   * rows stay UNSCALED during the elimination: the sixteen 1/sqrt(p_k) are one rsqrt sequence at the end
 //     (lane c holds p_c), the scaling of W = D^{-1/2} Z happens in the final transposition to the A-operand layout, the pivot
 //     product / first bad pivot are one DPP reduction and one ballot.
 // Finished rows are not protected: row k of S becomes ~0 after its step and only ever feeds itself again (dead rows and columns
 // of the symmetric Schur complement never reach a live entry).  ~470 instructions per block, dependency chain ~80 cycles per pivot.
-// Same interface as the other forms; results agree to rounding (multipliers S/p instead of (S/sqrt p)(S/sqrt p)).
 // ---------------------------------------------------------------------------------------------
-#ifndef HGP_DIAG_ROWCOPY
-#define HGP_DIAG_ROWCOPY 1   // 1 (shipped since round 4) = the three row copies of a pivot step through LDS memory: one ds_write2_b64, one
-                             // ds_read2_b64, one ds_read_b64 in the wave's scratch; 0 = six ds_bpermute_b32 (crossbar, no memory; round 3).
-                             // tools/probe_diag16: 2 811 vs 3 088 cycles per block; in the kernels (tools/ab_rowcopy.sh) k_pairs<8> 1.004 ->
-                             // 0.991 ms, k_pairs<6> 0.642 -> 0.616, cooph<16> 13.60 -> 13.37; results identical bit for bit
-#endif
-#ifndef HGP_DIAG_SCHED
-#define HGP_DIAG_SCHED 0     // 0 = the compiler's schedule; 4 = the pinned order below.  (Three other pinned orders, built on the ds_bpermute
-                             // form in round 4 - off-chain FMAs behind the broadcasts / crossbar instructions in one run / dealt two by
-                             // two into the reciprocal's gaps - measured 3 004 / 3 144 / 3 388 cycles per block against 3 088 and made no
-                             // difference inside the kernels: profiles/r04_ab_sched.txt; their code is gone.)
-#endif
 template <int G0>
 __device__ __forceinline__ double row_to_all(double v) {   // row G0 (16 lanes) of v copied to all four rows of the wave
   const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
@@ -579,20 +294,6 @@ __device__ __forceinline__ void elim_rest(double (&S)[4], double (&Z)[4], double
 #undef HGP_FD
 }
 
-// elim_rest one instruction at a time (I = 0 .. 5: S[RS+1], Z[RS+1], S[RS+2], Z[RS+2], ...; nothing beyond register 3), so that a
-// pinned order can place each where the pivot chain waits.  No s_nop: the DPP source (mrot) comes from an LDS read, never from
-// the VALU instruction in front (tools/check_dpp_hazard.py looks at the compiled stream).
-template <int RS, int I>
-__device__ __forceinline__ void rest_one(double (&S)[4], double (&Z)[4], double mrot, double nt, double ntz) {
-  constexpr int reg = RS + 1 + I / 2;
-  if constexpr (reg <= 3) {
-    if constexpr (I % 2 == 0)
-      asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(S[reg]) : "v"(mrot), "v"(nt), "n"(4 * reg));
-    else
-      asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(Z[reg]) : "v"(mrot), "v"(ntz), "n"(4 * reg));
-  }
-}
-
 struct NoBg {
   template <class KC>
   __device__ __forceinline__ void operator()(KC) const {}
@@ -603,15 +304,6 @@ template <class BG = NoBg>
 __device__ __forceinline__ d4 diag16_acc(const d4& X, double* scr, int lane, PivotAcc& pa, int col0,
                                          double* Lout, int ldl, int nvalid, BG&& bg = BG{}) {
   const int g = lane >> 4, c = lane & 15;
-#ifdef HGP_EXP_NODIAG   // in-situ knock-out experiment (diagnostic builds only)
-  {
-    d4 w;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) w[s] = (4 * s + g == c) ? 1.0 / sqrt(fabs(X[s]) + 1.0) : 0.0;
-    pa.mant *= 1.0 + 1e-300 * X[0];
-    return w;
-  }
-#endif
 #ifdef HGP_STAMPS
   const unsigned long long td0 = __builtin_readcyclecounter();
 #endif
@@ -629,69 +321,6 @@ __device__ __forceinline__ d4 diag16_acc(const d4& X, double* scr, int lane, Piv
   const int crot = (c + g) & 15;
   double p = lane_bcast(S[0], 0);
   double sk = row_to_all_bperm(S[0], 4 * c), mrot = row_to_all_bperm(S[0], 4 * crot), zk = row_to_all_bperm(Z[0], 4 * c);
-#if HGP_DIAG_SCHED == 4
-  // The step's instruction ORDER is pinned (a wave issues in order; every statement below is fenced by a scheduling barrier):
-  // behind the two FMAs that finish row k + 1 come its LDS copy and the pivot read, then v_rcp_f64 at once, and the off-chain FMAs of
-  // step k (one instruction each, rest_one) are dealt into the latency gaps of the reciprocal's dependent chain (v_rcp 21 cycles,
-  // each dependent f64 operation ~9.5, tools/probe_lat.hip) instead of sitting in one run in front of it.
-#define HGP_SB __builtin_amdgcn_sched_barrier(0)
-  asm("v_writelane_b32 %0, %1, %2" : "+v"(pvlo) : "s"(__double2loint(p)), "n"(0));
-  asm("v_writelane_b32 %0, %1, %2" : "+v"(pvhi) : "s"(__double2hiint(p)), "n"(0));
-  double rp = rcp_nr(p);
-  static_for<0, 15>([&](auto kc) {
-    constexpr int k = decltype(kc)::value, r0 = k >> 2, g0 = k & 3;
-    constexpr int RS = (g0 == 3) ? r0 + 1 : r0;                          // register of row k + 1
-    constexpr int RMF = (g0 == 3) ? 0xf : (0xf << (g0 + 1)) & 0xf;      // its rows below the pivot
-    if (Lout != nullptr) Us[r0] = (g == g0) ? sk : Us[r0];
-    const double nt = -(sk * rp), ntz = -(zk * rp), mr = mrot;
-    HGP_SB;
-    elim_crit<RS, RMF>(S, Z, mr, nt, ntz);
-    HGP_SB;
-    constexpr int k1 = k + 1, g1 = k1 & 3;
-    if constexpr (k1 < 15) {
-      scr[lane] = S[RS];
-      scr[64 + lane] = Z[RS];
-      __builtin_amdgcn_wave_barrier();
-    }
-    p = lane_bcast(S[RS], 16 * g1 + k1);
-    HGP_SB;
-    if constexpr (k1 < 15) {
-      sk = scr[16 * g1 + c];
-      zk = scr[64 + 16 * g1 + c];
-      mrot = scr[16 * g1 + crot];
-      __builtin_amdgcn_wave_barrier();
-      HGP_SB;
-      const double y = __builtin_amdgcn_rcp(p);
-      HGP_SB;
-      bg(kc);
-      HGP_SB;
-      rest_one<RS, 0>(S, Z, mr, nt, ntz);
-      rest_one<RS, 1>(S, Z, mr, nt, ntz);
-      HGP_SB;
-      const double e = fma(-p, y, 1.0);
-      HGP_SB;
-      rest_one<RS, 2>(S, Z, mr, nt, ntz);
-      HGP_SB;
-      const double ye = y * e, t = fma(y, e, y);
-      HGP_SB;
-      rest_one<RS, 3>(S, Z, mr, nt, ntz);
-      asm("v_writelane_b32 %0, %1, %2" : "+v"(pvlo) : "s"(__double2loint(p)), "n"(k1));
-      asm("v_writelane_b32 %0, %1, %2" : "+v"(pvhi) : "s"(__double2hiint(p)), "n"(k1));
-      HGP_SB;
-      rp = fma(ye, e, t);
-      HGP_SB;
-      rest_one<RS, 4>(S, Z, mr, nt, ntz);
-      rest_one<RS, 5>(S, Z, mr, nt, ntz);
-      HGP_SB;
-    } else {
-      asm("v_writelane_b32 %0, %1, %2" : "+v"(pvlo) : "s"(__double2loint(p)), "n"(k1));
-      asm("v_writelane_b32 %0, %1, %2" : "+v"(pvhi) : "s"(__double2hiint(p)), "n"(k1));
-      bg(kc);
-      elim_rest<RS>(S, Z, mr, nt, ntz);
-    }
-  });
-#undef HGP_SB
-#else
   static_for<0, 15>([&](auto kc) {
     constexpr int k = decltype(kc)::value, r0 = k >> 2, g0 = k & 3;
     constexpr int RS = (g0 == 3) ? r0 + 1 : r0;                          // register of row k + 1
@@ -705,7 +334,6 @@ __device__ __forceinline__ d4 diag16_acc(const d4& X, double* scr, int lane, Piv
     constexpr int k1 = k + 1, g1 = k1 & 3;
     p = lane_bcast(S[RS], 16 * g1 + k1);
     if constexpr (k1 < 15) {
-#if HGP_DIAG_ROWCOPY == 1
       // the row copies through LDS memory instead of the crossbar: one ds_write2_b64 + one ds_read2_b64 + one ds_read_b64 (64-bit)
       // in place of six ds_bpermute_b32 - three instructions fewer per pivot, at 77 instead of ~25 cycles of latency
       scr[lane] = S[RS];
@@ -715,18 +343,12 @@ __device__ __forceinline__ d4 diag16_acc(const d4& X, double* scr, int lane, Piv
       zk = scr[64 + 16 * g1 + c];
       mrot = scr[16 * g1 + crot];
       __builtin_amdgcn_wave_barrier();
-#else
-      sk = row_to_all_bperm(S[RS], 4 * (16 * g1 + c));
-      mrot = row_to_all_bperm(S[RS], 4 * (16 * g1 + crot));
-      zk = row_to_all_bperm(Z[RS], 4 * (16 * g1 + c));
-#endif
     }
     bg(kc);
     elim_rest<RS>(S, Z, mr, nt, ntz);
   });
   asm("v_writelane_b32 %0, %1, %2" : "+v"(pvlo) : "s"(__double2loint(p)), "n"(15));
   asm("v_writelane_b32 %0, %1, %2" : "+v"(pvhi) : "s"(__double2hiint(p)), "n"(15));
-#endif
   if (Lout != nullptr) Us[3] = (g == 3) ? S[3] : Us[3];
   // the pivots: lane c of row 0 holds p_c; every row needs it for the scaling of its part of W
   const double pv = row_to_all<0>(__hiloint2double(pvhi, pvlo));
@@ -764,28 +386,6 @@ __device__ __forceinline__ d4 diag16_acc(const d4& X, double* scr, int lane, Piv
   return w;
 }
 
-// Which 16 x 16 diagonal-block routine the factorisations use (A/B builds: -DHGP_DIAG_IMPL=0 restores rounds 1-2:
-// diag16_valu where the register budget asks for it, the MFMA-blocked diag16 elsewhere).
-#ifndef HGP_DIAG_IMPL
-#define HGP_DIAG_IMPL 3   // 3 = diag16_acc everywhere (shipped: k_pairs<8> 1.265 -> 1.121 ms, k_pairs<6> 0.757 -> 0.677, k_pairs_cooph<16> 7.39 -> 6.91 per 16 384 pairs);
-                          // 0 = rounds 1-2 (diag16_valu / MFMA-blocked diag16); 1 / 2 = diag16_col (measured SLOWER in the kernels: see diag16_col); 4 = diag16_acc for the VALU users only
-#endif
-template <bool VALU, class BG = NoBg>
-__device__ __forceinline__ d4 diag16_sel(const d4& X, double* scr, int lane, PivotAcc& pa, int col0, double* Lout, int ldl,
-                                         int nvalid, BG&& bg = BG{}) {
-#if HGP_DIAG_IMPL == 3
-  return diag16_acc(X, scr, lane, pa, col0, Lout, ldl, nvalid, bg);
-#elif HGP_DIAG_IMPL == 4
-  return VALU ? diag16_acc(X, scr, lane, pa, col0, Lout, ldl, nvalid) : diag16(X, scr, lane, pa, col0, Lout, ldl, nvalid);
-#elif HGP_DIAG_IMPL == 2
-  return diag16_col(X, scr, lane, pa, col0, Lout, ldl, nvalid);
-#elif HGP_DIAG_IMPL == 1
-  return VALU ? diag16_col(X, scr, lane, pa, col0, Lout, ldl, nvalid) : diag16(X, scr, lane, pa, col0, Lout, ldl, nvalid);
-#else
-  return VALU ? diag16_valu(X, scr, lane, pa, col0, Lout, ldl, nvalid) : diag16(X, scr, lane, pa, col0, Lout, ldl, nvalid);
-#endif
-}
-
 // ---------------------------------------------------------------------------------------------
 // Upper-form blocked Cholesky of an NB x NB tile matrix held in registers (upper tiles only),
 // right-looking, with ONE block column of 16 right-hand sides eliminated in the same sweep:
@@ -797,9 +397,6 @@ __device__ __forceinline__ d4 diag16_sel(const d4& X, double* scr, int lane, Piv
 // RHSMODE: 0 = none; 1 = one block column of 16 right-hand sides as MFMA tiles R[K]; 2 = ONE right-hand side kept
 // as a vector in LDS (dvec[16 NB], per wave) and eliminated on the VALU next to the MFMA stream: on exit dvec
 // holds z = L^{-1} d and the return value is z^T z (valid in every lane).
-#ifndef HGP_LOOKAHEAD
-#define HGP_LOOKAHEAD 1   // shipped since round 4 (tools/ab_look.sh: k_pairs<8> 0.998 -> 0.980 ms, k_pairs<6> 0.625 -> 0.612; bit-identical results); 0 = trailing update in one run
-#endif
 // The trailing-update MFMAs of block step Kp that wave_factor hands to diag16_acc of block Kp + 1 (look-ahead): every tile
 // (I, J), Kp < I <= J < NB, except (Kp + 1, Kp + 1) itself, which the next diagonal block needs first.  Operation q of the 4 NT:
 // k-step q / NT of tile q % NT (consecutive operations go to different accumulators); tiles in row-major order.
@@ -817,7 +414,7 @@ struct Pending {
     return I + u;
   }
 };
-template <int NB, int RHSMODE, bool DIAG_VALU = false, bool RHS_DEFER = false, bool LOOK = (HGP_LOOKAHEAD != 0)>
+template <int NB, int RHSMODE, bool RHS_DEFER = false>
 __device__ __forceinline__ double wave_factor(d4 (&U)[NB * (NB + 1) / 2], d4 (&R)[NB], double* scr, double* Wlds,
                                               double* dvec, int lane_in, PivotAcc& pa, double* Lout, int ldl, int n) {
   constexpr bool RHS = (RHSMODE == 1);
@@ -834,11 +431,12 @@ __device__ __forceinline__ double wave_factor(d4 (&U)[NB * (NB + 1) / 2], d4 (&R
     const int g = lane >> 4, c = lane & 15;
     double* Ld = (Lout != nullptr) ? Lout + (size_t)(16 * K) * ldl + 16 * K : nullptr;
     d4 W;
-    if constexpr (LOOK && K > 0 && K + 1 < NB) {
+    if constexpr (K > 0 && K + 1 < NB) {
       // look-ahead: the pivot chain of the diagonal block leaves the f64 pipe idle while it waits for its LDS round trips
       // (~130 of ~165 cycles per pivot); the trailing-update MFMAs of step K - 1 that this block does not depend on fill it
+      // (round 4: k_pairs<8> 0.998 -> 0.980 ms, k_pairs<6> 0.625 -> 0.612, bit-identical)
       using P = Pending<NB, K - 1>;
-      W = diag16_sel<DIAG_VALU>(U[tix(K, K, NB)], scr, lane, pa, 16 * K, Ld, ldl, n - 16 * K, [&](auto kc) {
+      W = diag16_acc(U[tix(K, K, NB)], scr, lane, pa, 16 * K, Ld, ldl, n - 16 * K, [&](auto kc) {
         constexpr int k = decltype(kc)::value, q0 = k * P::CH, q1 = (q0 + P::CH < P::N) ? q0 + P::CH : P::N;
         static_for<q0, q1>([&](auto qc) {
           constexpr int q = decltype(qc)::value, s = q / P::NT, t = q % P::NT, I = P::row(t), J = P::col(t);
@@ -846,7 +444,7 @@ __device__ __forceinline__ double wave_factor(d4 (&U)[NB * (NB + 1) / 2], d4 (&R
         });
       });
     } else {
-      W = diag16_sel<DIAG_VALU>(U[tix(K, K, NB)], scr, lane, pa, 16 * K, Ld, ldl, n - 16 * K);
+      W = diag16_acc(U[tix(K, K, NB)], scr, lane, pa, 16 * K, Ld, ldl, n - 16 * K);
     }
     if (Wlds != nullptr) {
 #pragma unroll
@@ -918,17 +516,16 @@ __device__ __forceinline__ double wave_factor(d4 (&U)[NB * (NB + 1) / 2], d4 (&R
         __builtin_amdgcn_wave_barrier();
       }
     }
-    // trailing update: A_IJ -= U_KI^T U_KJ  for K < I <= J  (and the rhs tiles I > K).  No look-ahead: on gfx950 the
-    // f64 MFMA and f64 VALU share the DP pipe (tools/probe_coexec.hip: 1 MFMA + 12 independent v_fma_f64 = 64 + 64 clk),
-    // so deferring these MFMAs into the VALU stream of the next diagonal block gains nothing (tried, measured).
-    // With LOOK only the next diagonal tile (and the rhs tiles) are updated here; the rest rides in the next diag16_acc (above).
+    // trailing update: A_IJ -= U_KI^T U_KJ  for K < I <= J  (and the rhs tiles I > K).  While a later block step takes the
+    // look-ahead (K + 2 < NB), only the next diagonal tile (and the rhs tiles) are updated here; the rest rides in the next
+    // diag16_acc (above).
 #pragma unroll
     for (int I = K + 1; I < NB; ++I) {
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
 #pragma unroll
         for (int J = I; J < NB; ++J) {
-          if (LOOK && K + 2 < NB && !(I == K + 1 && J == K + 1)) continue;
+          if (K + 2 < NB && !(I == K + 1 && J == K + 1)) continue;
           U[tix(I, J, NB)] = mfma_sub(U[tix(K, I, NB)][s], U[tix(K, J, NB)][s], U[tix(I, J, NB)]);
         }
         if (RHS) R[I] = mfma_sub(U[tix(K, I, NB)][s], R[K][s], R[I]);
@@ -1287,7 +884,7 @@ __device__ __forceinline__ double coop_factor(d4 (&U)[Coop<NB>::NT], double* row
     const int g = lane >> 4, c = lane & 15;
     if (wave == wK) {
       double* Ld = (Lout != nullptr) ? Lout + (size_t)(16 * K) * ldl + 16 * K : nullptr;
-      const d4 Wd = diag16_sel<false>(U[C::loc(K, qK)], scr, lane, pa, 16 * K, Ld, ldl, n - 16 * K);
+      const d4 Wd = diag16_acc(U[C::loc(K, qK)], scr, lane, pa, 16 * K, Ld, ldl, n - 16 * K);
 #pragma unroll
       for (int s = 0; s < 4; ++s) Wbuf[s * 64 + lane] = Wd[s];
       if (Wout != nullptr) {
@@ -1385,20 +982,11 @@ __device__ __forceinline__ double coop_factor(d4 (&U)[Coop<NB>::NT], double* row
       // R_I at the top of step I (Z_I = W R_I) with no workgroup barrier in between, so nobody else may write it.
       // (Until round 2 the rows were dealt round-robin, (I & 3) == wave, which differs from the snake ownership for
       // columns 4-7 and 12-15: a write/read race across waves that ~4 k cycles of diag16 slack hid, and that a build
-      // slowed by register spills lost - the "wrong rows in L^-1" of DESIGN 7; `make raceprobe` + tools/probe_coop_race.py
-      // reproduce it with an injected delay.)
+      // slowed by register spills lost - the "wrong rows in L^-1" of DESIGN 7.)
       const d4 zk = lds_tile_load(Rbuf, K, lane);
-#ifdef HGP_RACE_PROBE_DELAY
-      if (K + 1 < NB && ((K + 1) & 3) == wave && C::owner(K + 1) != wave)
-        for (int spin = 0; spin < 400; ++spin) __builtin_amdgcn_s_sleep(127);
-#endif
 #pragma unroll
       for (int I = K + 1; I < NB; ++I) {
-#ifdef HGP_RACE_PROBE_ROUNDROBIN
-        if ((I & 3) == wave) {
-#else
         if (C::owner(I) == wave) {
-#endif
           const d4 uki = lds_tile_load(rowbuf, I, lane);
           d4 ri = lds_tile_load(Rbuf, I, lane);
 #pragma unroll
@@ -1559,7 +1147,7 @@ __device__ __forceinline__ double cooph_factor(d4 (&U)[CoopH<NB>::NT], double* r
     const int lane = launder(lane_in);
     const int g = lane >> 4, c = lane & 15;
     if (wave == C::owner(K)) {
-      const d4 Wd = diag16_sel<false>(U[C::diag_slot(K)], scr, lane, pa, 16 * K, nullptr, 0, n - 16 * K);
+      const d4 Wd = diag16_acc(U[C::diag_slot(K)], scr, lane, pa, 16 * K, nullptr, 0, n - 16 * K);
 #pragma unroll
       for (int s = 0; s < 4; ++s) Wbuf[s * 64 + lane] = Wd[s];
       double p = 0.0;   // z_K = W d_K
@@ -1734,7 +1322,7 @@ __device__ __forceinline__ double cooph_factor_df(d4 (&U)[CoopH<NB>::NT], double
     const int g = lane >> 4, c = lane & 15;
     HGP_DF(4);
     __builtin_amdgcn_s_setprio(3);
-    const d4 Wd = diag16_sel<false>(U[C::diag_slot(K)], scr, lane, pa, 16 * K, nullptr, 0, n - 16 * K);
+    const d4 Wd = diag16_acc(U[C::diag_slot(K)], scr, lane, pa, 16 * K, nullptr, 0, n - 16 * K);
 #pragma unroll
     for (int s = 0; s < 4; ++s) Wall[(K * 4 + s) * 64 + lane] = Wd[s];
     if (Wpack != nullptr) *reinterpret_cast<d4*>(Wpack + ((size_t)K * 64 + lane) * 4) = Wd;
@@ -1829,9 +1417,6 @@ __device__ __forceinline__ double cooph_factor_df(d4 (&U)[CoopH<NB>::NT], double
     constexpr int HC = (K + 1 < C::NW) ? 0 : 1;                 // column (A / B) of block K + 1 in its owner's registers
     bool crit = false;
     if constexpr (K + 1 < NB) crit = (wave == C::owner(K + 1));
-#ifdef HGP_DF_NOCRIT
-    crit = false;
-#endif
     if constexpr (K + 1 < NB) {
       if (crit) {
         const d4 acc = panel_col(std::integral_constant<int, HC>{});
@@ -1875,11 +1460,6 @@ __device__ __forceinline__ double cooph_factor_df(d4 (&U)[CoopH<NB>::NT], double
           for (int s = 0; s < 4; ++s) U[C::slotB(I)] = mfma_sub(ucur[s], U[C::slotB(K)][s], U[C::slotB(I)]);
         }
       }
-#ifdef HGP_DF_NOCRIT
-      if constexpr (I == K + 1) {
-        if (wave == C::owner(I)) do_diag(std::integral_constant<int, I>{});
-      }
-#endif
     });
     df_publish(&tdone[wave], K + 1, lane_in);
   });

@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B of a variant library (arg 1) against the shipped one: whole GPU suite on the variant, then timings of both
+# A/B of a variant library (arg 1, e.g. built by tools/build_variant.sh) against the shipped one: whole GPU suite on the
+# variant, then timings of both
 set -o pipefail
 LIBV=$1
 O=gpurun_out

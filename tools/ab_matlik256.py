@@ -1,4 +1,4 @@
-"""a8 / a9 at T = 256, b = 256 exactly as bench.py measures them (for A/B runs with HGP_LIB / HGP_MATLIK_COOP4)."""
+"""a8 / a9 at T = 256, b = 256 exactly as bench.py measures them (for A/B runs with HGP_LIB)."""
 import os
 import sys
 

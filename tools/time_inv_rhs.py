@@ -1,6 +1,6 @@
 """Latency of ops.chol_inverse_rhs (the two inversions of the LDS member step) at small batches:
-    python tools/time_inv_rhs.py [T]        (HGP_INV_COOP_MAX_WG=0 in the environment selects the one-wave-per-panel kernel)
-Prints us per call for b = 2, 4, 8, 20, 40, 80 and a checksum of the outputs (the two kernels must agree bit for bit)."""
+    python tools/time_inv_rhs.py [T]
+Prints us per call for b = 2, 4, 8, 20, 40, 80 and a checksum of the outputs."""
 import hashlib
 import os
 import sys

@@ -1,5 +1,5 @@
 """a8 / a9 at T = 256 for the SMALL batches of the online step (a few items per call: latency, not throughput):
-    python tools/time_matlik_small.py        (HGP_MATLIK_COOP4=1: the four-wave kernels)"""
+    python tools/time_matlik_small.py"""
 import os
 import sys
 

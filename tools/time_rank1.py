@@ -1,5 +1,5 @@
 """k_chol_rank1 (rank-1 Cholesky update, BASELINE configs[4]'s kernel): ms per launch and HBM fraction at b factors of size T, and a
-checksum of the updated factors.   python tools/time_rank1.py [b] [T]      (HGP_RANK1_DIRECT=1: the uncoalesced row-per-thread form)"""
+checksum of the updated factors.   python tools/time_rank1.py [b] [T]      (odd T: the uncoalesced row-per-thread form)"""
 import hashlib
 import os
 import sys
