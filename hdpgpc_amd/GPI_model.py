@@ -20,7 +20,7 @@ from collections.abc import MutableSequence
 import numpy as np
 import torch
 
-from . import ops
+from . import chain_batch, ops
 from .GPI import IterativeGaussianProcess, RBFWhiteKernel
 
 f64 = torch.float64
@@ -180,7 +180,7 @@ class GPI_model:
 
     def __getstate__(self):
         """Host copies of the state; caches, pending status words and the online pool's slot are dropped."""
-        d = {k: v for k, v in self.__dict__.items() if k not in ("_stk", "_pending", "_graph_keepalive", "_slot", "_dyn", "theta_source",
+        d = {k: v for k, v in self.__dict__.items() if k not in ("_stk", "_pending", "_slot", "_dyn", "theta_source",
                                                                   "_Lobs", "_def_diag_key", "_def_diag", "_dyn_def")}
         cpu = lambda t: t.detach().cpu() if torch.is_tensor(t) else t           # noqa: E731
         for name in self._TENSOR_LISTS:
@@ -671,7 +671,7 @@ class GPI_model:
     # The eager methods above issue ~90 launches and one host sync per member: launch-bound.  For a run of members
     # (dynamic model, shared grid, h = 1, N >= 2) the step is restated on pre-allocated stacks with device-side
     # indices/counters and no host synchronisation, captured once with torch.cuda.CUDAGraph (hipGraph) and replayed per
-    # member; the RTS backward pass likewise.  Same arithmetic, same order.
+    # member by chain_batch; the RTS backward pass likewise.  Same arithmetic, same order.
     def _chain_alloc(self, n_more):
         T = self.x_basis.shape[0]
         L = len(self.f_star)
@@ -696,80 +696,19 @@ class GPI_model:
         ch["W"] = torch.stack((torch.stack((mi.m_mean, mo.m_mean)),
                                torch.stack((eye if mi.m_r_cov is None else mi.m_r_cov, eye if mo.m_r_cov is None else mo.m_r_cov)),
                                torch.stack((mi.scale, mo.scale)))).contiguous()
-        ch["ws"] = torch.empty(6 * T * T + 2 * T, dtype=f64, device=dev)     # gathered previous state (hgp_lds_chain_gather_f64)
-        ch["X5"] = torch.empty((5, T, T), dtype=f64, device=dev)             # Kalman P_k + the 4 inputs of the batched inverse
-        ch["y1s"] = torch.zeros((2, T, 1), dtype=f64, device=dev)            # (f_post, y) of the MNIW updates
-        ch["y2s"] = torch.zeros((2, T, 1), dtype=f64, device=dev)            # (f_sm_prev, f_post)
-        ch["I0"] = torch.stack((eye, torch.zeros_like(eye))).contiguous()    # addends of the batched (I - K C, -K Sigma)
+        ch["ws"] = torch.empty(6 * T * T + 2 * T, dtype=f64, device=dev)     # gathered previous state (hgp_lds_chain_gather2_batched_f64)
         ch["bad"] = torch.zeros(2, dtype=torch.int32, device=dev)          # [MNIW updates skipped, first step whose filter failed]
-        ch["sync"] = torch.zeros(1, dtype=torch.int32, device=dev)           # inter-block counter of hgp_lds_chain_finish_f64
+        ch["sync"] = torch.zeros(1, dtype=torch.int32, device=dev)           # inter-block counter of hgp_lds_chain_finish2_batched_f64
         return ch
 
-    def _chain_step(self, ch):
-        """One member (N >= 2 after it): include_sample + backwards_pair + bayesian_new_params on the stacks.
-
-        (Measured: running the three branches that only read the previous state - Kalman update, smoother gain, first
-        MNIW inverse - on separate streams, i.e. as parallel branches of the captured hipGraph, is SLOWER on ROCm 7.2:
-        1.03 ms instead of 0.77 ms per member.  One stream.)"""
-        mm = ops.gemm_batched
-        eye = self._eye()
-        T = eye.shape[0]
-        tt = T * T
-        pos = ch["pos"]
-        y1s, y2s, X5 = ch["y1s"], ch["y2s"], ch["X5"]
-        ws = ops.lds_chain_gather(ch["A"], ch["G"], ch["C"], ch["S"], ch["Psm"], ch["P"], ch["F"], ch["Fsm"], pos, ch["ws"],
-                                  Y=ch["Y"], y_row0=ch["y_row0"], y_out=y1s[1])
-        A, G, C, S, Psm, c0 = (ws[i * tt:(i + 1) * tt].view(T, T) for i in range(6))
-        m0, Fsm = ws[6 * tt:6 * tt + T].view(T, 1), ws[6 * tt + T:].view(T, 1)   # filtered / smoothed mean of the previous step
-        y = y1s[1]                                                              # the member's observation
-        n0 = ch["n0"]
-        means, Rs, scales = ch["W"][0], ch["W"][1], ch["W"][2]
-        # The three factorisations that only need the previous state go out as ONE batch of 4 single-matrix inverses
-        # (a 90 x 90 inverse is latency-bound: the launch costs the same with one matrix or four): A c0 A^T + G of
-        # backwards_pair, S of the Kalman update, and the two MNIW scale matrices.  X5 = [Pk, P, Sk, R0', R1'] holds the
-        # Kalman predictive covariance followed by the four inverse inputs; additions ride in the GEMM epilogues.
-        AP = mm(A, ws[4 * tt:6 * tt].view(2, T, T))                            # A P_sm and A c0 (A shared)
-        mm(AP, A, transB=True, add=G, out=X5[0:2])                             # predictive covariances of both
-        Pk, P = X5[0], X5[1]
-        Amf = mm(A, ws[6 * tt:].view(2, T, 1))                                 # A m0 and A f_sm (A shared)
-        Am0, xm = Amf[0], Amf[1]
-        f_pred = mm(C, xm)                                                     # pred_dist short-circuits on the shared grid
-        CPk = mm(C, Pk)
-        mm(CPk, C, transB=True, add=S, out=X5[2])
-        ops.add_diag_mean(Rs, scales, 1e-2, out=X5[3:5])
-        Z4, i4 = ops.chol_inverse(X5[1:5])
-        # (i4 is rewritten by every graph replay: hgp_lds_chain_finish_f64 latches a failure of i4[:2] in ch["bad"][1])
-        inv4 = mm(Z4, Z4, transA=True)
-        i1, scale_inv = i4[2:], inv4[2:]
-        # Kalman update (GPI.py:140-151, Joseph form).  P C^T is the transpose of the C P already formed for S (P is a
-        # covariance), so the gain is one transposed product: K = (C P)^T S^{-1}.
-        K_t = mm(CPk, inv4[1], transA=True)
-        f_post = mm(K_t, y - f_pred, add=xm, out=y1s[0])
-        KCS = mm(K_t, ws[2 * tt:4 * tt].view(2, T, T), alpha=-1.0, add=ch["I0"])   # (I - K C, -K Sigma) in one launch
-        IKC = KCS[0]
-        c_post = mm(KCS[1], K_t, transB=True, alpha=-1.0, add=mm(mm(IKC, Pk), IKC, transB=True))
-        # backwards_pair on the last two filtered states: J = c0 A^T P^{-1} = (A c0)^T P^{-1}
-        J = mm(AP[1], inv4[0], transA=True)
-        f_sm_prev = mm(J, f_post - Am0, add=m0, out=y2s[0])
-        y2s[1].copy_(f_post)
-        P_sm_prev = mm(mm(J, c_post - P), J, transB=True, add=c0)
-        ops.lds_chain_scatter(f_post, c_post, f_sm_prev, P_sm_prev, ch["F"], ch["Fsm"], ch["P"], ch["Psm"], pos)
-        # bayesian_new_params (one-step MNIW update; on a failed factorisation the previous distributions are kept):
-        # y1s = (f_post, y), y2s = (f_sm_prev, f_post)
-        S__ = mm(y2s, y2s, transB=True, add=scale_inv)
-        S_ = mm(y1s, y2s, transB=True, add=mm(means, scale_inv))
-        Zs, i2 = ops.chol_inverse(S__, 0.0, 1e-8)
-        part = mm(mm(S_, Zs, transB=True), Zs)
-        e = y1s - y2s
-        ops.lds_chain_finish(part, mm(e, e, transB=True), S__, i1, i2, ch["W"], n0, ch["Nf"], ch["bad"], ch["A"], ch["G"],
-                             ch["C"], ch["S"], pos, self.annealing, ch["sync"], info0=i4)
-
-    def _chain_lists(self, ch, views=None):
+    def _chain_lists(self, ch, views):
         """The member step as ONE launch per dependency level (hgp_chain.hip): every product of the step is an item of a
         device-resident list whose pointers are fixed for the life of the chain; the two inversions carry their right-hand
         sides.  14 launches per member, no torch arithmetic, no allocation (measured: a dependent launch costs ~4.5 us
         whatever it does, so launches - not flops - were the step's time).  128 < T <= 256: the inversions are the
-        cooperative inverse-only kernels and Z rhs is one more list level behind each of them (16 launches)."""
+        cooperative inverse-only kernels and Z rhs is one more list level behind each of them (16 launches).
+        views: this chain's slices of the inversion buffers and their status words, which chains that run side by side share
+        (one batched inversion for all of them)."""
         T = self.x_basis.shape[0]
         riding = T <= 128
         tt = T * T
@@ -778,9 +717,8 @@ class GPI_model:
         ws = ch["ws"]
         A, G, C, S, Psm, c0 = (ws[i * tt:(i + 1) * tt].view(T, T) for i in range(6))
         m0, Fsm = ws[6 * tt:6 * tt + T], ws[6 * tt + T:]
-        v = views or {}     # chain_batch.run hands out slices of buffers shared by many chains (one batched inversion for all)
-        X4, RH4, Z4, Y4 = (v[k] if k in v else new(4, T, T) for k in ("X4", "RH4", "Z4", "Y4"))   # [P, Sk, R0', R1'], riding RHS, Z, Z rhs
-        S__, S_, Zs, Y3 = (v[k] if k in v else new(2, T, T) for k in ("S__", "S_", "Zs", "Y3"))
+        X4, RH4, Z4, Y4 = (views[k] for k in ("X4", "RH4", "Z4", "Y4"))   # [P, Sk, R0', R1'], riding RHS, Z, Z rhs
+        S__, S_, Zs, Y3 = (views[k] for k in ("S__", "S_", "Zs", "Y3"))
         part = new(2, T, T)
         AP0, Pk, K_t, J, SINV, IKC, KS, MS, T1, KKt, KKtmP, c_post, CmP, X, P_sm_prev = (
             new(T, T), new(T, T), new(T, T), new(T, T), new(2, T, T), new(T, T), new(T, T), new(2, T, T), new(T, T), new(T, T),
@@ -831,39 +769,10 @@ class GPI_model:
             lvy[1].add(Zs[0], S_[0], Y3[0], transB=True)         # Z_s S_^T
             lvy[1].add(Zs[1], S_[1], Y3[1], transB=True)
             lv += lvy
-        if views is None:
-            for l_ in lv:
-                l_.finalize()
         ch["lv"], ch["riding"] = lv, riding
         ch["bufs"] = dict(X4=X4, RH4=RH4, Z4=Z4, Y4=Y4, S__=S__, S_=S_, Zs=Zs, Y3=Y3, part=part, y=y, f_post=f_post, c_post=c_post,
                           f_sm_prev=f_sm_prev, P_sm_prev=P_sm_prev)
-        ch["rhs_on"] = torch.tensor([1, 1, 0, 0], dtype=torch.int32, device=dev)
-        ch["i4"] = v["i4"] if "i4" in v else torch.zeros(4, dtype=torch.int32, device=dev)
-        ch["i2"] = v["i2"] if "i2" in v else torch.zeros(2, dtype=torch.int32, device=dev)
-
-    def _chain_step2(self, ch):
-        """_chain_step with one launch per dependency level; see _chain_lists."""
-        lv, b = ch["lv"], ch["bufs"]
-        ops.lds_chain_gather2(ch["A"], ch["G"], ch["C"], ch["S"], ch["Psm"], ch["P"], ch["F"], ch["Fsm"], ch["pos"], ch["ws"],
-                              ch["Y"], ch["y_row0"], b["y"], ch["W"], b["X4"][2:4])
-        for i in range(4):
-            lv[i].run()
-        if ch["riding"]:
-            ops.chol_inverse_rhs(b["X4"], b["Z4"], b["RH4"], b["Y4"], ch["i4"], rhs_on=ch["rhs_on"])
-        else:
-            ops.chol_inverse(b["X4"], out=b["Z4"], info=ch["i4"])
-            lv[10].run()
-        for i in range(4, 9):
-            lv[i].run()
-        if ch["riding"]:
-            ops.chol_inverse_rhs(b["S__"], b["Zs"], b["S_"], b["Y3"], ch["i2"], rhs_trans=True, add_diag=1e-8)
-        else:
-            ops.chol_inverse(b["S__"], 0.0, 1e-8, out=b["Zs"], info=ch["i2"])
-            lv[11].run()
-        lv[9].run()
-        ops.lds_chain_finish2(b["f_post"], b["c_post"], b["f_sm_prev"], b["P_sm_prev"], b["y"], b["part"], b["S__"], ch["i4"], ch["i2"],
-                              ch["W"], ch["n0"], ch["Nf"], ch["bad"], ch["A"], ch["G"], ch["C"], ch["S"], ch["F"], ch["Fsm"], ch["P"],
-                              ch["Psm"], ch["pos"], self.annealing, ch["sync"])
+        ch["i4"], ch["i2"] = views["i4"], views["i2"]
 
     def _chain_commit(self, ch, members, x_trains, y_trains):
         L = int(ch["pos"][0]) + 1
@@ -880,39 +789,6 @@ class GPI_model:
             self.y_train.append(y_trains[idx].reshape(-1, 1))
         self.N += len(members)
         self._stk = {}
-
-    def _run_graphed(self, fn, n_iter, unroll=1):
-        """Run fn() n_iter times: once eagerly (warm-up, counts as the first iteration), then `unroll` iterations captured ONCE
-        as a hipGraph and replayed (a replay costs ~8 us of launch gap, amortised over the unrolled iterations); the remainder
-        runs eagerly.  A failed capture or replay raises: silently re-running eagerly would both hide a 30x slow-down and,
-        after a partial replay, apply steps twice."""
-        if n_iter <= 0:
-            return
-        self._check_pending()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()                                        # warm-up iteration (counts as the first one)
-        torch.cuda.current_stream().wait_stream(side)
-        n_iter -= 1
-        if n_iter == 0:
-            return
-        unroll = max(1, min(int(unroll), n_iter))
-        graph = torch.cuda.CUDAGraph()
-        keep = self._pending
-        try:
-            with torch.cuda.graph(graph):
-                for _ in range(unroll):
-                    fn()
-        except RuntimeError as e:
-            raise RuntimeError(f"hipGraph capture of the LDS step failed: {e}") from e
-        self._pending = keep + self._pending            # info tensors written by every replay
-        for _ in range(n_iter // unroll):
-            graph.replay()
-        for _ in range(n_iter % unroll):
-            fn()
-        self.graph_replays = getattr(self, "graph_replays", 0) + n_iter // unroll
-        self._graph_keepalive = graph
 
     def _backwards_graphed(self):
         """GPI_model.backwards (full RTS) with the step captured once: index t runs down on the device."""
@@ -969,50 +845,26 @@ class GPI_model:
 
     def full_pass_weighted(self, x_trains, y_trains, resp, q=None, q_lat=None, snr=None, use_graphs=True):
         """GPI_model.py:377-406: filter / smooth / re-estimate over the members (resp > 0.99), then score everything.
-        With use_graphs (default) members beyond the first are processed by hipGraph replays of the captured step."""
-        x_trains = self.cond_to_torch(x_trains)
-        y_trains = self.cond_to_torch(y_trains)
-        resp = torch.as_tensor(resp)
-        dynamic = bool(torch.any(self.Gamma[-1] != 0))
-        active = torch.nonzero(resp > 0.99, as_tuple=False).reshape(-1).tolist()
-        if len(active) == 0:
+        With use_graphs (default) this is chain_batch.run over this one chain: members beyond the first go through hipGraph
+        replays of the captured member step where it covers the run (chain_batch._graphable), the eager methods otherwise."""
+        job = chain_batch.Job(self, x_trains, y_trains, resp, prev=(q, q_lat))
+        if use_graphs:
+            return chain_batch.run([job])[0]
+        if len(job.active) == 0:
             return q, q_lat
+        return self._full_pass_eager(self.cond_to_torch(x_trains), self.cond_to_torch(y_trains), job.resp, job.active)
+
+    def _full_pass_eager(self, x_trains, y_trains, resp, active):
+        """full_pass_weighted over the members `active` by the eager methods (device tensors x_trains, y_trains)."""
+        dynamic = bool(torch.any(self.Gamma[-1] != 0))
         hs = [float(resp[i]) for i in active]
-        X2 = x_trains[..., 0] if x_trains.ndim == 3 else x_trains
-        graphable = (use_graphs and dynamic and all(h == 1.0 for h in hs) and len(active) >= 4 and
-                     self.estimation_limit == np.inf and
-                     bool(torch.equal(X2[active], self.x_basis.reshape(1, -1).expand(len(active), -1))))
-        if graphable:
-            head = 1 if self.N == 0 else 0                  # the first member of a fresh model takes the eager path
-            for index in active[:head]:
-                self.include_weighted_sample(index, x_trains[index], x_trains[index], y_trains[index], 1.0)
-                self.backwards_pair(1.0)
-                self.bayesian_new_params(1.0)
-            rest = active[head:]
-            ch = self._chain_alloc(len(rest))
-            # observations of the run; the step reads row (pos - y_row0) inside its gather kernel
-            ch["Y"] = (y_trains[rest][..., 0] if y_trains.ndim == 3 else y_trains[rest]).reshape(len(rest), -1).contiguous()
-            ch["y_row0"] = int(ch["pos"][0])
-            if not ops.env_flag("HGP_CHAIN_PER_PRODUCT"):
-                self._chain_lists(ch)
-                self._run_graphed(lambda: self._chain_step2(ch), len(rest), unroll=8)
-            else:                                       # round-1 form, one launch per product: kept for comparison
-                self._run_graphed(lambda: self._chain_step(ch), len(rest))
-            self._chain_commit(ch, rest, x_trains, y_trains)
-            bad = ch["bad"].tolist()
-            if bad[1] != 0:      # torch.linalg.solve / inv of the reference would have raised at that member
-                raise torch.linalg.LinAlgError(f"posterior / backwards_pair: the input is not positive-definite (LDS step {bad[1]})")
-            if bad[0] != 0 and self.verbose:
-                print("Alg error matrix ill conditioned.")     # GPI_model.py:1069
-            self._backwards_graphed()
-        else:
-            for index, h in zip(active, hs):
-                self.include_weighted_sample(index, x_trains[index], x_trains[index], y_trains[index], h)
-                if dynamic:
-                    self.backwards_pair(h)
-                    self.bayesian_new_params(h)
+        for index, h in zip(active, hs):
+            self.include_weighted_sample(index, x_trains[index], x_trains[index], y_trains[index], h)
             if dynamic:
-                self.backwards()
+                self.backwards_pair(h)
+                self.bayesian_new_params(h)
+        if dynamic:
+            self.backwards()
         self._check_pending()
         self._stk = {}
         return self.compute_sq_err_all(x_trains, y_trains), self.compute_q_lat_all(x_trains)

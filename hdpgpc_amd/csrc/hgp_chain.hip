@@ -371,12 +371,7 @@ __device__ __forceinline__ void chain_gather2_body(const Gather2Args& a, double 
   }
 }
 
-__global__ __launch_bounds__(256) void k_chain_gather2(Gather2Args a) {
-  __shared__ double red[2][4];
-  chain_gather2_body(a, red);
-}
-
-// the same for a BATCH of independent chains: blockIdx.y = chain, one descriptor per chain in device memory
+// a BATCH of independent chains (one chain: n_chains = 1): blockIdx.y = chain, one descriptor per chain in device memory
 __global__ __launch_bounds__(256) void k_chain_gather2_b(const Gather2Args* __restrict__ descs) {
   __shared__ double red[2][4];
   const Gather2Args a = descs[blockIdx.y];
@@ -451,11 +446,6 @@ __device__ __forceinline__ void chain_finish2_body(const Finish2Args& a, int& la
     if (a.bad_count[1] == 0 && (a.info1[0] | a.info1[1]) != 0) a.bad_count[1] = (int32_t)nxt;
     a.sync[0] = 0;
   }
-}
-
-__global__ __launch_bounds__(256) void k_chain_finish2(Finish2Args a) {
-  __shared__ int last;
-  chain_finish2_body(a, last);
 }
 
 __global__ __launch_bounds__(256) void k_chain_finish2_b(const Finish2Args* __restrict__ descs) {
@@ -534,31 +524,6 @@ int hgp_chol_inverse_rhs_batched_f64(const double* A, int T, int b, double jitte
     case 6: launch_inv_rhs<6>(a, st); break;
     default: launch_inv_rhs<8>(a, st); break;
   }
-  return launch_status();
-}
-
-int hgp_lds_chain_gather2_f64(const double* stA, const double* stG, const double* stC, const double* stS, const double* stPsm,
-                              const double* stP, const double* stF, const double* stFsm, const int64_t* pos, int T, double* out,
-                              const double* Y, long y_row0, double* y_out, const double* W, double* Rp, void* stream) {
-  if (!stA || !stG || !stC || !stS || !stP || !stPsm || !stF || !stFsm || !pos || !out || !W || !Rp || T <= 0 || (Y && !y_out)) return -1;
-  Gather2Args a{{stA, stG, stC, stS, stPsm, stP, stF, stFsm}, pos, out, Y, y_out, W, Rp, y_row0, T};
-  const long total = 8L * T * T + 2L * T;
-  hipLaunchKernelGGL(k_chain_gather2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return launch_status();
-}
-
-int hgp_lds_chain_finish2_f64(int T, const double* f_post, const double* c_post, const double* f_sm_prev, const double* P_sm_prev,
-                              const double* y, const double* part, const double* Snew, const int32_t* info1, const int32_t* info2,
-                              double* W, double* n0, double* Nf, int32_t* bad_count, double* stA, double* stG, double* stC, double* stS,
-                              double* stF, double* stFsm, double* stP, double* stPsm, int64_t* pos, int annealing, int32_t* sync,
-                              void* stream) {
-  if (!f_post || !c_post || !f_sm_prev || !P_sm_prev || !y || !part || !Snew || !info1 || !info2 || !W || !n0 || !Nf || !bad_count ||
-      !stA || !stG || !stC || !stS || !stF || !stFsm || !stP || !stPsm || !pos || !sync || T <= 0)
-    return -1;
-  Finish2Args a{f_post, c_post, f_sm_prev, P_sm_prev, y, part, Snew, info1, info2, W, n0, Nf, bad_count,
-                stA, stG, stC, stS, stF, stFsm, stP, stPsm, pos, sync, T, annealing};
-  const long n2 = 2L * T * T;
-  hipLaunchKernelGGL(k_chain_finish2, dim3((unsigned)std::min<long>(64, (n2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return launch_status();
 }
 

@@ -1133,92 +1133,6 @@ __global__ __launch_bounds__(256, 2) void k_chol_rank1_pipe(Rank1Args a) {
   if (i == 0 && a.info) a.info[m] = s_info;
 }
 
-// ------------------------------------------------------------------ 8f-1: glue of the LDS chain step, fused
-// The captured per-member step (hdpgpc_amd/GPI_model.py: _chain_step) is a chain of small GEMMs and inverses; what sits
-// between them was ~75 element-wise / index launches of 3-5 us each.  Two kernels replace most of them.
-//
-// k_chain_gather: rows `pos` of the eight state stacks -> one contiguous workspace (A, G, C, S, Psm, P [T,T]; F, Fsm [T]),
-// and the observation of the member this step includes, Y[pos - y_row0], into y_out.
-struct ChainGatherArgs {
-  const double* st[8];   // A, G, C, S, Psm, P (T*T each), F, Fsm (T each)
-  const int64_t* pos;
-  double* out;           // [6 T T + 2 T]
-  int T;
-  const double* Y;       // [n,T] observations of the run (may be NULL)
-  long y_row0;
-  double* y_out;         // [T]
-};
-
-__global__ __launch_bounds__(256) void k_chain_gather(ChainGatherArgs a) {
-  const long tt = (long)a.T * a.T, p = a.pos[0];
-  const long total = 6 * tt + 2 * a.T;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    double v;
-    if (i < 6 * tt) {
-      const int w = (int)(i / tt);
-      v = a.st[w][p * tt + (i - w * tt)];
-    } else {
-      const long j = i - 6 * tt;
-      const int w = 6 + (int)(j / a.T);
-      v = a.st[w][p * a.T + (j - (long)(w - 6) * a.T)];
-    }
-    a.out[i] = v;
-  }
-  if (a.Y && blockIdx.x == 0)
-    for (int i = threadIdx.x; i < a.T; i += 256) a.y_out[i] = a.Y[(p - a.y_row0) * a.T + i];
-}
-
-// k_chain_scatter: the new filtered state and the re-smoothed previous one into the stacks (rows pos + 1 and pos).
-struct ChainScatterArgs {
-  const double* f_post;     // [T]
-  const double* c_post;     // [T,T]
-  const double* f_sm_prev;  // [T]
-  const double* P_sm_prev;  // [T,T]
-  double* stF;
-  double* stFsm;
-  double* stP;
-  double* stPsm;
-  const int64_t* pos;
-  int T;
-};
-
-__global__ __launch_bounds__(256) void k_chain_scatter(ChainScatterArgs a) {
-  const long tt = (long)a.T * a.T, p = a.pos[0], nx = p + 1;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tt; i += (long)gridDim.x * 256) {
-    const double c = a.c_post[i];
-    a.stP[nx * tt + i] = c;
-    a.stPsm[nx * tt + i] = c;
-    a.stPsm[p * tt + i] = a.P_sm_prev[i];
-    if (i < a.T) {
-      const double f = a.f_post[i];
-      a.stF[nx * a.T + i] = f;
-      a.stFsm[nx * a.T + i] = f;
-      a.stFsm[p * a.T + i] = a.f_sm_prev[i];
-    }
-  }
-}
-
-// out[b] = R[b] + factor * max(mean |diag S[b]|, eps) I   (the jitter of matrix_normal_inv_wishart.posterior,
-// GPI_model.py:1312-1316, taken from the CURRENT scale matrix)
-__global__ __launch_bounds__(256) void k_add_diag_mean(const double* __restrict__ R, const double* __restrict__ S, int T,
-                                                       double factor, double* __restrict__ out) {
-  __shared__ double red[256];
-  const long tt = (long)T * T;
-  const double* Sb = S + (size_t)blockIdx.x * tt;
-  double s = 0.0;
-  for (int i = threadIdx.x; i < T; i += 256) s += fabs(Sb[(size_t)i * T + i]);
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double jit = factor * fmax(red[0] / T, F64_EPS);
-  const double* Rb = R + (size_t)blockIdx.x * tt;
-  double* ob = out + (size_t)blockIdx.x * tt;
-  for (long i = threadIdx.x; i < tt; i += 256) ob[i] = Rb[i] + ((i / T == i % T) ? jit : 0.0);
-}
-
 // k_rts_chain: the sequential part of the RTS smoother (GPI.backward, GPI.py:240-270) for ALL steps in one launch.
 // The gains J_t, the predictive covariances P_t and A_t m_t only depend on the filtered states and are batched by the
 // caller; what remains is, for t = n-2 .. 0:
@@ -1393,76 +1307,6 @@ __global__ __launch_bounds__(64 * RTS_WAVES) void k_rts_chain(RtsArgs a) {
     __syncthreads();                         // LDS free for the next step; m_t visible
   }
 }
-
-// k_chain_finish: matrix_normal_inv_wishart.posterior's element-wise tail for BOTH updates (GPI_model.py:1326-1336),
-// the keep-previous rule on a failed factorisation (GPI_model.py:1068-1071), the annealed scales
-// (GPI_model.py:1083-1091), the append of A, Gamma, C, Sigma and the counters - one workgroup, one launch.
-struct ChainFinishArgs {
-  int T;
-  const double* part;     // [2,T,T]  S_ S__^{-1}
-  const double* ee;       // [2,T,T]  (y1 - y2)(y1 - y2)^T
-  const double* Snew;     // [2,T,T]  S__ (the new right covariance)
-  const int32_t* info1;   // [2]
-  const int32_t* info2;   // [2]
-  const int32_t* info0;   // [2] or NULL: status of the Kalman / pair-smoother factorisations of this step
-  double* W;              // [3,2,T,T] means, R, scales (in/out)
-  double* n0;             // device scalars (in/out)
-  double* Nf;
-  int32_t* bad_count;
-  double* stA;            // stacks [L,T,T]: row pos + 1 is written
-  double* stG;
-  double* stC;
-  double* stS;
-  int64_t* pos;           // in/out: += 1
-  int annealing;
-  int32_t* sync;          // one zero-initialised counter (left zero)
-};
-
-#pragma clang fp contract(off)   // the reference's op order, no fused multiply-adds
-__global__ __launch_bounds__(256) void k_chain_finish(ChainFinishArgs a) {
-  __shared__ int last;
-  const long tt = (long)a.T * a.T;
-  const bool bad = (a.info1[0] | a.info1[1] | a.info2[0] | a.info2[1]) != 0;
-  const double n0 = a.n0[0], Nf = a.Nf[0] + 1.0;
-  const long nxt = a.pos[0] + 1;
-  const double n0n = bad ? n0 : n0 + 1.0;
-  const double scl = n0n / (n0n - 2.0);
-  const double ann = a.annealing ? 1.0 / (Nf * Nf) : 0.0;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < 2 * tt; i += (long)gridDim.x * 256) {
-    double m = a.W[i], r = a.W[2 * tt + i], sc = a.W[4 * tt + i];
-    if (!bad) {
-      m = ((n0 - 2.0) * m + a.part[i]) / (n0 - 1.0);
-      r = a.Snew[i];
-      sc = ((n0 - 2.0) * sc + a.ee[i]) / (n0 - 1.0);
-      a.W[i] = m;
-      a.W[2 * tt + i] = r;
-      a.W[4 * tt + i] = sc;
-    }
-    const bool obs = i >= tt;           // item 0 = internal (A, Gamma), item 1 = observation (C, Sigma)
-    const long e = obs ? i - tt : i;
-    (obs ? a.stC : a.stA)[nxt * tt + e] = m;
-    double* sg = obs ? a.stS : a.stG;
-    sg[nxt * tt + e] = sc * scl + sg[e] * ann;
-  }
-  // the scalars are rewritten by whichever block finishes last: every block has read them by then
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    last = (atomicAdd(a.sync, 1) == (int)gridDim.x - 1);
-  }
-  __syncthreads();
-  if (last && threadIdx.x == 0) {
-    a.n0[0] = n0n;
-    a.Nf[0] = Nf;
-    a.bad_count[0] += bad ? 1 : 0;
-    // bad_count[1]: 1-based index of the first step whose Kalman / smoother factorisation failed (0 = none) - the info
-    // tensors themselves are overwritten by every graph replay
-    if (a.info0 && a.bad_count[1] == 0 && (a.info0[0] | a.info0[1]) != 0) a.bad_count[1] = (int32_t)nxt;
-    a.pos[0] = nxt;
-    a.sync[0] = 0;
-  }
-}
-#pragma clang fp contract(on)
 
 // a10 (reference as written, GPI.py:1043): || G^{-1} y ||^2 with G = tril(K) used as if it were a Cholesky factor.
 // One workgroup, column-oriented forward substitution in LDS; T <= 2048.
@@ -2305,31 +2149,6 @@ int hgp_chol_rank1_f64(double* L, const double* v, const double* alpha, const do
   return launch_status();
 }
 
-int hgp_lds_chain_gather_f64(const double* stA, const double* stG, const double* stC, const double* stS, const double* stPsm,
-                             const double* stP, const double* stF, const double* stFsm, const int64_t* pos, int T,
-                             double* out, const double* Y, long y_row0, double* y_out, void* stream) {
-  if (!stA || !stG || !stC || !stS || !stP || !stPsm || !stF || !stFsm || !pos || !out || T <= 0 || (Y && !y_out)) return -1;
-  ChainGatherArgs a{{stA, stG, stC, stS, stPsm, stP, stF, stFsm}, pos, out, T, Y, y_row0, y_out};
-  const long total = 6L * T * T + 2L * T;
-  hipLaunchKernelGGL(k_chain_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return launch_status();
-}
-
-int hgp_lds_chain_scatter_f64(const double* f_post, const double* c_post, const double* f_sm_prev, const double* P_sm_prev,
-                              double* stF, double* stFsm, double* stP, double* stPsm, const int64_t* pos, int T, void* stream) {
-  if (!f_post || !c_post || !f_sm_prev || !P_sm_prev || !stF || !stFsm || !stP || !stPsm || !pos || T <= 0) return -1;
-  ChainScatterArgs a{f_post, c_post, f_sm_prev, P_sm_prev, stF, stFsm, stP, stPsm, pos, T};
-  hipLaunchKernelGGL(k_chain_scatter, dim3((unsigned)(((long)T * T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  return launch_status();
-}
-
-int hgp_add_diag_mean_f64(const double* R, const double* S, int T, int b, double factor, double* out, void* stream) {
-  if (!R || !S || !out || T <= 0 || b < 0) return -1;
-  if (b == 0) return 0;
-  hipLaunchKernelGGL(k_add_diag_mean, dim3(b), dim3(256), 0, (hipStream_t)stream, R, S, T, factor, out);
-  return launch_status();
-}
-
 int hgp_gemm_add_batched_f64(int transA, int transB, int M, int N, int Kd, double alpha, const double* A, int lda, long strideA,
                              const double* B, int ldb, long strideB, double beta, const double* D, int ldd, long strideD,
                              double* C, int ldc, long strideC, int batch, void* stream) {
@@ -2350,19 +2169,6 @@ int hgp_rts_chain_f64(const double* J, const double* P, const double* AM, double
   const size_t lds = sizeof(double) * (2 * 96 * 100 + 2 * 96);
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_rts_chain), lds)) return rc_;
   hipLaunchKernelGGL(k_rts_chain, dim3(1), dim3(64 * RTS_WAVES), lds, (hipStream_t)stream, a);
-  return launch_status();
-}
-
-int hgp_lds_chain_finish_f64(int T, const double* part, const double* ee, const double* Snew, const int32_t* info1,
-                             const int32_t* info2, const int32_t* info0, double* W, double* n0, double* Nf, int32_t* bad_count,
-                             double* stA, double* stG, double* stC, double* stS, int64_t* pos, int annealing, int32_t* sync,
-                             void* stream) {
-  if (!part || !ee || !Snew || !info1 || !info2 || !W || !n0 || !Nf || !bad_count || !stA || !stG || !stC || !stS || !pos ||
-      !sync || T <= 0)
-    return -1;
-  ChainFinishArgs a{T, part, ee, Snew, info1, info2, info0, W, n0, Nf, bad_count, stA, stG, stC, stS, pos, annealing, sync};
-  const long n2 = 2L * T * T;
-  hipLaunchKernelGGL(k_chain_finish, dim3((unsigned)std::min<long>(64, (n2 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return launch_status();
 }
 

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _ffi, ops
+from .chain_batch import _descs, finish_desc, gather_desc
 from .GPI_model import LOG2PI, StackList, matrix_normal_inv_wishart
 
 f64 = torch.float64
@@ -245,27 +246,12 @@ class OnlinePool:
     def _prepare(self):
         """Descriptor arrays of the gather / finish launches for the current slots (re-uploaded when a slot is added or its
         stacks move)."""
-        p = lambda t: ctypes.c_void_p(t.data_ptr())      # noqa: E731
         T = self.T
         gd, fd_dry, fd_real = [], [], []
         for c, sl in enumerate(self.slots):
-            ch, b = sl.ch, sl.ch["bufs"]
-            g = _ffi.ChainGatherDesc()
-            for i, k in enumerate(_STACKS):
-                g.st[i] = ch[k].data_ptr()
-            g.pos, g.out, g.Y, g.y_out, g.W, g.Rp = p(ch["pos"]), p(ch["ws"]), p(self.ybuf), p(b["y"]), p(ch["W"]), p(b["X4"][2:4])
-            g.y_row0, g.T = -1, T
-            gd.append(g)
-            for flags, bad, lst in ((2 | 4, self.badc_all[c], fd_dry), (4, self.bad_all[c], fd_real)):
-                f = _ffi.ChainFinishDesc()
-                f.f_post, f.c_post, f.f_sm_prev, f.P_sm_prev, f.y = p(b["f_post"]), p(b["c_post"]), p(b["f_sm_prev"]), p(b["P_sm_prev"]), p(b["y"])
-                f.part, f.Snew, f.info1, f.info2 = p(b["part"]), p(b["S__"]), p(ch["i4"]), p(ch["i2"])
-                f.W, f.n0, f.Nf, f.bad_count = p(ch["W"]), p(ch["n0"]), p(ch["Nf"]), p(bad)
-                f.stA, f.stG, f.stC, f.stS = p(ch["A"]), p(ch["G"]), p(ch["C"]), p(ch["S"])
-                f.stF, f.stFsm, f.stP, f.stPsm = p(ch["F"]), p(ch["Fsm"]), p(ch["P"]), p(ch["Psm"])
-                f.pos, f.sync, f.T, f.annealing = p(ch["pos"]), p(ch["sync"]), T, int(self.annealing) | flags
-                lst.append(f)
-        from .chain_batch import _descs
+            gd.append(gather_desc(sl.ch, T, self.ybuf, -1))
+            fd_dry.append(finish_desc(sl.ch, T, int(self.annealing) | 2 | 4, self.badc_all[c]))
+            fd_real.append(finish_desc(sl.ch, T, int(self.annealing) | 4, self.bad_all[c]))
         self.gdev, self.fdev_dry, self.fdev_real = _descs(gd, self.device), _descs(fd_dry, self.device), _descs(fd_real, self.device)
         self.riding = self.slots[0].ch["riding"]
         self.descs_dirty = False
@@ -278,7 +264,7 @@ class OnlinePool:
                    "chain_gather2_batched")
 
     def _step(self, lo, hi, dry, gather=True):
-        """The member step of slots [lo, hi): one launch per dependency level (GPI_model._chain_step2 for many chains)."""
+        """The member step of slots [lo, hi): one launch per dependency level (the step of chain_batch._run_group)."""
         if self.descs_dirty:
             self._prepare()
         T, k, sh = self.T, hi - lo, self.shared

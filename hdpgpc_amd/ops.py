@@ -406,27 +406,10 @@ def gemm_batched(A, B, transA=False, transB=False, alpha=1.0, add=None, beta=1.0
     return C if (A.dim() == 3 or B.dim() == 3) else C[0]
 
 
-def add_diag_mean(R, S, factor, out=None):
-    """out[b] = R[b] + factor * max(mean |diag S[b]|, eps) I  for [b,T,T] stacks (MNIW jitter, GPI_model.py:1312-1316)."""
-    R, S = _dev64(R, "R"), _dev64(S, "S")
-    b, T, _ = R.shape
-    if out is None:
-        out = torch.empty_like(R)
-    _ffi.check(_ffi.lib.hgp_add_diag_mean_f64(_ptr(R), _ptr(S), T, b, float(factor), _ptr(out), _stream()), "add_diag_mean")
-    return out
-
-
 def rts_chain(J, P, AM, M, Cv):
     """Sequential part of the RTS smoother for all steps in one launch (in place on M [n,T] and Cv [n,T,T]); T <= 96."""
     n, T = M.shape[0], Cv.shape[1]
     _ffi.check(_ffi.lib.hgp_rts_chain_f64(_ptr(J), _ptr(P), _ptr(AM), _ptr(M), _ptr(Cv), n, T, _stream()), "rts_chain")
-
-
-def lds_chain_scatter(f_post, c_post, f_sm_prev, P_sm_prev, stF, stFsm, stP, stPsm, pos):
-    """8f-1 glue: append the new filtered state (rows pos + 1) and overwrite the re-smoothed previous one (rows pos)."""
-    T = stP.shape[1]
-    _ffi.check(_ffi.lib.hgp_lds_chain_scatter_f64(_ptr(f_post), _ptr(c_post), _ptr(f_sm_prev), _ptr(P_sm_prev), _ptr(stF),
-                                                  _ptr(stFsm), _ptr(stP), _ptr(stPsm), _ptr(pos), T, _stream()), "lds_chain_scatter")
 
 
 def lat_error(f_cur, f_prev, A, Gamma, covprev):
@@ -483,24 +466,6 @@ def chol_rank1(L, v, alpha=None, beta=None):
     info = torch.zeros(b, dtype=torch.int32, device=L.device)
     _ffi.check(_ffi.lib.hgp_chol_rank1_f64(_ptr(L3), _ptr(v), _ptr(al), _ptr(be), T, b, _ptr(info), _stream()), "chol_rank1")
     return (L3 if L.dim() == 3 else L3[0]), info
-
-
-def lds_chain_gather(stA, stG, stC, stS, stPsm, stP, stF, stFsm, pos, out, Y=None, y_row0=0, y_out=None):
-    """8f-1 glue: row pos[0] of the eight state stacks -> out[6 T T + 2 T] (A, G, C, S, Psm, P, F, Fsm); optionally the
-    observation Y[pos[0] - y_row0] -> y_out."""
-    T = stA.shape[1]
-    _ffi.check(_ffi.lib.hgp_lds_chain_gather_f64(_ptr(stA), _ptr(stG), _ptr(stC), _ptr(stS), _ptr(stPsm), _ptr(stP), _ptr(stF),
-                                                 _ptr(stFsm), _ptr(pos), T, _ptr(out), _ptr(Y), int(y_row0), _ptr(y_out),
-                                                 _stream()), "lds_chain_gather")
-    return out
-
-
-def lds_chain_finish(part, ee, Snew, info1, info2, W, n0, Nf, bad_count, stA, stG, stC, stS, pos, annealing, sync, info0=None):
-    """8f-1 glue: element-wise tail of the two MNIW updates + append of A, Gamma, C, Sigma + counters (see the header)."""
-    T = stA.shape[1]
-    _ffi.check(_ffi.lib.hgp_lds_chain_finish_f64(T, _ptr(part), _ptr(ee), _ptr(Snew), _ptr(info1), _ptr(info2), _ptr(info0), _ptr(W), _ptr(n0),
-                                                 _ptr(Nf), _ptr(bad_count), _ptr(stA), _ptr(stG), _ptr(stC), _ptr(stS), _ptr(pos),
-                                                 int(bool(annealing)), _ptr(sync), _stream()), "lds_chain_finish")
 
 
 class GemmList:
@@ -609,25 +574,6 @@ def chol_inverse_rhs(A, Linv, rhs, rhs_out, info, rhs_on=None, rhs_trans=False, 
     _ffi.check(_ffi.lib.hgp_chol_inverse_rhs_batched_f64(_ptr(A), T, b, float(jitter_rel), float(add_diag), _ptr(Linv), _ptr(rhs),
                                                          _ptr(rhs_on), int(bool(rhs_trans)), _ptr(rhs_out), _ptr(info), _stream()),
                "chol_inverse_rhs")
-
-
-def lds_chain_gather2(stA, stG, stC, stS, stPsm, stP, stF, stFsm, pos, out, Y, y_row0, y_out, W, Rp):
-    """lds_chain_gather + the jittered right covariances Rp = W[1] + 1e-2 mean|diag W[2]| I of the two MNIW updates."""
-    T = stA.shape[1]
-    _ffi.check(_ffi.lib.hgp_lds_chain_gather2_f64(_ptr(stA), _ptr(stG), _ptr(stC), _ptr(stS), _ptr(stPsm), _ptr(stP), _ptr(stF),
-                                                  _ptr(stFsm), _ptr(pos), T, _ptr(out), _ptr(Y), int(y_row0), _ptr(y_out), _ptr(W),
-                                                  _ptr(Rp), _stream()), "lds_chain_gather2")
-
-
-def lds_chain_finish2(f_post, c_post, f_sm_prev, P_sm_prev, y, part, Snew, info1, info2, W, n0, Nf, bad_count, stA, stG, stC, stS, stF,
-                      stFsm, stP, stPsm, pos, annealing, sync):
-    """lds_chain_scatter + lds_chain_finish in one launch ((y1 - y2)(y1 - y2)^T formed inside)."""
-    T = stA.shape[1]
-    _ffi.check(_ffi.lib.hgp_lds_chain_finish2_f64(T, _ptr(f_post), _ptr(c_post), _ptr(f_sm_prev), _ptr(P_sm_prev), _ptr(y), _ptr(part),
-                                                  _ptr(Snew), _ptr(info1), _ptr(info2), _ptr(W), _ptr(n0), _ptr(Nf), _ptr(bad_count),
-                                                  _ptr(stA), _ptr(stG), _ptr(stC), _ptr(stS), _ptr(stF), _ptr(stFsm), _ptr(stP),
-                                                  _ptr(stPsm), _ptr(pos), int(bool(annealing)), _ptr(sync), _stream()),
-               "lds_chain_finish2")
 
 
 def trsv_lower_quad(G, y):

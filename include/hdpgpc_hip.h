@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define HGP_ABI_VERSION 6   /* 6: + hgp_chol_inverse_ws_f64, candidate / no-smoother flags of the chain finish; 5: + hgp_pairs_plan_set_score_output, hgp_debug_exp_neg_f64; 3: + hgp_pairs_plan_set_accuracy (solve-based per-pair path), assignment tail, warp fit, member-step lists; 4: + batched chain gather / finish */
+#define HGP_ABI_VERSION 6   /* 6: + hgp_chol_inverse_ws_f64, candidate / no-smoother flags of the chain finish, - the single-chain gather / scatter / finish glue and its jitter helper (one chain = n_chains 1 of the batched calls); 5: + hgp_pairs_plan_set_score_output, hgp_debug_exp_neg_f64; 3: + hgp_pairs_plan_set_accuracy (solve-based per-pair path), assignment tail, warp fit, member-step lists; 4: + batched chain gather / finish */
 /* largest T (basis length) and T* (segment length) served by the register-resident wave kernels */
 #define HGP_MAX_T_WAVE 128
 /* largest T served at all: 128 < T <= 256 runs on cooperative kernels (one workgroup of 4-8 waves per matrix / pair) */
@@ -182,46 +182,15 @@ int hgp_warp_cov_f64(const double* x, int T, double rho, double omega, double di
 int hgp_chol_rank1_f64(double* L, const double* v, const double* alpha, const double* beta, int T, int b, int32_t* info,
                        void* stream);
 
-/* 8f-1 (first "next" row) - glue of one member step of the LDS recursion (GPI_model.full_pass_weighted,
- * GPI_model.py:377-406), fused so that a captured step is GEMMs + inverses + two of these launches.
- * hgp_lds_chain_gather_f64: row pos[0] of the state stacks A, Gamma, C, Sigma, cov_f_sm, cov_f ([L,T,T]) and f_star,
- *   f_star_sm ([L,T]) into out[6 T T + 2 T] in that order (replaces the per-step list indexing of GPI_model.py:300-318);
- *   if Y != NULL also y_out[T] = Y[pos[0] - y_row0] (the observation of the member this step includes).
- * hgp_lds_chain_finish_f64: element-wise tail of the two matrix_normal_inv_wishart.posterior updates
- *   (GPI_model.py:1326-1336; item 0 = internal (A, Gamma), item 1 = observation (C, Sigma)):
- *     bad = any(info1, info2 != 0)                      (then the previous distributions are kept, GPI_model.py:1068-1071)
- *     means' = ((n0 - 2) means + part) / (n0 - 1);  R' = Snew;  scales' = ((n0 - 2) scales + ee) / (n0 - 1)
- *     n0' = n0 + 1 (unless bad);  Nf' = Nf + 1;  scl = n0' / (n0' - 2);  ann = annealing ? 1 / Nf'^2 : 0
- *     A[pos+1] = means'[0]; C[pos+1] = means'[1]; Gamma[pos+1] = scales'[0] scl + Gamma[0] ann; Sigma likewise
- *                                                        (bayesian_new_params, GPI_model.py:1076-1106)
- *     W = (means', R', scales') [3,2,T,T];  n0, Nf, bad_count[2], pos updated in place (pos += 1).
- *     bad_count[0] counts the steps that kept their previous distributions; info0[2] (may be NULL) is the status of the
- *     step's Kalman / pair-smoother factorisations: the first step (row index) where one failed is latched in bad_count[1].
- *     sync: one int32 the caller zero-initialises once (inter-block counter, left at zero). */
-int hgp_lds_chain_gather_f64(const double* stA, const double* stG, const double* stC, const double* stS, const double* stPsm,
-                             const double* stP, const double* stF, const double* stFsm, const int64_t* pos, int T,
-                             double* out, const double* Y, long y_row0, double* y_out, void* stream);
 /* hgp_rts_chain_f64: the sequential part of GPI.backward (GPI.py:240-270) for all n states in one launch, T <= 96
  * (-2 above).  J[n-1,T,T] = c_t A_t^T P_t^{-1}, P[n-1,T,T] = A_t c_t A_t^T + Gamma_t and AM[n-1,T] = A_t m_t come from
  * the FILTERED states (batched by the caller); in place, for t = n-2 .. 0:
  *     M[t] += J[t] (M[t+1] - AM[t]);   Cv[t] += J[t] (Cv[t+1] - P[t]) J[t]^T. */
 int hgp_rts_chain_f64(const double* J, const double* P, const double* AM, double* M, double* Cv, int n, int T, void* stream);
-/* hgp_lds_chain_scatter_f64: f_star[pos+1] = f_star_sm[pos+1] = f_post; cov_f[pos+1] = cov_f_sm[pos+1] = c_post
- *   (include_sample, GPI_model.py:317); f_star_sm[pos] = f_sm_prev, cov_f_sm[pos] = P_sm_prev (backwards_pair,
- *   GPI_model.py:705-716). */
-int hgp_lds_chain_scatter_f64(const double* f_post, const double* c_post, const double* f_sm_prev, const double* P_sm_prev,
-                              double* stF, double* stFsm, double* stP, double* stPsm, const int64_t* pos, int T, void* stream);
-/* out[b] = R[b] + factor * max(mean |diag S[b]|, eps) I  - the jitter matrix_normal_inv_wishart.posterior adds to the
- * right covariance before inverting it (GPI_model.py:1312-1316). */
-int hgp_add_diag_mean_f64(const double* R, const double* S, int T, int b, double factor, double* out, void* stream);
 /* C[b] = alpha op(A[b]) op(B[b]) + beta D[b]  (D: leading dimension ldd, batch stride strideD, 0 = shared). */
 int hgp_gemm_add_batched_f64(int transA, int transB, int M, int N, int Kd, double alpha, const double* A, int lda, long strideA,
                              const double* B, int ldb, long strideB, double beta, const double* D, int ldd, long strideD,
                              double* C, int ldc, long strideC, int batch, void* stream);
-int hgp_lds_chain_finish_f64(int T, const double* part, const double* ee, const double* Snew, const int32_t* info1,
-                             const int32_t* info2, const int32_t* info0, double* W, double* n0, double* Nf, int32_t* bad_count,
-                             double* stA, double* stG, double* stC, double* stS, int64_t* pos, int annealing, int32_t* sync,
-                             void* stream);
 
 /* 8f-1, one launch per dependency level of the member step.  hgp_gemm_list_f64 executes a DEVICE-resident list of
  * heterogeneous products  C = alpha op(A) op(B) + beta D (+ add_eye on the diagonal), any M x N x K, vectors as N = 1;
@@ -246,20 +215,15 @@ int hgp_gemm_list_mapped_f64(const hgp_gemm_item* items_dev, int n_items, const 
  * so that  B^T A^-1 = rhs_out^T Linv  costs ONE product after the factorisation (GPI.py:144-145,295; GPI_model.py:1329-1330). */
 int hgp_chol_inverse_rhs_batched_f64(const double* A, int T, int b, double jitter_rel, double add_diag, double* Linv, const double* rhs,
                                      const int32_t* rhs_on, int rhs_trans, double* rhs_out, int32_t* info, void* stream);
-/* hgp_lds_chain_gather_f64 plus the jittered right covariances of the two MNIW updates, Rp[2,T,T] = W[1] + 1e-2 max(mean|diag W[2]|, eps) I;
- * hgp_lds_chain_scatter_f64 + hgp_lds_chain_finish_f64 in one launch, with (y1 - y2)(y1 - y2)^T formed inside; info1[4] = status of
- * the first inversion (P, S_k, R0', R1'), info2[2] of the second. */
-int hgp_lds_chain_gather2_f64(const double* stA, const double* stG, const double* stC, const double* stS, const double* stPsm,
-                              const double* stP, const double* stF, const double* stFsm, const int64_t* pos, int T, double* out,
-                              const double* Y, long y_row0, double* y_out, const double* W, double* Rp, void* stream);
-int hgp_lds_chain_finish2_f64(int T, const double* f_post, const double* c_post, const double* f_sm_prev, const double* P_sm_prev,
-                              const double* y, const double* part, const double* Snew, const int32_t* info1, const int32_t* info2,
-                              double* W, double* n0, double* Nf, int32_t* bad_count, double* stA, double* stG, double* stC, double* stS,
-                              double* stF, double* stFsm, double* stP, double* stPsm, int64_t* pos, int annealing, int32_t* sync,
-                              void* stream);
-/* The same two launches for a BATCH of independent chains (clusters x leads x proposals of the variational loop: the recursion
- * is sequential per chain, so throughput comes from running many chains side by side): one descriptor per chain in DEVICE
- * memory, blockIdx.y = chain.  Field meaning as the arguments of the single-chain calls above. */
+/* 8f-1 (first "next" row) - the glue of one member step of the LDS recursion (GPI_model.full_pass_weighted,
+ * GPI_model.py:377-406), fused so that a captured step is the product lists + the two inversions above + two launches, gather
+ * and finish, for a BATCH of independent chains (clusters x leads x proposals of the variational loop: the recursion is
+ * sequential per chain, so throughput comes from running many chains side by side; one chain is n_chains = 1): one descriptor
+ * per chain in DEVICE memory, blockIdx.y = chain.
+ * hgp_lds_chain_gather2_batched_f64: row pos[0] of the state stacks A, Gamma, C, Sigma, cov_f_sm, cov_f ([L,T,T]) and f_star,
+ *   f_star_sm ([L,T]) into out[6 T T + 2 T] in that order (replaces the per-step list indexing of GPI_model.py:300-318); if
+ *   Y != NULL also y_out[T] = Y[pos[0] - y_row0] (the observation of the member this step includes); and the jittered right
+ *   covariances of the two MNIW updates, Rp[2,T,T] = W[1] + 1e-2 max(mean|diag W[2]|, eps) I (GPI_model.py:1312-1316). */
 typedef struct hgp_chain_gather_desc {
   const double* st[8];   /* stacks A, G, C, S, Psm, P ([L,T,T]), F, Fsm ([L,T]) */
   const int64_t* pos;
@@ -271,6 +235,20 @@ typedef struct hgp_chain_gather_desc {
   long y_row0;
   int T;
 } hgp_chain_gather_desc;
+/* hgp_lds_chain_finish2_batched_f64: the new filtered state and the re-smoothed previous one into the stacks,
+ *   f_star[pos+1] = f_star_sm[pos+1] = f_post, cov_f[pos+1] = cov_f_sm[pos+1] = c_post (include_sample, GPI_model.py:317),
+ *   f_star_sm[pos] = f_sm_prev, cov_f_sm[pos] = P_sm_prev (backwards_pair, GPI_model.py:705-716); then the element-wise tail of
+ *   the two matrix_normal_inv_wishart.posterior updates (GPI_model.py:1326-1336; item 0 = internal (A, Gamma) with
+ *   (y1, y2) = (f_post, f_sm_prev), item 1 = observation (C, Sigma) with (y1, y2) = (y, f_post)):
+ *     bad = any(info1[2..3], info2 != 0)                (then the previous distributions are kept, GPI_model.py:1068-1071)
+ *     means' = ((n0 - 2) means + part) / (n0 - 1);  R' = Snew;  scales' = ((n0 - 2) scales + (y1 - y2)(y1 - y2)^T) / (n0 - 1)
+ *     n0' = n0 + 1 (unless bad);  Nf' = Nf + 1;  scl = n0' / (n0' - 2);  ann = annealing ? 1 / Nf'^2 : 0
+ *     A[pos+1] = means'[0]; C[pos+1] = means'[1]; Gamma[pos+1] = scales'[0] scl + Gamma[0] ann; Sigma likewise
+ *                                                        (bayesian_new_params, GPI_model.py:1076-1106)
+ *     W = (means', R', scales') [3,2,T,T];  n0, Nf, bad_count[2], pos updated in place (pos += 1).
+ *   info1[4] = status of the first inversion (P, S_k, R0', R1'), info2[2] of the second.  bad_count[0] counts the steps that kept
+ *   their previous distributions; the first step (row index) whose Kalman / pair-smoother factorisation (info1[0..1]) failed is
+ *   latched in bad_count[1].  sync: one int32 the caller zero-initialises once (inter-block counter, left at zero). */
 typedef struct hgp_chain_finish_desc {
   const double* f_post; const double* c_post; const double* f_sm_prev; const double* P_sm_prev; const double* y;
   const double* part; const double* Snew;

@@ -48,6 +48,30 @@ def test_batched_chains_equal_sequential(sizes):
         assert ma.indexes == mb.indexes and ma.N == mb.N and float(ma.internal_params.n0) == float(mb.internal_params.n0)
 
 
+@pytest.mark.parametrize("T", [144, 256])
+def test_chain_above_128_graphed_equals_eager(T):
+    """128 < T <= 256: the graphed step inverts with the inverse-only kernels and forms Z rhs one list level later (no riding
+    right-hand sides).  One chain over beats of record 100 resampled to T, graphed and eager: every per-step list and both score
+    vectors agree to 1e-9, as in test_gpu_mirror_api.py::test_producer_step_forms_agree."""
+    y90 = golden("mitbih100_lead0.npz")["y"][:30]
+    t = np.linspace(0, y90.shape[1] - 1, T)
+    y = np.stack([np.interp(t, np.arange(y90.shape[1]), r) for r in y90])
+    N = y.shape[0]
+    x = np.repeat(np.arange(float(T))[None, :, None], N, axis=0)
+    members = [i for i in range(N) if i % 5 != 3]
+    resp = torch.zeros(N)
+    resp[members] = 1.0
+    states = []
+    for use_graphs in (True, False):
+        m = _models(1, T)[0]
+        q, q_lat = m.full_pass_weighted(x, y[:, :, None], resp, use_graphs=use_graphs)
+        assert m.indexes == members and (getattr(m, "graph_replays", 0) > 0) == use_graphs
+        states.append({k: torch.stack(list(getattr(m, k))).cpu().numpy() for k in ("f_star", "f_star_sm", "cov_f", "cov_f_sm", "A", "Gamma", "C", "Sigma")}
+                      | {"q": q.cpu().numpy(), "q_lat": q_lat.cpu().numpy()[members]})
+    for k, ref in states[0].items():
+        assert np.allclose(states[1][k], ref, rtol=1e-9, atol=1e-9 * max(np.abs(ref).max(), 1e-300)), k
+
+
 def test_batch_with_an_empty_and_a_tiny_chain():
     """A column without members hands back the previous scores; chains too short for the graphed path take the eager one."""
     from hdpgpc_amd import chain_batch

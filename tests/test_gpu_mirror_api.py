@@ -202,10 +202,10 @@ def test_producer_full_pass_weighted_reproduces_reference_state(tag, members):
     assert rel_err(q_lat.cpu().numpy()[members], g["q_lat"][members]) < 1e-9
 
 
-def test_producer_step_forms_agree(monkeypatch):
-    """The member step exists in three forms - one launch per dependency level (hgp_chain.hip, the default for T <= 128), one
-    launch per product (128 < T <= 256; HGP_CHAIN_PER_PRODUCT=1 forces it) and the eager methods (use_graphs=False).  They
-    order the same arithmetic differently (B^T A^-1 as (Z B)^T Z against B^T (Z^T Z)): every list must agree to 1e-9."""
+def test_producer_step_forms_agree():
+    """The member step exists in two forms - one launch per dependency level, replayed from hipGraphs (hgp_chain.hip driven by
+    chain_batch, the default) and the eager methods (use_graphs=False).  They order the same arithmetic differently (B^T A^-1 as
+    (Z B)^T Z against B^T (Z^T Z)): every list must agree to 1e-9."""
     g = golden("state_t45.npz")
     y = g["y"]
     n, T = y.shape
@@ -215,11 +215,7 @@ def test_producer_step_forms_agree(monkeypatch):
     resp = np.zeros(n)
     resp[members] = 1.0
     states = []
-    for form in ("levels", "products", "eager"):
-        if form == "products":
-            monkeypatch.setenv("HGP_CHAIN_PER_PRODUCT", "1")
-        else:
-            monkeypatch.delenv("HGP_CHAIN_PER_PRODUCT", raising=False)
+    for form in ("levels", "eager"):
         m = GPI_model(RBFWhiteKernel(300.0, 3.0, sigma * 1e-5), g["st_x_basis"][:, None], annealing=True, bayesian=True, free_deg_MNIV=5)
         cond = m.GPR_dynamic(gamma, sigma)
         m.initial_conditions(ini_A=cond[0], ini_Gamma=cond[1], ini_C=cond[2], ini_Sigma=cond[3])
@@ -363,13 +359,25 @@ def test_gemm_addend_epilogue_and_out():
     assert np.allclose(r2.cpu().numpy(), B.transpose(0, 2, 1) @ B + Dm, rtol=1e-12, atol=1e-12)
 
 
-def test_add_diag_mean_is_the_mniw_jitter():
+def test_chain_gather_forms_the_mniw_jitter():
+    """The member step's gather (hgp_lds_chain_gather2_batched_f64, one chain) writes the right covariances both MNIW updates
+    invert: Rp[b] = R[b] + 1e-2 max(mean |diag S[b]|, eps) I with W = (means, R, S) (GPI_model.py:1312-1316)."""
+    import ctypes
+
+    from hdpgpc_amd import _ffi, chain_batch
     rng = np.random.default_rng(22)
-    R, S = rng.normal(size=(2, 37, 37)), rng.normal(size=(2, 37, 37))
-    got = ops.add_diag_mean(dev(R), dev(S), 1e-2).cpu().numpy()
+    T = 37
+    R, S = rng.normal(size=(2, T, T)), rng.normal(size=(2, T, T))
+    z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")     # noqa: E731
+    ch = {k: z(1, T, T) for k in ("A", "G", "C", "S", "Psm", "P")} | {k: z(1, T, 1) for k in ("F", "Fsm")}
+    ch.update(pos=torch.zeros(1, dtype=torch.int64, device="cuda"), ws=z(6 * T * T + 2 * T), W=dev(np.stack([np.zeros_like(R), R, S])),
+              bufs={"y": z(T), "X4": z(4, T, T)})
+    descs = chain_batch._descs([chain_batch.gather_desc(ch, T, z(1, T), 0)], "cuda")
+    _ffi.check(_ffi.lib.hgp_lds_chain_gather2_batched_f64(ctypes.c_void_p(descs.data_ptr()), 1, T, ops._stream()), "gather")
+    got = ch["bufs"]["X4"][2:4].cpu().numpy()
     for b in range(2):
         jit = 1e-2 * max(np.mean(np.abs(np.diag(S[b]))), np.finfo(np.float64).eps)
-        assert np.allclose(got[b], R[b] + jit * np.eye(37), rtol=0, atol=1e-15)
+        assert np.allclose(got[b], R[b] + jit * np.eye(T), rtol=0, atol=1e-15)
 
 
 @pytest.mark.parametrize("T,n", [(90, 40), (33, 7), (96, 3)])
