@@ -20,7 +20,7 @@ from collections.abc import MutableSequence
 import numpy as np
 import torch
 
-from . import chain_batch, ops
+from . import ops
 from .GPI import IterativeGaussianProcess, RBFWhiteKernel
 
 f64 = torch.float64
@@ -667,129 +667,6 @@ class GPI_model:
             self.cov_f_sm[i + 1] = covs[i]
         self._stk = {}
 
-    # ---- the same recursion as capture-safe, buffer-based steps replayed as hipGraphs ----------------------------
-    # The eager methods above issue ~90 launches and one host sync per member: launch-bound.  For a run of members
-    # (dynamic model, shared grid, h = 1, N >= 2) the step is restated on pre-allocated stacks with device-side
-    # indices/counters and no host synchronisation, captured once with torch.cuda.CUDAGraph (hipGraph) and replayed per
-    # member by chain_batch; the RTS backward pass likewise.  Same arithmetic, same order.
-    def _chain_alloc(self, n_more):
-        T = self.x_basis.shape[0]
-        L = len(self.f_star)
-        dev = self.device
-
-        def stack(lst, shape):
-            buf = torch.empty((L + n_more,) + shape, dtype=f64, device=dev)
-            buf[:L] = lst.stack() if isinstance(lst, StackList) else torch.stack(lst)
-            buf[L:].zero_()
-            return buf
-
-        ch = {"F": stack(self.f_star, (T, 1)), "Fsm": stack(self.f_star_sm, (T, 1)), "P": stack(self.cov_f, (T, T)),
-              "Psm": stack(self.cov_f_sm, (T, T)), "A": stack(self.A, (T, T)), "G": stack(self.Gamma, (T, T)),
-              "C": stack(self.C, (T, T)), "S": stack(self.Sigma, (T, T))}
-        ch["pos"] = torch.tensor([L - 1], dtype=torch.int64, device=dev)
-        ch["Nf"] = torch.tensor([float(self.N)], dtype=f64, device=dev)
-        ch["n0"] = torch.tensor([float(self.internal_params.n0)], dtype=f64, device=dev)
-        eye = self._eye()
-        # the two MNIW distributions (internal, observation) as one tensor: W[0] = means, W[1] = right covariances,
-        # W[2] = scales, each [2,T,T]
-        mi, mo = self.internal_params, self.observation_params
-        ch["W"] = torch.stack((torch.stack((mi.m_mean, mo.m_mean)),
-                               torch.stack((eye if mi.m_r_cov is None else mi.m_r_cov, eye if mo.m_r_cov is None else mo.m_r_cov)),
-                               torch.stack((mi.scale, mo.scale)))).contiguous()
-        ch["ws"] = torch.empty(6 * T * T + 2 * T, dtype=f64, device=dev)     # gathered previous state (hgp_lds_chain_gather2_batched_f64)
-        ch["bad"] = torch.zeros(2, dtype=torch.int32, device=dev)          # [MNIW updates skipped, first step whose filter failed]
-        ch["sync"] = torch.zeros(1, dtype=torch.int32, device=dev)           # inter-block counter of hgp_lds_chain_finish2_batched_f64
-        return ch
-
-    def _chain_lists(self, ch, views):
-        """The member step as ONE launch per dependency level (hgp_chain.hip): every product of the step is an item of a
-        device-resident list whose pointers are fixed for the life of the chain; the two inversions carry their right-hand
-        sides.  14 launches per member, no torch arithmetic, no allocation (measured: a dependent launch costs ~4.5 us
-        whatever it does, so launches - not flops - were the step's time).  128 < T <= 256: the inversions are the
-        cooperative inverse-only kernels and Z rhs is one more list level behind each of them (16 launches).
-        views: this chain's slices of the inversion buffers and their status words, which chains that run side by side share
-        (one batched inversion for all of them)."""
-        T = self.x_basis.shape[0]
-        riding = T <= 128
-        tt = T * T
-        dev = self.device
-        new = ch.get("alloc") or (lambda *shape: torch.zeros(shape, dtype=f64, device=dev))      # noqa: E731  (a pool hands out slices of its arena)
-        ws = ch["ws"]
-        A, G, C, S, Psm, c0 = (ws[i * tt:(i + 1) * tt].view(T, T) for i in range(6))
-        m0, Fsm = ws[6 * tt:6 * tt + T], ws[6 * tt + T:]
-        X4, RH4, Z4, Y4 = (views[k] for k in ("X4", "RH4", "Z4", "Y4"))   # [P, Sk, R0', R1'], riding RHS, Z, Z rhs
-        S__, S_, Zs, Y3 = (views[k] for k in ("S__", "S_", "Zs", "Y3"))
-        part = new(2, T, T)
-        AP0, Pk, K_t, J, SINV, IKC, KS, MS, T1, KKt, KKtmP, c_post, CmP, X, P_sm_prev = (
-            new(T, T), new(T, T), new(T, T), new(T, T), new(2, T, T), new(T, T), new(T, T), new(2, T, T), new(T, T), new(T, T),
-            new(T, T), new(T, T), new(T, T), new(T, T), new(T, T))
-        y, xm, innov, f_post, w, f_sm_prev = new(T), new(T), new(T), new(T), new(T), new(T)
-        means = ch["W"][0]
-        P, Sk = X4[0], X4[1]
-        lv = [ops.GemmList(dev) for _ in range(10)]
-        # L1-L4: predictions (GPI.py:100-139; GPI.py:283-287 for the pair smoother's P = A c0 A^T + G)
-        lv[0].add(A, Psm, AP0)
-        lv[0].add(A, c0, RH4[0])                                  # A c0, the smoother gain's right-hand side
-        lv[0].add(A, Fsm, xm)
-        lv[1].add(AP0, A, Pk, D=G, transB=True)
-        lv[1].add(RH4[0], A, P, D=G, transB=True)
-        lv[1].add(C, xm, innov, D=y, alpha=-1.0)                  # y - C x_m
-        lv[2].add(C, Pk, RH4[1])                                  # C P_k, the Kalman gain's right-hand side
-        lv[3].add(RH4[1], C, Sk, D=S, transB=True)
-        # after INV1 (Z = L^-1 of P, Sk, R0', R1';  Y = Z rhs):  K = (C Pk)^T Sk^-1 = Y1^T Z1,  J = (A c0)^T P^-1 = Y0^T Z0
-        lv[4].add(Y4[1], Z4[1], K_t, transA=True)
-        lv[4].add(Y4[0], Z4[0], J, transA=True)
-        lv[4].add(Z4[2], Z4[2], SINV[0], transA=True)
-        lv[4].add(Z4[3], Z4[3], SINV[1], transA=True)
-        lv[5].add(K_t, innov, f_post, D=xm)
-        lv[5].add(K_t, C, IKC, alpha=-1.0, add_eye=1.0)
-        lv[5].add(K_t, S, KS)
-        lv[5].add(means[0], SINV[0], MS[0])
-        lv[5].add(means[1], SINV[1], MS[1])
-        lv[6].add(IKC, Pk, T1)
-        lv[6].add(KS, K_t, KKt, transB=True)
-        lv[6].add(KS, K_t, KKtmP, D=P, transB=True, beta=-1.0)
-        lv[6].add(A, m0, w, D=f_post, alpha=-1.0)                 # f_post - A m0
-        lv[7].add(T1, IKC, c_post, D=KKt, transB=True)            # Joseph form (GPI.py:148-150)
-        lv[7].add(T1, IKC, CmP, D=KKtmP, transB=True)             # c_post - P for the smoother
-        lv[7].add(J, w, f_sm_prev, D=m0)
-        lv[8].add(J, CmP, X)
-        lv[8].add(f_sm_prev, f_sm_prev, S__[0], D=SINV[0], transB=True)      # y2 y2^T + R'^-1 (GPI_model.py:1317-1322)
-        lv[8].add(f_post, f_post, S__[1], D=SINV[1], transB=True)
-        lv[8].add(f_post, f_sm_prev, S_[0], D=MS[0], transB=True)            # y1 y2^T + M R'^-1
-        lv[8].add(y, f_post, S_[1], D=MS[1], transB=True)
-        # after INV2 (Zs of S__ + 1e-8 I;  Y3 = Zs S_^T):  S_ S__^-1 = Y3^T Zs
-        lv[9].add(Y3[0], Zs[0], part[0], transA=True)
-        lv[9].add(Y3[1], Zs[1], part[1], transA=True)
-        lv[9].add(X, J, P_sm_prev, D=c0, transB=True)
-        if not riding:
-            lvy = [ops.GemmList(dev), ops.GemmList(dev)]
-            lvy[0].add(Z4[0], RH4[0], Y4[0])                     # Z_P (A c0)
-            lvy[0].add(Z4[1], RH4[1], Y4[1])                     # Z_S (C P_k)
-            lvy[1].add(Zs[0], S_[0], Y3[0], transB=True)         # Z_s S_^T
-            lvy[1].add(Zs[1], S_[1], Y3[1], transB=True)
-            lv += lvy
-        ch["lv"], ch["riding"] = lv, riding
-        ch["bufs"] = dict(X4=X4, RH4=RH4, Z4=Z4, Y4=Y4, S__=S__, S_=S_, Zs=Zs, Y3=Y3, part=part, y=y, f_post=f_post, c_post=c_post,
-                          f_sm_prev=f_sm_prev, P_sm_prev=P_sm_prev)
-        ch["i4"], ch["i2"] = views["i4"], views["i2"]
-
-    def _chain_commit(self, ch, members, x_trains, y_trains):
-        L = int(ch["pos"][0]) + 1
-        unb = lambda k: StackList(ch[k][:L])               # noqa: E731  (rows stay views of the chain's stacks)
-        self.f_star, self.f_star_sm, self.cov_f, self.cov_f_sm = unb("F"), unb("Fsm"), unb("P"), unb("Psm")
-        self.A, self.Gamma, self.C, self.Sigma = unb("A"), unb("G"), unb("C"), unb("S")
-        n0 = float(ch["n0"])
-        W = ch["W"]
-        self.internal_params = matrix_normal_inv_wishart(W[0, 0], W[1, 0], n0, W[2, 0])
-        self.observation_params = matrix_normal_inv_wishart(W[0, 1], W[1, 1], n0, W[2, 1])
-        for idx in members:
-            self.indexes.append(int(idx))
-            self.x_train.append(x_trains[idx])
-            self.y_train.append(y_trains[idx].reshape(-1, 1))
-        self.N += len(members)
-        self._stk = {}
-
     def _backwards_graphed(self):
         """GPI_model.backwards (full RTS) with the step captured once: index t runs down on the device."""
         mm = ops.gemm_batched
@@ -847,6 +724,7 @@ class GPI_model:
         """GPI_model.py:377-406: filter / smooth / re-estimate over the members (resp > 0.99), then score everything.
         With use_graphs (default) this is chain_batch.run over this one chain: members beyond the first go through hipGraph
         replays of the captured member step where it covers the run (chain_batch._graphable), the eager methods otherwise."""
+        from . import chain_batch          # (chain_batch -> member_step imports this module)
         job = chain_batch.Job(self, x_trains, y_trains, resp, prev=(q, q_lat))
         if use_graphs:
             return chain_batch.run([job])[0]

@@ -20,18 +20,18 @@ with 128 < T <= 256, whose inversions are the cooperative inverse-only kernels w
 batch size picks the inversion kernel, so these chains are not batched).  GPI_model.full_pass_weighted is ``run`` over one job.
 Results are bit-identical to running the chains one after the other.  Chains the graphed step does not cover (static models,
 soft members, irregular grids, T > 256, fewer than 4 members, an estimation limit) take GPI_model._full_pass_eager.
-"""
-import ctypes
 
+The step itself - a chain's device state, its level lists, the descriptors, the launch order - is member_step.py, which the
+online pool (online_chain.py) runs too; here is the offline orchestration around it.
+"""
 import numpy as np
 import torch
 
-from . import _ffi, ops
+from . import ops
+from .member_step import Chain, finish_desc, gather_desc, member_step, shared_buffers, upload_descs
 
 f64 = torch.float64
 UNROLL = 8                                   # member steps per captured hipGraph
-_STACKS = ("A", "G", "C", "S", "Psm", "P", "F", "Fsm")          # order of hgp_chain_gather_desc.st
-_SH4 = ("X4", "RH4", "Z4", "Y4", "i4")       # step buffers of the first inversion: four matrices per chain, the others two
 
 
 class Job:
@@ -56,38 +56,15 @@ def _graphable(job):
     return bool(torch.equal(X2[a], gp.x_basis.reshape(1, -1).expand(len(a), -1)))
 
 
-def _descs(structs, dev):
-    arr = (type(structs[0]) * len(structs))(*structs)
-    return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(dev)
+class _MergedLevels:
+    """The level lists of chains that advance together, merged chain-major: level l has per[l] items per chain."""
 
+    def __init__(self, chs):
+        self.per = [len(l_._items) for l_ in chs[0].lv]
+        self.merged = [ops.GemmList.concat([ch.lv[l] for ch in chs]).finalize() for l in range(len(self.per))]
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def gather_desc(ch, T, Y, y_row0):
-    """hgp_chain_gather_desc of a chain (GPI_model._chain_alloc + _chain_lists); the step reads observation row pos - y_row0 of Y
-    (y_row0 < 0: Y is the observation itself)."""
-    b = ch["bufs"]
-    g = _ffi.ChainGatherDesc()
-    for i, k in enumerate(_STACKS):
-        g.st[i] = ch[k].data_ptr()
-    g.pos, g.out, g.Y, g.y_out, g.W, g.Rp = _p(ch["pos"]), _p(ch["ws"]), _p(Y), _p(b["y"]), _p(ch["W"]), _p(b["X4"][2:4])
-    g.y_row0, g.T = y_row0, T
-    return g
-
-
-def finish_desc(ch, T, flags, bad):
-    """hgp_chain_finish_desc of a chain; flags = its `annealing` field (include/hdpgpc_hip.h), bad = the status words it updates."""
-    b = ch["bufs"]
-    f = _ffi.ChainFinishDesc()
-    f.f_post, f.c_post, f.f_sm_prev, f.P_sm_prev, f.y = _p(b["f_post"]), _p(b["c_post"]), _p(b["f_sm_prev"]), _p(b["P_sm_prev"]), _p(b["y"])
-    f.part, f.Snew, f.info1, f.info2 = _p(b["part"]), _p(b["S__"]), _p(ch["i4"]), _p(ch["i2"])
-    f.W, f.n0, f.Nf, f.bad_count = _p(ch["W"]), _p(ch["n0"]), _p(ch["Nf"]), _p(bad)
-    f.stA, f.stG, f.stC, f.stS = _p(ch["A"]), _p(ch["G"]), _p(ch["C"]), _p(ch["S"])
-    f.stF, f.stFsm, f.stP, f.stPsm = _p(ch["F"]), _p(ch["Fsm"]), _p(ch["P"]), _p(ch["Psm"])
-    f.pos, f.sync, f.T, f.annealing = _p(ch["pos"]), _p(ch["sync"]), T, flags
-    return f
+    def run(self, l, lo, hi):
+        self.merged[l].run_range(self.per[l] * lo, self.per[l] * (hi - lo))
 
 
 def run(jobs):
@@ -126,48 +103,22 @@ def _run_group(jobs):
         gp._check_pending()
     jobs = sorted(jobs, key=lambda j: -len(j.rest))    # longest first: the live set is always a prefix
     nc = len(jobs)
-    new = lambda *shape: torch.zeros(shape, dtype=f64, device=dev)      # noqa: E731
-    sh = {"X4": new(nc * 4, T, T), "RH4": new(nc * 4, T, T), "Z4": new(nc * 4, T, T), "Y4": new(nc * 4, T, T),
-          "S__": new(nc * 2, T, T), "S_": new(nc * 2, T, T), "Zs": new(nc * 2, T, T), "Y3": new(nc * 2, T, T),
-          "i4": torch.zeros(nc * 4, dtype=torch.int32, device=dev), "i2": torch.zeros(nc * 2, dtype=torch.int32, device=dev)}
-    rhs_on = torch.tensor([1, 1, 0, 0] * nc, dtype=torch.int32, device=dev)
-    per_chain = lambda k: 4 if k in _SH4 else 2          # noqa: E731
+    sh = shared_buffers(nc, T, dev)
     chs = []
     for c, j in enumerate(jobs):
-        ch = j.gp._chain_alloc(len(j.rest))
+        ch = Chain.from_model(j.gp, len(j.gp.f_star) + len(j.rest))
+        ch.ws = torch.empty(6 * T * T + 2 * T, dtype=f64, device=dev)     # gathered previous state
+        ch.bad = torch.zeros(2, dtype=torch.int32, device=dev)            # [MNIW updates skipped, first step whose filter failed]
+        ch.sync = torch.zeros(1, dtype=torch.int32, device=dev)           # inter-block counter of the finish kernel
         # observations of the run; the step reads row (pos - y_row0) inside its gather kernel
-        ch["Y"] = (j.y[j.rest][..., 0] if j.y.ndim == 3 else j.y[j.rest]).reshape(len(j.rest), -1).contiguous()
-        ch["y_row0"] = int(ch["pos"][0])
-        j.gp._chain_lists(ch, views={k: v[per_chain(k) * c:per_chain(k) * (c + 1)] for k, v in sh.items()})
+        ch.Y = (j.y[j.rest][..., 0] if j.y.ndim == 3 else j.y[j.rest]).reshape(len(j.rest), -1).contiguous()
+        ch.y_row0 = int(ch.pos[0])
+        ch.build_lists(sh, c)
         chs.append(ch)
-    gdev = _descs([gather_desc(ch, T, ch["Y"], ch["y_row0"]) for ch in chs], dev)
-    fdev = _descs([finish_desc(ch, T, int(bool(j.gp.annealing)), ch["bad"]) for j, ch in zip(jobs, chs)], dev)
-    # level lists, chain-major: items [0, n_l * k) of level l belong to the first k chains
-    n_lv = len(chs[0]["lv"])
-    per = [len(chs[0]["lv"][l]._items) for l in range(n_lv)]
-    merged = [ops.GemmList.concat([ch["lv"][l] for ch in chs]).finalize() for l in range(n_lv)]
-    level = lambda l, k: merged[l].run_range(0, per[l] * k)          # noqa: E731
-    riding = chs[0]["riding"]
-    stream = ops._stream
-
-    def step(k):                                           # one member of the first k chains
-        _ffi.check(_ffi.lib.hgp_lds_chain_gather2_batched_f64(_p(gdev), k, T, stream()), "chain_gather2_batched")
-        for l in range(4):
-            level(l, k)
-        if riding:
-            ops.chol_inverse_rhs(sh["X4"][:4 * k], sh["Z4"], sh["RH4"], sh["Y4"], sh["i4"], rhs_on=rhs_on)
-        else:
-            ops.chol_inverse(sh["X4"][:4 * k], out=sh["Z4"][:4 * k], info=sh["i4"][:4 * k])
-            level(10, k)
-        for l in range(4, 9):
-            level(l, k)
-        if riding:
-            ops.chol_inverse_rhs(sh["S__"][:2 * k], sh["Zs"], sh["S_"], sh["Y3"], sh["i2"], rhs_trans=True, add_diag=1e-8)
-        else:
-            ops.chol_inverse(sh["S__"][:2 * k], 0.0, 1e-8, out=sh["Zs"][:2 * k], info=sh["i2"][:2 * k])
-            level(11, k)
-        level(9, k)
-        _ffi.check(_ffi.lib.hgp_lds_chain_finish2_batched_f64(_p(fdev), k, T, stream()), "chain_finish2_batched")
+    gdev = upload_descs([gather_desc(ch) for ch in chs], dev)
+    fdev = upload_descs([finish_desc(ch, int(bool(j.gp.annealing)), ch.bad) for j, ch in zip(jobs, chs)], dev)
+    levels = _MergedLevels(chs)
+    step = lambda k: member_step(levels, sh, gdev, fdev, 0, k, T)      # noqa: E731  (one member of the first k chains)
 
     lengths = [len(j.rest) for j in jobs]
     graphs = []
@@ -177,13 +128,19 @@ def _run_group(jobs):
         if n_it > 0:
             graphs.append(_replay([j.gp for j in jobs[:k]], lambda: step(k), n_it, 1 if nc == 1 else 2 * UNROLL))
             done += n_it
-    bads = [ch["bad"].tolist() for ch in chs]             # the first read-back waits for every replay: the graphs may go
+    bads = [ch.bad.tolist() for ch in chs]             # the first read-back waits for every replay: the graphs may go
     del graphs
     main = torch.cuda.current_stream()
     side = [None] if nc == 1 else [torch.cuda.Stream() for _ in jobs]
     for j, ch, s, bad in zip(jobs, chs, side, bads):       # commit + backward recursion (lock-step: one stream per chain)
         gp = j.gp
-        gp._chain_commit(ch, j.rest, j.x, j.y)
+        ch.bind_model(gp, int(ch.pos[0]) + 1, float(ch.n0))
+        for idx in j.rest:
+            gp.indexes.append(int(idx))
+            gp.x_train.append(j.x[idx])
+            gp.y_train.append(j.y[idx].reshape(-1, 1))
+        gp.N += len(j.rest)
+        gp._stk = {}
         if bad[1] != 0:      # torch.linalg.solve / inv of the reference would have raised at that member
             raise torch.linalg.LinAlgError(f"posterior / backwards_pair: the input is not positive-definite (LDS step {bad[1]})")
         if bad[0] != 0 and gp.verbose:

@@ -8,7 +8,7 @@ parameters - candidate after candidate, ~150 dependent launches each (round 3: 3
 Nothing a candidate computes feeds another one.  Here every cluster model of a lead owns a slot of an ``OnlinePool``:
 
 * its per-step lists live in growing stacks ([rows, T, T]; the model's lists are views, a12) with the device-side position,
-  counters and MNIW distributions of GPI_model._chain_alloc - the cluster IS a chain that is never torn down;
+  counters and MNIW distributions of member_step.Chain - the cluster IS a chain that is never torn down;
 * ``candidates(y)`` runs the member step of ALL clusters side by side with the level-fused lists of the offline chains
   (hgp_gemm_list_f64, one launch per dependency level over every cluster's items; the two inversions batched over
   [4 x clusters] / [2 x clusters] matrices) as a DRY run: the new rows land behind each chain's end, the re-smoothed previous
@@ -27,14 +27,10 @@ import numpy as np
 import torch
 
 from . import _ffi, ops
-from .chain_batch import _descs, finish_desc, gather_desc
-from .GPI_model import LOG2PI, StackList, matrix_normal_inv_wishart
+from .GPI_model import LOG2PI
+from .member_step import Chain, finish_desc, gather, gather_desc, member_step, shared_buffers, upload_descs
 
 f64 = torch.float64
-_STACKS = ("A", "G", "C", "S", "Psm", "P", "F", "Fsm")          # order of hgp_chain_gather_desc.st
-_LISTS = {"A": "A", "G": "Gamma", "C": "C", "S": "Sigma", "Psm": "cov_f_sm", "P": "cov_f", "F": "f_star", "Fsm": "f_star_sm"}
-_SH4 = ("X4", "RH4", "Z4", "Y4", "WK4")
-_SH2 = ("S__", "S_", "Zs", "Y3", "WK2")
 
 
 class _LevelLists:
@@ -100,16 +96,12 @@ class OnlinePool:
         self.cap = cap
         self.WS = 6 * T * T + 2 * T
         self.ws_all = new(cap, self.WS)
-        self.shared = {k: new(cap * 4, T, T) for k in _SH4}
-        self.shared.update({k: new(cap * 2, T, T) for k in _SH2})
-        self.shared["i4"] = torch.zeros(cap * 4, dtype=torch.int32, device=dev)
-        self.shared["i2"] = torch.zeros(cap * 2, dtype=torch.int32, device=dev)
-        self.rhs_on = torch.tensor([1, 1, 0, 0] * cap, dtype=torch.int32, device=dev)
+        self.shared = shared_buffers(cap, T, dev, work=True)
         self.bad_all = torch.zeros((cap, 2), dtype=torch.int32, device=dev)      # committed steps
         self.badc_all = torch.zeros((cap, 2), dtype=torch.int32, device=dev)     # candidate steps (cleared per beat)
         self.sync_all = torch.zeros(cap, dtype=torch.int32, device=dev)
         self.est_mean, self.mean_last = new(cap, T), new(cap, T)
-        # the step buffers of every slot (GPI_model._chain_lists: 21 T x T matrices and 6 vectors) come out of ONE arena, zeroed once:
+        # the step buffers of every slot (Chain.build_lists: 21 T x T matrices and 6 vectors) come out of ONE arena, zeroed once:
         # adopting a cluster used to cost 43 allocations and 22 MB of memsets at T = 256
         self.ARENA = 21 * T * T + 6 * T + 128          # (every piece starts on a 32-byte boundary)
         self.arena = new(cap, self.ARENA)
@@ -131,19 +123,14 @@ class OnlinePool:
         for sl in old:
             self._bind(sl)
 
-    def _views(self, c):
-        v = {k: self.shared[k][4 * c:4 * c + 4] for k in ("X4", "RH4", "Z4", "Y4", "i4")}
-        v.update({k: self.shared[k][2 * c:2 * c + 2] for k in ("S__", "S_", "Zs", "Y3", "i2")})
-        return v
-
     def _bind(self, sl):
         """Give the slot its index, its slices of the shared buffers and its level lists."""
         c = len(self.slots)
         sl.g._slot = c
         ch = sl.ch
-        ch["ws"] = self.ws_all[c]
-        ch["bad"], ch["sync"] = self.bad_all[c], self.sync_all[c:c + 1]
-        ch["Y"], ch["y_row0"] = self.ybuf, -1
+        ch.ws = self.ws_all[c]
+        ch.bad, ch.sync = self.bad_all[c], self.sync_all[c:c + 1]
+        ch.Y, ch.y_row0 = self.ybuf, -1
         arena, used = self.arena[c], [0]
         arena.zero_()
 
@@ -153,17 +140,16 @@ class OnlinePool:
             used[0] += (n + 3) & ~3
             return out
 
-        ch["alloc"] = alloc
-        sl.g._chain_lists(ch, views=self._views(c))
-        del ch["alloc"]
+        ch.build_lists(self.shared, c, alloc)
         T, tt = self.T, self.T * self.T
-        Cw = ch["ws"][2 * tt:3 * tt].view(T, T)
-        ch["lv"][6].add(Cw, ch["bufs"]["f_post"], self.est_mean[c])          # C_last f_post: the mean estimate_new scores against
+        Cw = ch.ws[2 * tt:3 * tt].view(T, T)
+        ch.lv[6].add(Cw, ch.bufs["f_post"], self.est_mean[c])                # C_last f_post: the mean estimate_new scores against
         lvm = ops.GemmList(self.device)                                      # C_last f_last: the mean the beat is scored against
-        lvm.add(Cw, ch["ws"][6 * tt:6 * tt + T], self.mean_last[c])
-        self.lists.set_slot(c, ch["lv"] + [lvm])
-        self._base[c] = [ch[k].data_ptr() for k in _STACKS]
-        self._bufp[c] = [ch["bufs"][k].data_ptr() for k in ("f_post", "f_sm_prev", "P_sm_prev")]
+        lvm.add(Cw, ch.ws[6 * tt:6 * tt + T], self.mean_last[c])
+        self.lv_mean_last = len(ch.lv)                                       # the pool's own level, behind the step's
+        self.lists.set_slot(c, ch.lv + [lvm])
+        self._base[c] = ch.stack_ptrs()
+        self._bufp[c] = [ch.bufs[k].data_ptr() for k in ("f_post", "f_sm_prev", "P_sm_prev")]
         self.descs_dirty = True
         dd = sl.g
         self.ini_noise_all[c] = 1e-2 * torch.mean(torch.diagonal(dd.Sigma[0]))
@@ -187,26 +173,10 @@ class OnlinePool:
         """Move the model's per-step lists into a slot's stacks (the model keeps reading them through views)."""
         if len(self.slots) == self.cap:
             self._grow()
-        T, dev = self.T, self.device
         L = len(g.f_star)
         sl = _Slot()
         sl.g, sl.N, sl.rows = g, L - 1, max(8, 2 * L)
-        ch = {}
-        for key in _STACKS:
-            lst = getattr(g, _LISTS[key])
-            shape = (T, 1) if key in ("F", "Fsm") else (T, T)
-            buf = torch.zeros((sl.rows,) + shape, dtype=f64, device=dev)
-            buf[:L] = (lst.stack() if isinstance(lst, StackList) else torch.stack(list(lst))).reshape((L,) + shape)
-            ch[key] = buf
-        ch["pos"] = torch.tensor([L - 1], dtype=torch.int64, device=dev)
-        ch["Nf"] = torch.tensor([float(g.N)], dtype=f64, device=dev)
-        ch["n0"] = torch.tensor([float(g.internal_params.n0)], dtype=f64, device=dev)
-        eye = torch.eye(T, dtype=f64, device=dev)
-        mi, mo = g.internal_params, g.observation_params
-        ch["W"] = torch.stack((torch.stack((mi.m_mean, mo.m_mean)),
-                               torch.stack((eye if mi.m_r_cov is None else mi.m_r_cov, eye if mo.m_r_cov is None else mo.m_r_cov)),
-                               torch.stack((mi.scale, mo.scale)))).contiguous()
-        sl.ch = ch
+        sl.ch = Chain.from_model(g, sl.rows)
         sl.ini_noise = None                                   # log_sq_error's `first` inflation: on the device (self.ini_noise_all)
         if getattr(g, "_def_diag_key", None) == (id(g.Sigma_def), id(g.Gamma_def)):
             sl.def_diag = g._def_diag
@@ -214,88 +184,44 @@ class OnlinePool:
             sl.def_diag = all(bool(torch.equal(s_, torch.diag(torch.diagonal(s_)))) for s_ in (g.Sigma_def, g.Gamma_def))
         sl.bad0 = 0
         self._bind(sl)
-        self._rebind_lists(sl, float(mi.n0))
+        self._rebind_lists(sl, float(g.internal_params.n0))
         return sl
 
     def _rebind_lists(self, sl, n0):
         """The model's lists and MNIW objects as views of the slot's stacks."""
-        g, ch, L = sl.g, sl.ch, sl.N + 1
-        for key in _STACKS:
-            setattr(g, _LISTS[key], StackList(ch[key][:L]))
-        W = ch["W"]
-        g.internal_params = matrix_normal_inv_wishart(W[0, 0], W[1, 0], n0, W[2, 0])
-        g.observation_params = matrix_normal_inv_wishart(W[0, 1], W[1, 1], n0, W[2, 1])
+        g = sl.g
+        sl.ch.bind_model(g, sl.N + 1, n0)
         g._stk = {k: v for k, v in g._stk.items() if k in ("_lat_all", "_lat_col")}
 
     def _more_rows(self, sl):
-        ch = sl.ch
-        rows = sl.rows * 2
-        for key in _STACKS:
-            buf = torch.zeros((rows,) + tuple(ch[key].shape[1:]), dtype=f64, device=self.device)
-            buf[:sl.rows] = ch[key]
-            ch[key] = buf
-        sl.rows = rows
+        sl.rows *= 2
+        sl.ch.more_rows(sl.rows)
         lat = sl.g._stk.get("_lat_all")
         self._rebind_lists(sl, float(sl.g.internal_params.n0))
         if lat is not None:           # the key holds data pointers of the old stacks
             sl.g._stk["_lat_all"] = (self._lat_key(sl.g), lat[1])
-        self._base[sl.g._slot] = [ch[k].data_ptr() for k in _STACKS]
+        self._base[sl.g._slot] = sl.ch.stack_ptrs()
         self.descs_dirty = True
 
     # ------------------------------------------------------------------ launch tables
     def _prepare(self):
         """Descriptor arrays of the gather / finish launches for the current slots (re-uploaded when a slot is added or its
         stacks move)."""
-        T = self.T
         gd, fd_dry, fd_real = [], [], []
         for c, sl in enumerate(self.slots):
-            gd.append(gather_desc(sl.ch, T, self.ybuf, -1))
-            fd_dry.append(finish_desc(sl.ch, T, int(self.annealing) | 2 | 4, self.badc_all[c]))
-            fd_real.append(finish_desc(sl.ch, T, int(self.annealing) | 4, self.bad_all[c]))
-        self.gdev, self.fdev_dry, self.fdev_real = _descs(gd, self.device), _descs(fd_dry, self.device), _descs(fd_real, self.device)
-        self.riding = self.slots[0].ch["riding"]
+            gd.append(gather_desc(sl.ch))
+            fd_dry.append(finish_desc(sl.ch, int(self.annealing) | 2 | 4, self.badc_all[c]))
+            fd_real.append(finish_desc(sl.ch, int(self.annealing) | 4, self.bad_all[c]))
+        self.gdev, self.fdev_dry, self.fdev_real = (upload_descs(d, self.device) for d in (gd, fd_dry, fd_real))
         self.descs_dirty = False
 
-    def _gather(self, lo, hi):
+    def _step(self, lo, hi, dry, gather_first=True):
+        """The member step of slots [lo, hi): a dry run for candidates (nothing of the cluster changes), else the committed step
+        without the smoother (see the module docstring)."""
         if self.descs_dirty:
             self._prepare()
-        gsz = ctypes.sizeof(_ffi.ChainGatherDesc)
-        _ffi.check(_ffi.lib.hgp_lds_chain_gather2_batched_f64(ctypes.c_void_p(self.gdev.data_ptr() + lo * gsz), hi - lo, self.T, ops._stream()),
-                   "chain_gather2_batched")
-
-    def _step(self, lo, hi, dry, gather=True):
-        """The member step of slots [lo, hi): one launch per dependency level (the step of chain_batch._run_group)."""
-        if self.descs_dirty:
-            self._prepare()
-        T, k, sh = self.T, hi - lo, self.shared
-        fsz = ctypes.sizeof(_ffi.ChainFinishDesc)
-        if gather:
-            self._gather(lo, hi)
-        run = lambda l: self.lists.run(l, lo, hi)        # noqa: E731
-        s4, s2 = slice(4 * lo, 4 * hi), slice(2 * lo, 2 * hi)
-        for l in range(4):
-            run(l)
-        if self.riding:
-            ops.chol_inverse_rhs(sh["X4"][s4], sh["Z4"][s4], sh["RH4"][s4], sh["Y4"][s4], sh["i4"][s4], rhs_on=self.rhs_on[s4])
-        else:
-            ops.chol_inverse(sh["X4"][s4], out=sh["Z4"][s4], info=sh["i4"][s4], work=sh["WK4"][s4])
-            run(10)
-        for l in range(4, 8):
-            run(l)
-        if not dry:        # no smoother in the committed step: the previous smoothed mean stands where f_sm_prev would
-            for sl in self.slots[lo:hi]:
-                tt = T * T
-                sl.ch["bufs"]["f_sm_prev"].copy_(sl.ch["ws"][6 * tt + T:6 * tt + 2 * T])
-        run(8)
-        if self.riding:
-            ops.chol_inverse_rhs(sh["S__"][s2], sh["Zs"][s2], sh["S_"][s2], sh["Y3"][s2], sh["i2"][s2], rhs_trans=True, add_diag=1e-8)
-        else:
-            ops.chol_inverse(sh["S__"][s2], 0.0, 1e-8, out=sh["Zs"][s2], info=sh["i2"][s2], work=sh["WK2"][s2])
-            run(11)
-        run(9)
-        fdev = self.fdev_dry if dry else self.fdev_real
-        _ffi.check(_ffi.lib.hgp_lds_chain_finish2_batched_f64(ctypes.c_void_p(fdev.data_ptr() + lo * fsz), k, T, ops._stream()),
-                   "chain_finish2_batched")
+        member_step(self.lists, self.shared, self.gdev, self.fdev_dry if dry else self.fdev_real, lo, hi, self.T,
+                    gather_first=gather_first, no_smoother=() if dry else [sl.ch for sl in self.slots[lo:hi]])
 
     # ------------------------------------------------------------------ the beat under the clusters' last states
     def begin_beat(self, y):
@@ -308,8 +234,10 @@ class OnlinePool:
             if sl.N + 2 > sl.rows:
                 self._more_rows(sl)
         self.ybuf.copy_(y.reshape(1, T))
-        self._gather(0, M)
-        self.lists.run(len(self.lists.per) - 1, 0, M)          # mean_last = C_last f_last
+        if self.descs_dirty:
+            self._prepare()
+        gather(self.gdev, 0, M, T)
+        self.lists.run(self.lv_mean_last, 0, M)                # mean_last = C_last f_last
         ar = np.arange(M, dtype=np.int32)
         quad, _, info = ops.score_each(self.ybuf.expand(M, T).contiguous(), self.mean_last, self.ws_all[0, 3 * tt:], ar, ar, None,
                                        strides=(T, self.WS))
@@ -329,7 +257,7 @@ class OnlinePool:
         if extra is not None and (M >= self.cap or extra.N != 1 or not extra._dyn_prior()):
             extra = None                                        # no room behind the last slot (or not the plain case): the caller's job
         self.badc_all[:M].zero_()
-        self._step(0, M, dry=True, gather=False)               # begin_beat(y) of this beat gathered the state
+        self._step(0, M, dry=True, gather_first=False)               # begin_beat(y) of this beat gathered the state
         # estimate_new: the beat against (C_last f_post, Sigma_last), `first` inflation for one-member clusters
         Y = self.ybuf.expand(M, T).contiguous()
         add = self.ini_noise_all[:M] * ops.to_dev(np.array([1.0 if sl.N == 1 else 0.0 for sl in self.slots]), f64, self.device)
@@ -454,10 +382,10 @@ class OnlinePool:
             # latent-transition scores: member 0 now reads the new last parameters, the new member is added; the rest is unchanged
             n = sl.N                                          # members now; rows 0..n
             ch = sl.ch
-            fs, ps = ch["Fsm"], ch["Psm"]
+            fs, ps = ch.Fsm, ch.Psm
             cur = torch.stack((fs[1], fs[n])).reshape(2, T)
             prv = torch.stack((fs[1], fs[n - 1])).reshape(2, T)
-            A2, G2 = torch.stack((ch["A"][n], ch["A"][n])), torch.stack((ch["G"][n], ch["G"][n]))
+            A2, G2 = torch.stack((ch.A[n], ch.A[n])), torch.stack((ch.G[n], ch.G[n]))
             C2 = torch.stack((ps[1], ps[n - 1]))
             out, info = ops.lat_error(cur, prv, A2, G2, C2)
             out = out - 0.5 * T * LOG2PI

@@ -364,17 +364,17 @@ def test_chain_gather_forms_the_mniw_jitter():
     invert: Rp[b] = R[b] + 1e-2 max(mean |diag S[b]|, eps) I with W = (means, R, S) (GPI_model.py:1312-1316)."""
     import ctypes
 
-    from hdpgpc_amd import _ffi, chain_batch
+    from hdpgpc_amd import _ffi, member_step
     rng = np.random.default_rng(22)
     T = 37
     R, S = rng.normal(size=(2, T, T)), rng.normal(size=(2, T, T))
     z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device="cuda")     # noqa: E731
-    ch = {k: z(1, T, T) for k in ("A", "G", "C", "S", "Psm", "P")} | {k: z(1, T, 1) for k in ("F", "Fsm")}
-    ch.update(pos=torch.zeros(1, dtype=torch.int64, device="cuda"), ws=z(6 * T * T + 2 * T), W=dev(np.stack([np.zeros_like(R), R, S])),
-              bufs={"y": z(T), "X4": z(4, T, T)})
-    descs = chain_batch._descs([chain_batch.gather_desc(ch, T, z(1, T), 0)], "cuda")
+    ch = member_step.Chain(**{k: z(1, T, T) for k in ("A", "G", "C", "S", "Psm", "P")}, **{k: z(1, T, 1) for k in ("F", "Fsm")},
+                           T=T, pos=torch.zeros(1, dtype=torch.int64, device="cuda"), ws=z(6 * T * T + 2 * T), Y=z(1, T), y_row0=0,
+                           W=dev(np.stack([np.zeros_like(R), R, S])), bufs={"y": z(T), "X4": z(4, T, T)})
+    descs = member_step.upload_descs([member_step.gather_desc(ch)], "cuda")
     _ffi.check(_ffi.lib.hgp_lds_chain_gather2_batched_f64(ctypes.c_void_p(descs.data_ptr()), 1, T, ops._stream()), "gather")
-    got = ch["bufs"]["X4"][2:4].cpu().numpy()
+    got = ch.bufs["X4"][2:4].cpu().numpy()
     for b in range(2):
         jit = 1e-2 * max(np.mean(np.abs(np.diag(S[b]))), np.finfo(np.float64).eps)
         assert np.allclose(got[b], R[b] + jit * np.eye(T), rtol=0, atol=1e-15)
