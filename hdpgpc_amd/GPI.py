@@ -3,7 +3,7 @@ error behaviour); all arithmetic runs in HIP kernels through hdpgpc_amd.ops.
 
 Built: the kernel object (scikit-learn's ConstantKernel*RBF + WhiteKernel, GPI_HDP.py:164-166),
 IterativeGaussianProcess.pred_dist (GPI.py:457-503), pred_latent_dist (GPI.py:505-560),
-log_marginal_likelihood (GPI.py:976-1056, value and gradient).  Not built here: posterior / backward (the LDS recursion,
+log_marginal_likelihood (GPI.py:976-1056, value and gradient), KL_divergence (GPI.py:1058-1094).  Not built here: posterior / backward (the LDS recursion,
 SURVEY.md 8f-1) and fit_torch (gpytorch, 8f-2).
 """
 import math
@@ -139,6 +139,14 @@ class IterativeGaussianProcess:
         term_data = ops.gemm_batched(K_X_Xs, sol_K, transA=True)
         term_prior = ops.gemm_batched(K_X_Xs, solve(ops.gemm_batched(cov_prior, sol_K)), transA=True)
         return f_star, K_Xs_Xs - term_data + term_prior
+
+    def KL_divergence(self, mean1, cov1, mean2, cov2):
+        """GPI.py:1058-1094: symmetric Kullback-Leibler divergence of two Gaussians, the 1 x 1 case of ops.kl_sym (Cholesky
+        inverses instead of torch.linalg.inv: a covariance that is not positive-definite raises LinAlgError)."""
+        T = self.cond_to_torch(cov1).shape[-1]
+        m = lambda v: self.cond_to_torch(v).reshape(1, T).contiguous()         # noqa: E731
+        c = lambda v: self.cond_to_torch(v).reshape(1, T, T).contiguous()      # noqa: E731
+        return float(ops.kl_sym(m(mean1), c(cov1), m(mean2), c(cov2))[0, 0])
 
     def log_marginal_likelihood(self, x_train, y_train, alpha_ini=None, theta=None, eval_gradient=False,
                                 clone_kernel=True, faithful=True):

@@ -224,7 +224,7 @@ class GPI_model:
         return torch.as_tensor(x, dtype=f64).to(self.device)
 
     def load_state(self, f_star, Sigma, C, indexes, f_star_sm=None, cov_f_sm=None, A=None, Gamma=None, A_def=None,
-                   Gamma_def=None, C_def=None, Sigma_def=None, n0=None):
+                   Gamma_def=None, C_def=None, Sigma_def=None, n0=None, cov_f=None):
         """Stacked state: f_star [S,T] or [S,T,1]; matrices [S,T,T]; indexes = member segment ids in order."""
         T = self.x_basis.shape[0]
 
@@ -238,6 +238,8 @@ class GPI_model:
         self.f_star, self.f_star_sm = unb(vec(f_star)), unb(vec(f_star_sm))
         self.Sigma, self.C, self.A, self.Gamma, self.cov_f_sm = (unb(mat(Sigma)), unb(mat(C)), unb(mat(A)), unb(mat(Gamma)),
                                                                  unb(mat(cov_f_sm)))
+        if cov_f is not None:
+            self.cov_f = unb(mat(cov_f))
         self._stk = {}
         self.indexes = [int(i) for i in indexes]
         self.N = len(self.indexes)
@@ -315,6 +317,66 @@ class GPI_model:
             mean, C, Sigma = (self.cond_to_torch(params[0]).reshape(-1, 1), self.cond_to_torch(params[2]).contiguous(),
                               self.cond_to_torch(params[3]))
         return self.gp.pred_dist(x_post, self.x_basis, ops.gemm_batched(C, mean), Sigma)
+
+    # ------------------------------------------------------------------ a13: distances between states
+    def _kl_static(self):
+        """GPI_model.py:918-921: without a dynamic noise the latent state itself is compared."""
+        return len(self.Gamma) == 0 or bool(torch.all(self.Gamma[-1] == 0))
+
+    def observed_moments(self, ts, smoothed=True, latent=None):
+        """The Gaussians GPI_model.KL_divergence compares (GPI_model.py:902-930) for the steps `ts` at once: mean [n,T] and
+        cov [n,T,T].  State t reads f_star[t+1] / cov_f[t+1] with C[t] / Sigma[t] (the last ones from estimation_limit on);
+        dynamic models observe them on the basis grid, C f and 0.5 (S + S^T) with S = C P C^T + Sigma.  latent: compare the
+        latent states themselves (None = this model's own rule, _kl_static)."""
+        ts = [int(t) for t in ts]
+        T = self.x_basis.shape[0]
+        if len(ts) == 0:
+            return torch.empty((0, T), dtype=f64, device=self.device), torch.empty((0, T, T), dtype=f64, device=self.device)
+        fi = torch.as_tensor([t + 1 for t in ts], dtype=torch.int64, device=self.device)
+        f = self._S("f_star_sm" if smoothed else "f_star").reshape(-1, T, 1).index_select(0, fi).contiguous()
+        P = self._S("cov_f_sm" if smoothed else "cov_f").index_select(0, fi).contiguous()
+        if self._kl_static() if latent is None else latent:
+            return f.reshape(-1, T), P
+        nC = len(self.C)
+        ci = torch.as_tensor([(t if self.estimation_limit > t else -1) % nC for t in ts], dtype=torch.int64, device=self.device)
+        C = self._S("C").index_select(0, ci).contiguous()
+        Sig = self._S("Sigma").index_select(0, ci)
+        S = ops.gemm_batched(ops.gemm_batched(C, P), C, transB=True, add=Sig.contiguous())
+        return ops.gemm_batched(C, f).reshape(-1, T), 0.5 * (S + S.transpose(1, 2))
+
+    def _kl_moments_on(self, ts, smoothed, x_bas, latent=None):
+        """observed_moments, or the observe(x_bas, t, params=...) route of GPI_model.py:923-925 when x_bas is another grid."""
+        latent = self._kl_static() if latent is None else latent
+        if latent or x_bas is None:
+            return self.observed_moments(ts, smoothed, latent)
+        x_bas = self.cond_to_torch(x_bas)
+        if torch.equal(x_bas.reshape(-1), self.x_basis.reshape(-1)):
+            return self.observed_moments(ts, smoothed, latent)
+        F, Pl = (self.f_star_sm, self.cov_f_sm) if smoothed else (self.f_star, self.cov_f)
+        means, covs = [], []
+        for t in ts:
+            tc = -1 if self.estimation_limit <= t else t
+            m, c = self.observe(x_bas, tc, params=[F[t + 1], Pl[t + 1], self.C[tc], self.Sigma[tc]])
+            means.append(m.reshape(-1))
+            covs.append(c)
+        return torch.stack(means).contiguous(), torch.stack(covs).contiguous()
+
+    def kl_states(self, ts, other=None, ts_other=None, smoothed=True, x_bas=None):
+        """[len(ts), len(ts_other)] symmetric KL distances between the states `ts` of this model and `ts_other` of `other`
+        (other None: these states against themselves) - GPI_model.KL_divergence for every pair in one ops.kl_sym call.  As in
+        the reference (GPI_model.py:918-921), THIS model's Gamma decides for both sides whether latent or observed states are
+        compared."""
+        latent = self._kl_static()
+        mA, cA = self._kl_moments_on(ts, smoothed, x_bas, latent)
+        if other is None:
+            return ops.kl_sym(mA, cA)
+        mB, cB = other._kl_moments_on(ts_other, smoothed, x_bas, latent)
+        return ops.kl_sym(mA, cA, mB, cB)
+
+    def KL_divergence(self, t, gpmodel, t_gp, smoothed=True, x_bas=None):
+        """GPI_model.py:899-931: symmetric Kullback-Leibler divergence between state t of this model and state t_gp of
+        `gpmodel`: the 1 x 1 case of kl_states."""
+        return float(self.kl_states([t], gpmodel, [t_gp], smoothed=smoothed, x_bas=x_bas)[0, 0])
 
     # ------------------------------------------------------------------ 8f-1: the producer of the state
     def _eye(self):

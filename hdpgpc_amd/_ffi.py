@@ -61,6 +61,7 @@ def _load():
         "hgp_lds_chain_finish2_batched_f64": (i32, [vp, i32, i32, vp]),
         "hgp_trsv_lower_solve_f64": (i32, [vp, i32, vp, i32, vp, vp, vp]),
         "hgp_lml_grad_f64": (i32, [vp, vp, vp, i32, f64, f64, f64, vp, vp]),
+        "hgp_kl_sym_f64": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header and library disagree

@@ -406,6 +406,42 @@ def gemm_batched(A, B, transA=False, transB=False, alpha=1.0, add=None, beta=1.0
     return C if (A.dim() == 3 or B.dim() == 3) else C[0]
 
 
+def _kl_precisions(cov, what):
+    """cov^-1 = Z^T Z with Z = chol(0.5 (cov + cov^T))^-1, no jitter (the reference's KL_divergence inverts the covariance
+    as it is, GPI.py:1080-1081); a covariance that is not positive-definite raises, naming the state."""
+    T = cov.shape[1]
+    work = torch.empty_like(cov) if T > 128 else None
+    Z, info = chol_inverse(cov, 0.0, 0.0, work=work)
+    raise_on_info(info, f"kl_sym: covariance of {what}")
+    return gemm_batched(Z, Z, transA=True)
+
+
+def kl_sym(meanA, covA, meanB=None, covB=None):
+    """a13: the symmetric Kullback-Leibler distance (GPI.py:1058-1094) between every Gaussian (meanA[i], covA[i]) and every
+    (meanB[j], covB[j]); B omitted = A against itself (bitwise symmetric, zero diagonal up to rounding).  mean [n,T] (or
+    [n,T,1]), cov [n,T,T].  Returns [nA,nB]; an entry depends on its own pair only (same bits in any call that holds it)."""
+    covA = _dev64(covA, "covA")
+    nA, T = covA.shape[0], covA.shape[-1]
+    meanA = _dev64(meanA, "meanA").reshape(nA, T)
+    if (meanB is None) != (covB is None):
+        raise ValueError("kl_sym: meanB and covB go together")
+    self_call = covB is None
+    if not self_call:
+        covB = _dev64(covB, "covB")
+        if covB.shape[-1] != T:
+            raise ValueError("kl_sym: the two sets of states live on different grids")
+        meanB = _dev64(meanB, "meanB").reshape(covB.shape[0], T)
+    nB = nA if self_call else covB.shape[0]
+    out = torch.empty((nA, nB), dtype=torch.float64, device=covA.device)
+    if nA == 0 or nB == 0:
+        return out
+    precA = _kl_precisions(covA, "state (first set)")
+    precB = None if self_call else _kl_precisions(covB, "state (second set)")
+    _ffi.check(_ffi.lib.hgp_kl_sym_f64(_ptr(meanA), _ptr(covA), _ptr(precA), nA, _ptr(meanB), _ptr(covB), _ptr(precB), nB, T,
+                                       _ptr(out), _stream()), "kl_sym")
+    return out
+
+
 def rts_chain(J, P, AM, M, Cv):
     """Sequential part of the RTS smoother for all steps in one launch (in place on M [n,T] and Cv [n,T,T]); T <= 96."""
     n, T = M.shape[0], Cv.shape[1]

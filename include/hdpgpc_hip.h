@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define HGP_ABI_VERSION 6   /* 6: + hgp_chol_inverse_ws_f64, candidate / no-smoother flags of the chain finish, - the single-chain gather / scatter / finish glue and its jitter helper (one chain = n_chains 1 of the batched calls); 5: + hgp_pairs_plan_set_score_output, hgp_debug_exp_neg_f64; 3: + hgp_pairs_plan_set_accuracy (solve-based per-pair path), assignment tail, warp fit, member-step lists; 4: + batched chain gather / finish */
+#define HGP_ABI_VERSION 6   /* still 6 with hgp_kl_sym_f64: purely additive, no existing entry changed; 6: + hgp_chol_inverse_ws_f64, candidate / no-smoother flags of the chain finish, - the single-chain gather / scatter / finish glue and its jitter helper (one chain = n_chains 1 of the batched calls); 5: + hgp_pairs_plan_set_score_output, hgp_debug_exp_neg_f64; 3: + hgp_pairs_plan_set_accuracy (solve-based per-pair path), assignment tail, warp fit, member-step lists; 4: + batched chain gather / finish */
 /* largest T (basis length) and T* (segment length) served by the register-resident wave kernels */
 #define HGP_MAX_T_WAVE 128
 /* largest T served at all: 128 < T <= 256 runs on cooperative kernels (one workgroup of 4-8 waves per matrix / pair) */
@@ -311,6 +311,16 @@ int hgp_trsv_lower_solve_f64(const double* G, int ld, const double* y, int T, do
  * with scikit-learn's kernel gradients (ConstantKernel * RBF: c R and c R d^2/ell^2; WhiteKernel: noise I). */
 int hgp_lml_grad_f64(const double* x, const double* alpha, const double* Kinv, int T, double c, double ell, double noise,
                      double* out3, void* stream);
+
+/* a13 - the symmetric Kullback-Leibler distance between the Gaussians of cluster states: IterativeGaussianProcess.KL_divergence
+ * (GPI.py:1058-1094) as called by GPI_model.KL_divergence (GPI_model.py:899-931) for every pair of member states in
+ * util_plots.plot_MDS / plot_MDS_plotly (util_plots.py:598-688), with the precisions prec = cov^-1 supplied by the caller:
+ *   out[i,j] = 1/4 (<precB_j, covA_i> + <precA_i, covB_j> - 2T) + 1/4 d^T (precA_i + precB_j) d,   d = meanA_i - meanB_j.
+ * mean [n,T]; cov, prec [n,T,T] dense and symmetric; out [nA,nB].  meanB == covB == precB == NULL: B = A (nB ignored), the
+ * square self-distance matrix, bitwise symmetric.  Any T >= 1 and any nA, nB; three launches whatever the sizes.
+ * An entry depends on its own pair only: a 1 x 1 call, a rectangular call and the full matrix give the same bits. */
+int hgp_kl_sym_f64(const double* meanA, const double* covA, const double* precA, int nA, const double* meanB, const double* covB,
+                   const double* precB, int nB, int T, double* out, void* stream);
 
 #ifdef __cplusplus
 }
