@@ -1386,6 +1386,14 @@ __device__ __forceinline__ double hmm_exp(double x, double m) {   // the referen
   const double e = exp(x - m);
   return (e != e) ? 1e-8 : e;
 }
+// one step of the row maximum safe_exp subtracts.  torch.max: a NaN anywhere in the row IS the row's maximum (the expression of
+// k_loglik_rows), so that every entry of such a row becomes 1e-8 as in the reference - fmax would drop the NaN.
+__device__ __forceinline__ double hmm_max(double m, double v) { return (v > m || v != v) ? ((m != m) ? m : v) : m; }
+// the same maximum over the lanes of the wave: the fmax reduction ignores NaN, a wave-wide "any NaN" puts it back
+__device__ __forceinline__ double hmm_wave_max(double v) {
+  const double m = wave_allreduce<true>(v);
+  return __any(v != v) ? __builtin_nan("") : m;
+}
 struct HmmArgs {
   const double* q;          // [N,K] log-observations
   const double* log_pi;     // [K]
@@ -1415,7 +1423,7 @@ __global__ __launch_bounds__(64) void k_hmm_messages(HmmArgs a) {
   // clamped at 1e-5 (GPI_HDP.py:3586-3589, 3637-3642)
   if (live) {
     double m = ninf;
-    for (int j = 0; j < K; ++j) m = fmax(m, fwd ? a.log_trans[(size_t)j * K + i] : a.log_trans[(size_t)i * K + j]);
+    for (int j = 0; j < K; ++j) m = hmm_max(m, fwd ? a.log_trans[(size_t)j * K + i] : a.log_trans[(size_t)i * K + j]);
     for (int j = 0; j < K; ++j) {
       double e = hmm_exp(fwd ? a.log_trans[(size_t)j * K + i] : a.log_trans[(size_t)i * K + j], m);
       if (e < (fwd ? 1e-6 : 1e-5)) e += 1e-4;
@@ -1435,7 +1443,7 @@ __global__ __launch_bounds__(64) void k_hmm_messages(HmmArgs a) {
         const int t = t0 + u;
         if (t >= N) break;
         const double qv = qv8[u];
-        const double qm = wave_allreduce<true>(qv);                     // (all 64 lanes take part in the shuffles)
+        const double qm = hmm_wave_max(qv);                             // (all 64 lanes take part in the shuffles)
         const double qe = live ? hmm_exp(qv, qm) : 0.0;
         double g = pi_;
         if (t > 0) {
@@ -1467,7 +1475,7 @@ __global__ __launch_bounds__(64) void k_hmm_messages(HmmArgs a) {
         const int t = t0 - u;
         if (t < 0) break;
         const double qv = qv8[u];
-        const double qm = wave_allreduce<true>(qv);
+        const double qm = hmm_wave_max(qv);
         const double qe = live ? hmm_exp(qv, qm) : 0.0;
         if (live) f[i] = b * qe;
         __builtin_amdgcn_wave_barrier();
@@ -1498,11 +1506,11 @@ __global__ __launch_bounds__(256) void k_hmm_pair(const double* __restrict__ q, 
     return;
   }
   double qm = -__builtin_inf();
-  for (int j = 0; j < K; ++j) qm = fmax(qm, q[(size_t)t * K + j]);
+  for (int j = 0; j < K; ++j) qm = hmm_max(qm, q[(size_t)t * K + j]);
   for (int j = tid; j < K; j += 256) {
     soft[j] = hmm_exp(q[(size_t)t * K + j], qm) * beta[(size_t)t * K + j];
     double m = -__builtin_inf();
-    for (int l = 0; l < K; ++l) m = fmax(m, log_trans[(size_t)j * K + l]);
+    for (int l = 0; l < K; ++l) m = hmm_max(m, log_trans[(size_t)j * K + l]);
     rmax[j] = m;
   }
   __syncthreads();
@@ -1549,11 +1557,11 @@ __global__ __launch_bounds__(256) void k_hmm_pair_first(const double* __restrict
   }
   if (tid == 0) any_nan = 0;
   double qm = -__builtin_inf();
-  for (int j = 0; j < K; ++j) qm = fmax(qm, q[(size_t)t * K + j]);
+  for (int j = 0; j < K; ++j) qm = hmm_max(qm, q[(size_t)t * K + j]);
   for (int j = tid; j < K; j += 256) {
     soft[j] = hmm_exp(q[(size_t)t * K + j], qm) * beta[(size_t)t * K + j];
     double m = -__builtin_inf();
-    for (int l = 0; l < K; ++l) m = fmax(m, log_trans[(size_t)j * K + l]);
+    for (int l = 0; l < K; ++l) m = hmm_max(m, log_trans[(size_t)j * K + l]);
     rmax[j] = m;
   }
   __syncthreads();

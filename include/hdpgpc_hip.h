@@ -275,7 +275,10 @@ int hgp_trsv_lower_quad_f64(const double* G, int ld, const double* y, int T, dou
  * GPI_HDP.py:3546-3700), full recursion.  q[N,K]: log-observations (the [N,K] score matrix after LogLik); log_pi[K] =
  * compute_trans_pi, log_trans[K,K] = compute_trans_A (both stay host-side control plane).  Outputs: fmsg[N,K],
  * marg[N] (forward messages and their normalisers), bmsg[N,K] (backward messages, normalised without the last state as
- * in GPI_HDP.py:3645), log_resp_pair[N,K,K] (may be NULL; row 0 = -inf as in the reference).  K <= 64 (-2 above). */
+ * in GPI_HDP.py:3645), log_resp_pair[N,K,K] (may be NULL; row 0 = -inf as in the reference).  K <= 64 (-2 above).
+ * Non-finite scores follow the reference's safe_exp, exp(x - torch.max(row)) with NaN -> 1e-8: torch.max propagates NaN, so ONE
+ * NaN score poisons its row - every entry of that row of q (or of log_trans) counts as 1e-8, not only the NaN itself; so does
+ * every entry of an all -inf row; a +inf entry counts as 1e-8 and the finite entries beside it as 0. */
 int hgp_hmm_messages_f64(const double* q, const double* log_pi, const double* log_trans, int N, int K, double* fmsg,
                          double* marg, double* bmsg, double* log_resp_pair, void* stream);
 /* The whole local step of the switching variable for a BATCH of B score matrices q[B,N,K] that share log_pi / log_trans (the
