@@ -472,6 +472,181 @@ __global__ __launch_bounds__(256) void k_copy_list(const hgp_copy_item* __restri
   }
 }
 
+// k_rts_chain: the sequential part of the RTS smoother (GPI.backward, GPI.py:240-270) for ALL steps in one launch.
+// The gains J_t, the predictive covariances P_t and A_t m_t only depend on the filtered states and are batched by the
+// caller; what remains is, for t = n-2 .. 0:
+//     m_t <- m_t + J_t (m_{t+1} - A_t m_t),      C_t <- C_t + J_t (C_{t+1} - P_t) J_t^T.
+// One workgroup of 12 waves walks the chain; wave w owns the output tiles w, w + 12, w + 24 of the 6 x 6 tile grid.
+// What crosses a step stays on chip: the new C_t tiles are still in the registers of the wave that formed them when the
+// next step needs them as C_{t+1} (D = C_{t+1} - P_t is formed tile-wise in registers and written to LDS), m_t sits in
+// LDS; and everything the NEXT step reads from memory (J, P, C, A m, m of step t - 1: filtered quantities, independent of
+// the recursion) is requested before the two product phases of the current step.  Per step: stage J and D in LDS (row
+// pitch 100 doubles), X = J D on the matrix core (kept in registers until D is dead, then written over it), C_t + X J^T.
+// The floor is the matrix core of ONE compute unit: 2 x 36 tiles x 24 MFMAs x 64 cycles / 4 SIMDs = 27.6 k cycles per step.
+struct RtsArgs {
+  const double* J;    // [n-1,T,T]
+  const double* P;    // [n-1,T,T]
+  const double* AM;   // [n-1,T]
+  double* M;          // [n,T]   in/out
+  double* Cv;         // [n,T,T] in/out
+  int n, T;
+};
+
+constexpr int RTS_WAVES = 12;   // three waves per SIMD: the LDS operand latency of one hides under the MFMAs of the others
+
+__global__ __launch_bounds__(64 * RTS_WAVES) void k_rts_chain(RtsArgs a) {
+  constexpr int NBR = 6, PITCH = 100;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double* Jl = smem;                    // [96][PITCH]
+  double* Dl = Jl + 96 * PITCH;         // [96][PITCH]  D, then X
+  double* vl = Dl + 96 * PITCH;         // [96]  m_{t+1} - A_t m_t
+  double* ml = vl + 96;                 // [96]  m_{t+1} (smoothed), then m_t
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int T = a.T;
+  const long tt = (long)T * T;
+  const int kpad = (T + 3) & ~3;          // k-steps beyond T multiply the zero padding
+  for (int i = tid; i < 96 * PITCH; i += 64 * RTS_WAVES) {   // zero padding once (rows/cols >= T are never written below)
+    Jl[i] = 0.0;
+    Dl[i] = 0.0;
+  }
+  if (tid < 96) {
+    vl[tid] = 0.0;
+    ml[tid] = (tid < T) ? a.M[(size_t)(a.n - 1) * T + tid] : 0.0;
+  }
+  // my tiles (I, Jc) = (wave / 2, 3 (wave % 2) + i), i = 0 .. 2, of a row-major [T,T] matrix, accumulator layout, zero outside
+  auto load_tiles = [&](const double* __restrict__ X, d4 (&v)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int I = wave >> 1, Jc = 3 * (wave & 1) + i;   // my three tiles share block row I (one A operand per k-step for three MFMAs)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * I + g + 4 * r, col = 16 * Jc + c;
+        v[i][r] = (row < T && col < T) ? X[(size_t)row * T + col] : 0.0;
+      }
+    }
+  };
+  // rows wave, wave + 12, ... of J (8 rows per wave), columns lane and lane + 64
+  auto load_rows = [&](const double* __restrict__ X, double (&v)[8][2]) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int r = wave + RTS_WAVES * u;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int q = lane + 64 * h;
+        v[u][h] = (r < T && q < T) ? X[(size_t)r * T + q] : 0.0;
+      }
+    }
+  };
+  d4 cn[3], pt[3], ct[3];
+  double jv[8][2];
+  double am = 0.0, mt = 0.0;
+  load_tiles(a.Cv + (size_t)(a.n - 1) * tt, cn);          // C_{n-1}: the last filtered state is its own smoothed state
+  {
+    const int t = a.n - 2;
+    load_rows(a.J + (size_t)t * tt, jv);
+    load_tiles(a.P + (size_t)t * tt, pt);
+    load_tiles(a.Cv + (size_t)t * tt, ct);
+    if (tid < T) {
+      am = a.AM[(size_t)t * T + tid];
+      mt = a.M[(size_t)t * T + tid];
+    }
+  }
+  __syncthreads();
+  for (int t = a.n - 2; t >= 0; --t) {
+    // ---- stage J_t (rows) and D = C_{t+1} - P_t (my tiles), v = m_{t+1} - A_t m_t
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int r = wave + RTS_WAVES * u;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int q = lane + 64 * h;
+        if (r < T && q < T) Jl[r * PITCH + q] = jv[u][h];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int I = wave >> 1, Jc = 3 * (wave & 1) + i;   // my three tiles share block row I (one A operand per k-step for three MFMAs)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Dl[(16 * I + g + 4 * r) * PITCH + 16 * Jc + c] = cn[i][r] - pt[i][r];
+    }
+    const double mt_cur = mt;
+    if (tid < T) vl[tid] = ml[tid] - am;
+    __syncthreads();
+    // ---- requests of step t - 1 (filtered quantities only): in flight under both product phases
+    if (t > 0) {
+      load_rows(a.J + (size_t)(t - 1) * tt, jv);
+      load_tiles(a.P + (size_t)(t - 1) * tt, pt);
+      if (tid < T) {
+        am = a.AM[(size_t)(t - 1) * T + tid];
+        mt = a.M[(size_t)(t - 1) * T + tid];
+      }
+    }
+    // ---- X = J D
+    d4 X[3];
+    {
+      const int I = wave >> 1, J0 = 3 * (wave & 1);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) X[i] = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll 8
+      for (int k = 0; k < kpad; k += 4) {
+        const double av = Jl[(16 * I + c) * PITCH + k + g];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) X[i] = mfma(av, Dl[(k + g) * PITCH + 16 * (J0 + i) + c], X[i]);
+      }
+    }
+    // ---- m_t += J v : eight lanes per row, 12 columns each, summed inside the 8-lane group
+    double mnew = 0.0;
+    {
+      const int row = tid >> 3, part = tid & 7;
+      double sv = 0.0;
+      if (row < T)
+        for (int j = part; j < T; j += 8) sv = fma(Jl[row * PITCH + j], vl[j], sv);
+      sv += __shfl_xor(sv, 1, 64);
+      sv += __shfl_xor(sv, 2, 64);
+      sv += __shfl_xor(sv, 4, 64);
+      mnew = sv;                             // valid in the lanes with part == 0
+    }
+    __syncthreads();                         // every wave has finished reading D, v and m_{t+1}
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int I = wave >> 1, Jc = 3 * (wave & 1) + i;   // my three tiles share block row I (one A operand per k-step for three MFMAs)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Dl[(16 * I + g + 4 * r) * PITCH + 16 * Jc + c] = X[i][r];
+    }
+    if ((tid & 7) == 0 && (tid >> 3) < T) vl[tid >> 3] = mnew;        // J v, row-indexed (v is dead)
+    __syncthreads();
+    if (tid < T) {                           // m_t = (filtered m_t) + J v: out to memory, and kept for the next step
+      const double m = mt_cur + vl[tid];
+      ml[tid] = m;
+      a.M[(size_t)t * T + tid] = m;
+    }
+    // ---- C_t = (filtered C_t) + X J^T : the result stays in cn for the next step
+    double* Ct = a.Cv + (size_t)t * tt;
+    {
+      const int I = wave >> 1, J0 = 3 * (wave & 1);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) cn[i] = ct[i];
+#pragma unroll 8
+      for (int k = 0; k < kpad; k += 4) {
+        const double av = Dl[(16 * I + c) * PITCH + k + g];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) cn[i] = mfma(av, Jl[(16 * (J0 + i) + c) * PITCH + k + g], cn[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * I + g + 4 * r, col = 16 * (J0 + i) + c;
+          if (row < T && col < T) Ct[(size_t)row * T + col] = cn[i][r];
+        }
+      }
+    }
+    if (t > 0) load_tiles(a.Cv + (size_t)(t - 1) * tt, ct);          // consumed one whole step later
+    __syncthreads();                         // LDS free for the next step; m_t visible
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -514,16 +689,11 @@ int hgp_chol_inverse_rhs_batched_f64(const double* A, int T, int b, double jitte
   // workgroups per CU at NB = 6); 32 < T <= 64: the barrier form (T = 50: 13.1 us against 14.7 / 16.5); T <= 32 is one wave anyway
   const long wgs = (long)b * 2 * ((T + 15) >> 4);
   if (T > 64 && wgs <= (nb_for(T) == 6 ? 2 : 1) * (long)coop_max_wg) {
-    return nb_for(T) == 6 ? launch_cooph_inv_rhs<6>(a, st) : launch_cooph_inv_rhs<8>(a, st);
+    return nb_for(T) == 6 ? launch_cooph_inv_rhs<6>(a, st) : launch_cooph_inv_rhs<8>(a, st);   // own choice: T > 64 only has {6, 8}
   } else if (T > 32 && T <= 64 && wgs <= coop_max_wg) {
     return launch_coop_inv_rhs<4>(a, st);
   }
-  switch (nb_for(T)) {
-    case 2: launch_inv_rhs<2>(a, st); break;
-    case 4: launch_inv_rhs<4>(a, st); break;
-    case 6: launch_inv_rhs<6>(a, st); break;
-    default: launch_inv_rhs<8>(a, st); break;
-  }
+  dispatch_nb_wave(T, [&](auto nb) { launch_inv_rhs<decltype(nb)::value>(a, st); });
   return launch_status();
 }
 
@@ -544,6 +714,18 @@ int hgp_lds_chain_finish2_batched_f64(const hgp_chain_finish_desc* descs_dev, in
   const long n2 = 2L * T * T;
   hipLaunchKernelGGL(k_chain_finish2_b, dim3((unsigned)std::min<long>(64, (n2 + 255) / 256), (unsigned)n_chains), dim3(256), 0,
                      (hipStream_t)stream, descs_dev);
+  return launch_status();
+}
+
+
+int hgp_rts_chain_f64(const double* J, const double* P, const double* AM, double* M, double* Cv, int n, int T, void* stream) {
+  if (!J || !P || !AM || !M || !Cv || n < 0 || T <= 0) return -1;
+  if (T > 96) return -2;
+  if (n < 2) return 0;
+  RtsArgs a{J, P, AM, M, Cv, n, T};
+  const size_t lds = sizeof(double) * (2 * 96 * 100 + 2 * 96);
+  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_rts_chain), lds)) return rc_;
+  hipLaunchKernelGGL(k_rts_chain, dim3(1), dim3(64 * RTS_WAVES), lds, (hipStream_t)stream, a);
   return launch_status();
 }
 

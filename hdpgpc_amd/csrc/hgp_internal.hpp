@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hdpgpc_hip.h"
@@ -19,6 +20,26 @@ static inline int nb_for(int n) {  // tile count, rounded to the instantiated si
   int nb = (n + 15) / 16;
   nb = (nb + 1) & ~1;
   return nb < 2 ? 2 : nb;
+}
+
+// The runtime tile count as a compile-time NB, decided once: f(std::integral_constant<int, NB>) with the instantiated size for a
+// matrix of order T - the one-wave kernels {2,4,6,8} (T <= HGP_MAX_T_WAVE) and the cooperative kernels {12,16} (T <= HGP_MAX_T_COOP).
+template <class F> static inline auto dispatch_nb_wave(int T, F&& f) {
+  switch (nb_for(T)) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+template <class F> static inline auto dispatch_nb_coop(int T, F&& f) {
+  return T <= 192 ? f(std::integral_constant<int, 12>{}) : f(std::integral_constant<int, 16>{});
+}
+template <class F> static inline auto dispatch_nb(int NB, F&& f) {   // a plan's tile count NB = TP / 16: either family
+  return NB <= 8 ? dispatch_nb_wave(16 * NB, f) : dispatch_nb_coop(16 * NB, f);
+}
+template <class F> static inline auto dispatch_bool(bool on, F&& f) {   // the same for a template flag: f(std::true_type) or f(std::false_type)
+  return on ? f(std::true_type{}) : f(std::false_type{});
 }
 
 static inline bool env_on(const char* name) {
@@ -68,25 +89,52 @@ struct hgp_pairs_plan {
   int score_out = 0;            // hgp_pairs_plan_set_score_output: out_quad receives -0.5 quad - 0.5 Ts log(2 pi)
 };
 
+// hgp_factor.hip: arguments of the factor / inverse-factor kernels
+struct PotrfArgs {
+  double* A;
+  int T, b;
+  double jitter_rel, add;
+  double* Linv;
+  double* logdet;
+  int32_t* info;
+  int inv_info = 0;   // k_wave_inv also reports info (used when no in-place factor follows)
+  int symmetric = 0;  // the caller guarantees A == A^T bit for bit: only the upper tiles are read
+  double* Aout = nullptr;   // cooperative factor only: L goes here instead of over A (hgp_chol_inverse_ws_f64)
+};
+// Z = chol(A)^-1 for a plan of NB tiles (inverse factor only below NB = 12; A receives L from there on)
+int hgp_internal_chol_inverse(const PotrfArgs& a, int NB, hipStream_t st);
+// hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device), under a lock
+int hgp_internal_ensure_dynamic_lds(const void* fn, size_t bytes);
+
+// hgp_gemm.hip: C[b] = alpha op(A[b]) op(B[b]) + beta C[b] (or + beta D[b]), and the batched reductions of the a9 composition
+struct GemmArgs {
+  const double* A;
+  const double* B;
+  double* C;
+  int M, N, Kd, lda, ldb, ldc;
+  long sA, sB, sC;
+  double alpha, beta;
+  int tA, tB;
+  int nb2 = 1;                 // optional second batch level: item b = b1 * nb2 + b2 uses offsets b1 * s?  + b2 * s?2
+  long sA2 = 0, sB2 = 0, sC2 = 0;
+  const double* D = nullptr;   // optional addend (instead of C): C = alpha op(A) op(B) + beta D
+  int ldd = 0;
+  long sD = 0;
+  int boff = 0;                // first batch item of this launch (gridDim.y is capped at 65535: larger batches go in chunks)
+  int triA = 0;                // A (not transposed) is lower triangular: row tile ti only needs k < 16 (ti + 1)
+};
+int hgp_internal_gemm(const GemmArgs& a, int batch, hipStream_t st);
+void hgp_internal_dot_batched(const double* X, const double* Y, long sX, long sY, long n, double scale, int accumulate, double* out, int b, hipStream_t st);
+void hgp_internal_colnorm_diag(const double* Z, const double* S, long sS, int T, double scale, int accumulate, double* out, int b, hipStream_t st);
+void hgp_internal_sub_batched(const double* A, const double* B, long sA, long sB, long n, double* C, int b, hipStream_t st);
+
 // hgp_pairs_acc.hip
 int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, hipStream_t st);
 int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts, const double* first_noise,
                            const int32_t* sel, double* out_quad, double* out_logdet, int32_t* out_info, hipStream_t st);
 size_t hgp_internal_acc_bytes(int TP, int K, size_t* sizes /*[6]*/);
 
-// hgp_assign.hip: batched LogLik normalisation / arg-max of the state posterior (B score matrices [N, K] back to back)
-int hgp_internal_loglik_rows_b(const double* q, int N, int K, int B, double* out, hipStream_t st);
-int hgp_internal_assign_b(const double* fmsg, const double* bmsg, int N, int K, int B, int64_t* labels, double* last_log, hipStream_t st);
-
-// hgp_matlik.hip: fused one-wave-per-item kernels of a8 / a9 (T <= HGP_MAX_T_WAVE)
-int hgp_internal_lat_error_wave(const double* f_cur, const double* f_prev, const double* A, const double* Gamma, const double* covprev,
-                                int T, int b, double* out, int32_t* info, hipStream_t st);
-int hgp_internal_mniw_wave(const double* M, const double* Sigma, const double* m_mean, const double* m_r_cov, const double* scale,
-                           int scale_is_diagonal, long prior_stride, int T, int b, double* out, int32_t* info, hipStream_t st);
-
 // hgp_matlik_coop.hip: the same two terms for 128 < T <= HGP_MAX_T_COOP, one workgroup per item (factor once, packed factor in ws)
-size_t hgp_internal_matlik_coop_ws_doubles(int T);
-size_t hgp_internal_lat_coop_ws_doubles(int T);
 int hgp_internal_lat_coop(const double* f_cur, const double* f_prev, const double* A, const double* Gamma, const double* P, int T, int b,
                           double* out, int32_t* info, double* ws, hipStream_t st);
 int hgp_internal_mniw_coop(const double* M, const double* Sigma, const double* m_mean, const double* scale, long prior_stride, int T, int b,
@@ -129,5 +177,3 @@ struct PairsArgs {
 extern unsigned long long* hgp_internal_stamp_dev;
 #endif
 int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t st);
-// hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device), under a lock
-int hgp_internal_ensure_dynamic_lds(const void* fn, size_t bytes);

@@ -375,39 +375,93 @@ __global__ __launch_bounds__(64 * WAVES, (NB <= 6 && !HASR && SDIAG) ? 2 : 1) vo
   }
 }
 
-}  // namespace
-
-int hgp_internal_lat_error_wave(const double* f_cur, const double* f_prev, const double* A, const double* Gamma, const double* covprev,
-                                int T, int b, double* out, int32_t* info, hipStream_t st) {
+// the fused one-wave-per-item kernels (T <= HGP_MAX_T_WAVE)
+int lat_error_wave(const double* f_cur, const double* f_prev, const double* A, const double* Gamma, const double* covprev,
+                   int T, int b, double* out, int32_t* info, hipStream_t st) {
   LatArgs a{f_cur, f_prev, A, Gamma, covprev, T, b, out, info};
   dim3 grid((b + WAVES - 1) / WAVES), blk(64 * WAVES);
-  switch (nb_for(T)) {
-    case 2: hipLaunchKernelGGL(k_wave_lat_gram<2>, grid, blk, 0, st, a); break;
-    case 4: hipLaunchKernelGGL(k_wave_lat_gram<4>, grid, blk, 0, st, a); break;
-    case 6: hipLaunchKernelGGL(k_wave_lat_gram<6>, grid, blk, 0, st, a); break;
-    default: hipLaunchKernelGGL(k_wave_lat<8>, grid, blk, 0, st, a); break;   // 64 tiles of Y do not fit next to the factor: panel form
-  }
+  dispatch_nb_wave(T, [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    if constexpr (NB == 8) hipLaunchKernelGGL(k_wave_lat<8>, grid, blk, 0, st, a);   // 64 tiles of Y do not fit next to the factor: panel form
+    else hipLaunchKernelGGL(k_wave_lat_gram<NB>, grid, blk, 0, st, a);
+  });
   return launch_status();
 }
 
-int hgp_internal_mniw_wave(const double* M, const double* Sigma, const double* m_mean, const double* m_r_cov, const double* scale,
-                           int scale_is_diagonal, long prior_stride, int T, int b, double* out, int32_t* info, hipStream_t st) {
+int mniw_wave(const double* M, const double* Sigma, const double* m_mean, const double* m_r_cov, const double* scale,
+              int scale_is_diagonal, long prior_stride, int T, int b, double* out, int32_t* info, hipStream_t st) {
   MniwArgs a{M, Sigma, m_mean, m_r_cov, scale, scale_is_diagonal, prior_stride, T, b, out, info};
   dim3 grid((b + WAVES - 1) / WAVES), blk(64 * WAVES);
-  const bool hasr = m_r_cov != nullptr, sd = scale_is_diagonal != 0;
-#define HGP_MNIW(NB_)                                                                                         \
-  do {                                                                                                        \
-    if (hasr && sd) hipLaunchKernelGGL((k_wave_mniw<NB_, true, true>), grid, blk, 0, st, a);                  \
-    else if (hasr) hipLaunchKernelGGL((k_wave_mniw<NB_, true, false>), grid, blk, 0, st, a);                  \
-    else if (sd) hipLaunchKernelGGL((k_wave_mniw<NB_, false, true>), grid, blk, 0, st, a);                    \
-    else hipLaunchKernelGGL((k_wave_mniw<NB_, false, false>), grid, blk, 0, st, a);                           \
-  } while (0)
-  switch (nb_for(T)) {
-    case 2: HGP_MNIW(2); break;
-    case 4: HGP_MNIW(4); break;
-    case 6: HGP_MNIW(6); break;
-    default: HGP_MNIW(8); break;
-  }
-#undef HGP_MNIW
+  dispatch_nb_wave(T, [&](auto nb) {
+    dispatch_bool(m_r_cov != nullptr, [&](auto hasr) {
+      dispatch_bool(scale_is_diagonal != 0, [&](auto sd) {
+        hipLaunchKernelGGL((k_wave_mniw<decltype(nb)::value, decltype(hasr)::value, decltype(sd)::value>), grid, blk, 0, st, a);
+      });
+    });
+  });
   return launch_status();
 }
+
+}  // namespace
+
+extern "C" {
+
+size_t hgp_matrix_lik_ws_bytes(int T, int b) { return (size_t)b * ((size_t)4 * T * T + T) * sizeof(double) + 256; }
+
+int hgp_lat_error_f64(const double* f_cur, const double* f_prev, const double* A, const double* Gamma, const double* covprev,
+                      int T, int b, double* out, int32_t* info, void* ws, size_t ws_bytes, void* stream) {
+  if (!f_cur || !f_prev || !A || !Gamma || !covprev || !out || T <= 0 || b < 0) return -1;
+  if (b == 0) return 0;
+  if (T > HGP_MAX_T_COOP) return -2;
+  if (T <= HGP_MAX_T_WAVE)   // fused: one wavefront per item, nothing goes through the workspace
+    return lat_error_wave(f_cur, f_prev, A, Gamma, covprev, T, b, out, info, (hipStream_t)stream);
+  if (!ws || ws_bytes < hgp_matrix_lik_ws_bytes(T, b)) return -1;
+  // 128 < T <= 256: one fused cooperative kernel per item, Gram form (hgp_matlik_coop.hip)
+  return hgp_internal_lat_coop(f_cur, f_prev, A, Gamma, covprev, T, b, out, info, (double*)ws, (hipStream_t)stream);
+}
+
+int hgp_mniw_loglik_f64(const double* M, const double* Sigma, const double* m_mean, const double* m_r_cov,
+                        const double* scale, int scale_is_diagonal, long prior_stride, int T, int b, double* out, int32_t* info,
+                        void* ws, size_t ws_bytes, void* stream) {
+  if (!M || !Sigma || !m_mean || !scale || !out || T <= 0 || b < 0) return -1;
+  if (b == 0) return 0;
+  if (T > HGP_MAX_T_COOP) return -2;
+  if (T <= HGP_MAX_T_WAVE)   // fused: one wavefront per item, nothing goes through the workspace
+    return mniw_wave(M, Sigma, m_mean, m_r_cov, scale, scale_is_diagonal, prior_stride, T, b, out, info, (hipStream_t)stream);
+  if (!ws || ws_bytes < hgp_matrix_lik_ws_bytes(T, b)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  // the hot path's call (identity right covariance, diagonal prior scale): one fused cooperative kernel per item (hgp_matlik_coop.hip)
+  if (!m_r_cov && scale_is_diagonal)
+    return hgp_internal_mniw_coop(M, Sigma, m_mean, scale, prior_stride, T, b, out, info, (double*)ws, st);
+  // everything else at 128 < T <= 256: composition of the batched kernels
+  const long tt = (long)T * T;
+  double* Sc = (double*)ws;
+  double* Z = Sc + (size_t)b * tt;
+  double* D = Z + (size_t)b * tt;
+  double* Y = D + (size_t)b * tt;
+  if (hipMemcpyAsync(Sc, Sigma, sizeof(double) * b * tt, hipMemcpyDeviceToDevice, st) != hipSuccess) return launch_status();
+  int rc = hgp_potrf_batched_f64(Sc, T, b, 0.0, 1e-8, Z, nullptr, info, stream);   // chol(0.5(S+S^T) + 1e-8 I), GPI_model.py:1353
+  if (rc) return rc;
+  hgp_internal_sub_batched(M, m_mean, tt, prior_stride, tt, D, b, st);
+  GemmArgs g1{Z, D, Y, T, T, T, T, T, T, tt, tt, tt, 1.0, 0.0, 0, 0};              // Y = L^{-1} D
+  g1.triA = 1;
+  if ((rc = hgp_internal_gemm(g1, b, st))) return rc;
+  if (m_r_cov) {                                                                     // sum (D R) o Sigma^{-1} D = sum (Y R) o Y
+    GemmArgs g2{Y, m_r_cov, D, T, T, T, T, T, T, tt, prior_stride, tt, 1.0, 0.0, 0, 0};
+    if ((rc = hgp_internal_gemm(g2, b, st))) return rc;
+    hgp_internal_dot_batched(D, Y, tt, tt, tt, -0.5, 0, out, b, st);
+  } else {
+    hgp_internal_dot_batched(Y, Y, tt, tt, tt, -0.5, 0, out, b, st);
+  }
+  if (scale_is_diagonal) {   // the hot path's prior scale sigma I: trace(Sigma^{-1} S) = sum_j S_jj |Z e_j|^2, no product
+    hgp_internal_colnorm_diag(Z, scale, prior_stride, T, -0.5, 1, out, b, st);
+    return launch_status();
+  }
+  GemmArgs g3{Z, scale, Y, T, T, T, T, T, T, tt, prior_stride, tt, 1.0, 0.0, 0, 0};  // trace(Sigma^{-1} S) = sum (Z S) o Z
+  g3.triA = 1;
+  if ((rc = hgp_internal_gemm(g3, b, st))) return rc;
+  hgp_internal_dot_batched(Y, Z, tt, tt, tt, -0.5, 1, out, b, st);
+  return launch_status();
+}
+
+}  // extern "C"

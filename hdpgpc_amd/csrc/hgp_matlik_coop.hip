@@ -482,20 +482,16 @@ int launch_coop_lat(const LatCoopArgs& a, hipStream_t st) {
 
 }  // namespace
 
-size_t hgp_internal_lat_coop_ws_doubles(int T) { return T <= 192 ? lat_ws_doubles<12>() : lat_ws_doubles<16>(); }
-
 // a8, 128 < T <= 256
 int hgp_internal_lat_coop(const double* f_cur, const double* f_prev, const double* A, const double* Gamma, const double* P, int T, int b,
                           double* out, int32_t* info, double* ws, hipStream_t st) {
   LatCoopArgs a{f_cur, f_prev, A, Gamma, P, T, b, out, info, ws};
-  return T <= 192 ? launch_coop_lat<12>(a, st) : launch_coop_lat<16>(a, st);
+  return dispatch_nb_coop(T, [&](auto nb) { return launch_coop_lat<decltype(nb)::value>(a, st); });
 }
-
-size_t hgp_internal_matlik_coop_ws_doubles(int T) { return T <= 192 ? packed_doubles<12>() : packed_doubles<16>(); }
 
 // a9, identity right covariance and diagonal prior scale, 128 < T <= 256
 int hgp_internal_mniw_coop(const double* M, const double* Sigma, const double* m_mean, const double* scale, long prior_stride, int T, int b,
                            double* out, int32_t* info, double* ws, hipStream_t st) {
   MniwCoopArgs a{M, Sigma, m_mean, scale, prior_stride, T, b, out, info, ws};
-  return T <= 192 ? launch_coop_mniw<12>(a, st) : launch_coop_mniw<16>(a, st);
+  return dispatch_nb_coop(T, [&](auto nb) { return launch_coop_mniw<decltype(nb)::value>(a, st); });
 }

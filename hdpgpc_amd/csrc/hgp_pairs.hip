@@ -1,7 +1,7 @@
 // a2 + a5, the per-pair kernels of hgp_loglik_pairs_f64 (explicit-operator evaluation of cov_f): k_pairs<NB> (T <= 128, one
 // wavefront per pair) and k_pairs_cooph<NB> (NB/2 waves per pair) for 128 < T <= 256.  (The 4-wave cooperative kernel of round 1,
 // k_pairs_coop, 1.28x slower, was removed in round 3.)
-// The plan (per-cluster operators) and the C-ABI live in hgp_kernels.hip; the solve-based kernel in hgp_pairs_acc.hip.
+// The plan (per-cluster operators) and the C-ABI live in hgp_plan.hip; the solve-based kernel in hgp_pairs_acc.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -1111,16 +1111,6 @@ int launch_pairs(const PairsArgs& a0, hipStream_t st) {
 
 // dispatch by padded size / kernel family (see hgp_loglik_pairs_f64)
 int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t st) {
-  if (coop) {   // NB/2 waves per pair (CoopH)
-    switch (NB) {
-      case 12: return launch_pairs_cooph<12>(a, st);
-      default: return launch_pairs_cooph<16>(a, st);
-    }
-  }
-  switch (NB) {
-    case 2: return launch_pairs<2>(a, st);
-    case 4: return launch_pairs<4>(a, st);
-    case 6: return launch_pairs<6>(a, st);
-    default: return launch_pairs<8>(a, st);
-  }
+  if (coop) return dispatch_nb_coop(16 * NB, [&](auto nb) { return launch_pairs_cooph<decltype(nb)::value>(a, st); });   // NB/2 waves per pair (CoopH)
+  return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs<decltype(nb)::value>(a, st); });
 }

@@ -1,7 +1,7 @@
 // Solve-based evaluation of the per-(segment, cluster) path (a2 + a5) for clusters whose kernel matrix K~ is
 // ill-conditioned (length-scale >> grid spacing, e.g. the drivers' ini_lengthscale = 3.0 on a unit-spaced grid).
 //
-// The explicit operator M' = c^2 (K~^-1 Sigma K~^-1 - K~^-1) of the fast kernels (hgp_kernels.hip) squares the condition
+// The explicit operator M' = c^2 (K~^-1 Sigma K~^-1 - K~^-1) of the fast kernels (hgp_plan.hip) squares the condition
 // number of K~: its rounding error relative to the reference's triangular solves grows like eps (c ||K~^-1||)^2 - 1e-11 at
 // ell = 1.2 but 1e-3 at ell = 3.  Here the reference's own operation order is kept (GPI.py:489-501):
 //     L L^T = K~;   S = L^-T (L^-1 K*)   (cholesky_solve, GPI.py:492);   f* = S^T m;
@@ -448,13 +448,10 @@ int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, hipStream_t st)
   const int K = p->K, TP = p->TP, NB = p->NB;
   hipLaunchKernelGGL(k_acc_flags, dim3(1), dim3(64), 0, st, p->d_scal, K, p->acc_tol, p->d_acc_list);
   if (p->acc_tol < 0.0) return launch_status();   // explicit operator everywhere: nothing else to prepare
-  switch (NB) {   // T <= 128: the plan update computed L^{-1} only; T > 128: d_A already holds L
-    case 2: hipLaunchKernelGGL(k_acc_factor<2>, dim3(K), dim3(64), 0, st, p->d_A, TP, p->d_scal, (int32_t*)nullptr); break;
-    case 4: hipLaunchKernelGGL(k_acc_factor<4>, dim3(K), dim3(64), 0, st, p->d_A, TP, p->d_scal, (int32_t*)nullptr); break;
-    case 6: hipLaunchKernelGGL(k_acc_factor<6>, dim3(K), dim3(64), 0, st, p->d_A, TP, p->d_scal, (int32_t*)nullptr); break;
-    case 8: hipLaunchKernelGGL(k_acc_factor<8>, dim3(K), dim3(64), 0, st, p->d_A, TP, p->d_scal, (int32_t*)nullptr); break;
-    default: break;
-  }
+  if (NB <= 8)   // T <= 128: the plan update computed L^{-1} only; T > 128: d_A already holds L
+    dispatch_nb_wave(TP, [&](auto nb) {
+      hipLaunchKernelGGL(k_acc_factor<decltype(nb)::value>, dim3(K), dim3(64), 0, st, p->d_A, TP, p->d_scal, (int32_t*)nullptr);
+    });
   AccPrepArgs a{p->d_A, p->d_S, mean, p->d_scal, p->T, TP, NB, p->d_Lop, p->d_LTop, p->d_Dop, p->d_Sop, p->d_mu};
   hipLaunchKernelGGL(k_acc_prep, dim3(K, 8), dim3(256), 0, st, a);
   return launch_status();
@@ -465,12 +462,5 @@ int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const double* x, const doubl
   if (p->acc_tol < 0.0) return 0;
   AccArgs a{x, y, N, Ts, p->d_xb, p->T, p->d_scal, p->d_mu, p->d_Lop, p->d_LTop, p->d_Dop, p->d_Sop, p->d_acc_list,
             first_noise, sel, p->K, out_quad, out_logdet, out_info, p->d_sscr, -0.5 * (double)Ts * 1.8378770664093453, p->score_out};
-  switch (p->NB) {
-    case 2: return launch_pairs_acc<2>(a, st);
-    case 4: return launch_pairs_acc<4>(a, st);
-    case 6: return launch_pairs_acc<6>(a, st);
-    case 8: return launch_pairs_acc<8>(a, st);
-    case 12: return launch_pairs_acc<12>(a, st);
-    default: return launch_pairs_acc<16>(a, st);
-  }
+  return dispatch_nb(p->NB, [&](auto nb) { return launch_pairs_acc<decltype(nb)::value>(a, st); });
 }

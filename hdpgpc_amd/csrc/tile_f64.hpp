@@ -864,7 +864,7 @@ __device__ __forceinline__ double coop_factor(d4 (&U)[Coop<NB>::NT], double* row
   // accumulator tile of U_KJ (K < J) IS the A operand of L[J, K] = U_KJ^T, so it is stored as it stands, 32 bytes per lane, at
   // tile index J (J - 1) / 2 + K; the inverses W_K of the diagonal blocks (A-operand order already) at tile index K of Wpack.
   // Wout (optional): the inverses W_K = L_KK^{-1} of the diagonal blocks go to the diagonal blocks of this [n, ldw] matrix -
-  // they ARE the diagonal blocks of L^{-1}; k_trtri (hgp_kernels.hip) fills in the rest from L.
+  // they ARE the diagonal blocks of L^{-1}; k_trtri (hgp_factor.hip) fills in the rest from L.
   // kstop (optional, the same in every thread): block steps K >= kstop are not taken - for callers whose blocks from kstop on are
   // identity padding (their factor is the identity, nothing of it is read) and who only want the right-hand side / the pivots.
   using C = Coop<NB>;

@@ -6,8 +6,8 @@ name=$1; shift
 od=build/probe/obj_$name
 mkdir -p $od hdpgpc_amd/lib/ab
 FLAGS="-O3 --offload-arch=gfx950 -mllvm -pragma-unroll-threshold=1048576 -fPIC -Wno-unused-result"
-for f in hgp_kernels hgp_pairs hgp_pairs_acc hgp_matlik hgp_matlik_coop hgp_assign hgp_warp hgp_chain; do
-  /opt/rocm/bin/hipcc $FLAGS "$@" -c -o $od/$f.o hdpgpc_amd/csrc/$f.hip &
+for src in hdpgpc_amd/csrc/*.hip; do   # the Makefile's SRCS
+  /opt/rocm/bin/hipcc $FLAGS "$@" -c -o $od/$(basename $src .hip).o $src &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o hdpgpc_amd/lib/ab/libhgp_$name.so $od/*.o
