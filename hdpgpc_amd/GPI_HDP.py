@@ -16,7 +16,9 @@ driver entry points -
 plus the small public helpers they and the drivers use (``LogLik``, ``_safe_exp``, ``weight_mean``, ``forward``,
 ``backward``, ``coupled_state_coef``, ``compute_trans_A/pi``, ``selected_gpmodels``).  NOT built (each raises
 NotImplementedError): ``include_sample(with_warp=True)`` (the reference's own path raises at its second beat), ``classify=True``,
-several leads online, static models, ``estimation_limit``, inducing points, different initial ``kernels=`` per cluster, ``bayesian_params=False``.
+several leads online, static models, ``estimation_limit``, inducing points, ``bayesian_params=False``.  ``kernels=`` IS built: scikit-learn
+``ConstantKernel * RBF + WhiteKernel`` objects or ``RBFWhiteKernel`` are read for their parameters, one kernel for all initial clusters (what
+every driver passes); only a list whose kernels differ from cluster to cluster raises.
 
 Kernel hyper-parameters: the reference fits them with gpytorch on the first member of every cluster (GPI.py:610-770).
 ``GPI_HDP.fixed_theta = (outputscale, lengthscale, noise)`` injects them instead (what the golden fixtures do); with

@@ -309,6 +309,33 @@ class GPI_model:
         mean = ops.gemm_batched(self.C[-1], self.f_star_sm[-1])
         return self.gp.pred_dist(x_post, self.x_basis, mean, self.Sigma[-1])
 
+    def bands(self, x_post, ts=None, check=True):
+        """Mean and pointwise variance of observe_last(x_post) (ts=None) or of observe(x_post, t) for every t of `ts`, in one
+        device call (ops.pred_bands): (mean [n,Q], var [n,Q]) = f_star[:,0] and diag(cov_f) of those calls, without their
+        [Q,Q] covariances.  On the basis grid itself it returns C f and diag Sigma (GPI.py:467-468)."""
+        T = self.x_basis.shape[0]
+        xq = self.cond_to_torch(x_post).reshape(-1).contiguous()
+        if ts is None:
+            ci = [len(self.Sigma) - 1]                      # observe_last reads Sigma[-1]
+            mean = ops.gemm_batched(self.C[-1], self.f_star_sm[-1]).reshape(1, T)
+        else:
+            sel = [self._select(int(t)) for t in ts]
+            ci = [c for c, _ in sel]
+            if len(sel) == 0:
+                empty = torch.empty((0, xq.numel()), dtype=f64, device=self.device)
+                return empty, empty.clone()
+            cix = ops.to_dev(ci, torch.int64, self.device)
+            fix = ops.to_dev([f for _, f in sel], torch.int64, self.device)
+            mean = ops.gemm_batched(self._S("C").index_select(0, cix).contiguous(),
+                                    self._S("f_star").reshape(-1, T, 1).index_select(0, fix).contiguous()).reshape(-1, T)
+        Sig = self._S("Sigma")
+        sidx = ops.to_dev(ci, torch.int32, self.device)
+        if xq.shape == self.x_basis.reshape(-1).shape and torch.equal(xq, self.x_basis.reshape(-1)):
+            return mean, torch.diagonal(Sig, dim1=1, dim2=2).index_select(0, sidx.to(torch.int64)).contiguous()
+        mean_q, var_q, _ = ops.pred_bands(self.x_basis.reshape(-1).contiguous(), self.gp.kernel.params(), mean.contiguous(), Sig,
+                                          xq, sigma_idx=sidx, check=check)
+        return mean_q, var_q
+
     def step_forward_last(self, x_post, params=None):
         """GPI_model.py:595-615."""
         if params is None:

@@ -442,6 +442,73 @@ def kl_sym(meanA, covA, meanB=None, covB=None):
     return out
 
 
+# (device index, raw stream handle) -> workspace of hgp_pred_bands_f64.  One per stream, so calls queued on different streams of a
+# device never share K~ / Z buffers; it grows to the largest call seen and is kept until pred_bands_release() (S = 2 000 states at
+# T = 90 hold 259 MB).  The key is the raw stream handle: a stream that is created, used for a call and destroyed leaves its entry
+# behind until pred_bands_release().
+_bands_ws = {}
+
+
+def pred_bands_release():
+    """Drop the cached workspaces of pred_bands (the memory returns to torch's allocator once queued calls have finished)."""
+    _bands_ws.clear()
+
+
+def pred_bands_ws_doubles(S, T):
+    """HGP_BANDS_WS_DOUBLES of include/hdpgpc_hip.h."""
+    return (3 if T > 128 else 2) * S * T * T + 5 * S
+
+
+def pred_bands(x_basis, theta, mean, Sigma, xq, sigma_idx=None, check=False):
+    """a2 on a query grid for S states in one call (hgp_pred_bands_f64): what pred_dist returns as f_star and diag(cov_f).
+    x_basis [T]; theta [S,3] = (c, ell, noise) per state (or one triple for all); mean [S,T]; Sigma a stack [*,T,T] of which
+    state s reads Sigma[sigma_idx[s]] (int32 device tensor; None: s); xq [Q].  Returns (mean_q [S,Q], var_q [S,Q], info [S]);
+    a state with info != 0 has NaN rows.  The values of sigma_idx must lie in [0, len(Sigma)): the kernels do not check them
+    (an index outside reads outside the stack).  No synchronisation unless check=True, which validates sigma_idx on the host
+    before the launch and raises on info after it.  The equal-grid short-circuit of GPI.py:467 is the caller's."""
+    x_basis = _dev64(x_basis.reshape(-1), "x_basis")
+    xq = _dev64(xq.reshape(-1), "xq")
+    Sigma = _dev64(Sigma, "Sigma")
+    T, Q, dev = x_basis.numel(), xq.numel(), x_basis.device
+    if Sigma.dim() != 3 or tuple(Sigma.shape[1:]) != (T, T):
+        raise ValueError("pred_bands: Sigma must be a stack [*, T, T] on the basis grid")
+    mean = _dev64(mean, "mean")
+    if mean.numel() % T:
+        raise ValueError("pred_bands: mean must be [S, T]")
+    mean = mean.reshape(-1, T)
+    S = mean.shape[0]
+    if not torch.is_tensor(theta):
+        theta = to_dev(np.broadcast_to(np.asarray(theta, dtype=np.float64).reshape(-1, 3), (S, 3)), torch.float64, dev)
+    theta = _dev64(theta, "theta")
+    if tuple(theta.shape) != (S, 3):
+        raise ValueError("pred_bands: theta must be [S, 3]")
+    if sigma_idx is None:
+        if Sigma.shape[0] != S:
+            raise ValueError("pred_bands: without sigma_idx the stack holds one Sigma per state")
+    elif not (torch.is_tensor(sigma_idx) and sigma_idx.is_cuda and sigma_idx.dtype == torch.int32 and sigma_idx.is_contiguous()
+              and sigma_idx.numel() == S):
+        raise TypeError("pred_bands: sigma_idx must be a contiguous int32 tensor [S] on the GPU")
+    mean_q = torch.empty((S, Q), dtype=torch.float64, device=dev)
+    var_q = torch.empty((S, Q), dtype=torch.float64, device=dev)
+    info = torch.zeros(S, dtype=torch.int32, device=dev)
+    if S == 0 or Q == 0:
+        return mean_q, var_q, info
+    if check and sigma_idx is not None and not bool(((sigma_idx >= 0) & (sigma_idx < Sigma.shape[0])).all()):
+        raise IndexError("pred_bands: sigma_idx out of range")
+    need = pred_bands_ws_doubles(S, T)
+    with torch.cuda.device(dev):
+        stream = _stream()
+    key = (dev.index, stream.value)
+    ws = _bands_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _bands_ws[key] = torch.empty(need, dtype=torch.float64, device=dev)
+    _ffi.check(_ffi.lib.hgp_pred_bands_f64(_ptr(x_basis), T, _ptr(theta), _ptr(mean), _ptr(Sigma), _ptr(sigma_idx), S, _ptr(xq), Q,
+                                           _ptr(mean_q), _ptr(var_q), _ptr(info), _ptr(ws), stream), "pred_bands")
+    if check:
+        raise_on_info(info, "pred_bands")
+    return mean_q, var_q, info
+
+
 def rts_chain(J, P, AM, M, Cv):
     """Sequential part of the RTS smoother for all steps in one launch (in place on M [n,T] and Cv [n,T,T]); T <= 96."""
     n, T = M.shape[0], Cv.shape[1]

@@ -1,6 +1,8 @@
 """hdpgpc/hdpgpc/util_plots.py: the result table the drivers print (util_plots.py:269-299).  Figures are presentation and
-out of scope: plot_models_plotly is a no-op that says so; plot_MDS / plot_MDS_plotly compute and
-return the distance matrix their figure is drawn from (util_plots.py:598-688) and draw nothing."""
+out of scope: every plot_* function computes and returns what its figure is drawn from and draws
+nothing - plot_models / plot_models_plotly / plot_partial_models the cluster templates with their predictive bands on the
+plotting grid (model_bands, model_evolution: one device call for all states, util_plots.py:335-476,755-772), plot_MDS /
+plot_MDS_plotly the distance matrix (util_plots.py:598-688)."""
 import numpy as np
 import torch
 
@@ -33,11 +35,84 @@ def print_results(sw_gp, labels, N_0, error=False, purity=False):
     return main_model
 
 
-def plot_models_plotly(*args, save=None, **kwargs):
-    """util_plots.py:725-794 draws the clusters with plotly / matplotlib: presentation, not part of this build (SURVEY.md
-    section 2, row 12).  Every reference driver ends with this call, so it returns quietly instead of raising."""
-    print("plot_models_plotly: figures are not part of the MI355X build" + (f" (nothing written to {save})" if save else ""))
-    return None
+def _plot_grid(gp, step):
+    """torch.arange(min(x_b), max(x_b), step) of util_plots.py:755-756, on the host."""
+    x_b = gp.x_basis.reshape(-1).cpu()
+    return x_b, torch.arange(float(x_b.min()), float(x_b.max()), step, dtype=torch.float64)
+
+
+def model_bands(sw_gp, selected_gpmodels=None, lead=0, step=0.1, width=1.9):
+    """What plot_models_plotly / plot_models draw for every selected cluster (util_plots.py:755-772), from ONE device call
+    for all of them: per cluster a dict with `x` = arange(min x_b, max x_b, step), `mean` and `var` of observe_last on it,
+    `lower` / `upper` = mean -/+ width sqrt(var), and the latent band on the basis grid: `x_basis`, `mean_latent` =
+    f_star_sm[-1], `noise_latent` = width sqrt(diag Gamma[-1]).  Returns {cluster index: dict}, numpy arrays on the host."""
+    from . import ops
+
+    models = sw_gp.gpmodels[lead]
+    sel = list(range(len(models))) if selected_gpmodels is None else [int(m) for m in selected_gpmodels]
+    out = {}
+    if not sel:
+        return out
+    gps = [models[m] for m in sel]
+    grids = [_plot_grid(gp, step) for gp in gps]
+    shared = all(g[0].shape == grids[0][0].shape and torch.equal(g[0], grids[0][0]) for g in grids)
+    if shared and grids[0][1].numel() > 0:
+        g0 = gps[0]
+        dev = g0.device
+        T = g0.x_basis.shape[0]
+        theta = ops.to_dev(np.asarray([gp.gp.kernel.params() for gp in gps], dtype=np.float64), torch.float64, dev)
+        mean = torch.cat([ops.gemm_batched(gp.C[-1], gp.f_star_sm[-1]).reshape(1, T) for gp in gps]).contiguous()
+        Sig = torch.stack([gp.Sigma[-1] for gp in gps]).contiguous()
+        mq, vq, _ = ops.pred_bands(g0.x_basis.reshape(-1).contiguous(), theta, mean, Sig, grids[0][1].to(dev), check=True)
+        res = [(mq[i], vq[i]) for i in range(len(gps))]
+    else:   # clusters on different basis grids: one call each
+        res = [tuple(v[0] for v in gp.bands(g[1])) for gp, g in zip(gps, grids)]
+    for m, gp, (x_b, x_), (mq, vq) in zip(sel, gps, grids, res):
+        mean, var = mq.cpu().numpy(), vq.cpu().numpy()
+        sd = np.sqrt(var)
+        out[m] = {"x": x_.numpy(), "mean": mean, "var": var, "lower": mean - width * sd, "upper": mean + width * sd,
+                  "x_basis": x_b.numpy(), "mean_latent": gp.f_star_sm[-1].reshape(-1).cpu().numpy(),
+                  "noise_latent": width * np.sqrt(np.diag(gp.Gamma[-1].cpu().numpy()))}
+    return out
+
+
+def model_evolution(sw_gp, m, lead=0, step=0.1, ts=None):
+    """The bands of one cluster at every member step (ts=None: all of them) - observe(x, t) of plot_partial_models
+    (util_plots.py:451-476) for the whole history in one device call.  Returns a dict: `x`, `mean` and `var` [n_steps, Q],
+    `ts` and `indexes` (the member segment of each step)."""
+    gp = sw_gp.gpmodels[lead][m]
+    ts = list(range(len(gp.indexes))) if ts is None else [int(t) for t in ts]
+    _, x_ = _plot_grid(gp, step)
+    mq, vq = gp.bands(x_, ts)
+    return {"x": x_.numpy(), "mean": mq.cpu().numpy(), "var": vq.cpu().numpy(), "ts": np.asarray(ts, dtype=np.int64),
+            "indexes": np.asarray([gp.indexes[t] if 0 <= t < len(gp.indexes) else -1 for t in ts], dtype=np.int64)}
+
+
+def _no_figure(name, save):
+    print(f"{name}: figures are not part of the MI355X build" + (f" (nothing written to {save})" if save else ""))
+
+
+def plot_models_plotly(sw_gp, selected_gpmodels, main_model=None, labels=None, N_0=0, save=None, lead=0, step=0.1,
+                       plot_latent=False, ticks=False):
+    """util_plots.py:725-794 without the figure: computes and returns what it is drawn from (model_bands)."""
+    data = model_bands(sw_gp, selected_gpmodels, lead=lead, step=step)
+    _no_figure("plot_models_plotly", save)
+    return data
+
+
+def plot_models(sw_gp, selected_gpmodels, main_model=None, labels=None, N_0=0, save=None, lead=0, step=0.1, plot_latent=False):
+    """util_plots.py:301-419 without the figure: computes and returns what it is drawn from (model_bands)."""
+    data = model_bands(sw_gp, selected_gpmodels, lead=lead, step=step)
+    _no_figure("plot_models", save)
+    return data
+
+
+def plot_partial_models(sw_gp, selected_gpmodels, main_model=None, labels=None, N_0=0, time_instant=(-1,), save=None):
+    """util_plots.py:421-520 without the figure: for every selected cluster the bands of observe(x, t) at the steps of
+    `time_instant` (model_evolution on the reference's 0.1 grid).  Returns {cluster index: dict}."""
+    data = {int(m): model_evolution(sw_gp, int(m), ts=list(time_instant)) for m in selected_gpmodels}
+    _no_figure("plot_partial_models", save)
+    return data
 
 
 def kl_distance_matrix(sw_gp, lead=0, smoothed=False):

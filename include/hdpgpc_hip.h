@@ -325,6 +325,25 @@ int hgp_lml_grad_f64(const double* x, const double* alpha, const double* Kinv, i
 int hgp_kl_sym_f64(const double* meanA, const double* covA, const double* precA, int nA, const double* meanB, const double* covB,
                    const double* precB, int nB, int T, double* out, void* stream);
 
+/* a2 on a query grid, mean and pointwise variance only - what IterativeGaussianProcess.pred_dist (GPI.py:457-503) returns as
+ * f_star and diag(cov_f), for S states and Q query points in three launches, without the [Q,Q] covariance:
+ *   jitter_s = 1e-4 max(mean|diag Sigma_s|, eps),  K~_s = ker(x_basis, x_basis) + jitter_s I (two-argument Gram: no white noise),
+ *   W = K~_s^-1 ker(x_basis, xq)  (explicit inverse factor + one step of iterative refinement),   mean_q[s] = W^T mean[s],
+ *   var_q[s,q] = (c + noise) - sum_t K*[t,q] W[t,q] + sum_t W[t,q] (Sigma_s W)[t,q] + 1e-6;
+ *   if diag Sigma_s is isclose to its mean m (torch defaults, GPI.py:497) var_q[s,:] = m.  Decided on the device per state.
+ * The equal-grid short-circuit of GPI.py:467 is NOT applied here (the Python layer does).
+ * x_basis [T], T <= HGP_MAX_T_COOP; theta3 [S,3] = (c, ell, noise) per state; mean [S,T]; Sigma a stack [*,T,T] of which state
+ * s reads matrix sigma_idx[s] (int32; NULL: s; the values are NOT range-checked: the caller guarantees 0 <= sigma_idx[s] < the
+ * stack's length); xq [Q], any order, any Q >= 1; mean_q, var_q [S,Q]; info [S].
+ * ws: caller-provided workspace of HGP_BANDS_WS_DOUBLES(S, T) doubles (K~, its inverse factor, per-state scalars).
+ * info[s] != 0 (the failing pivot of K~_s, or -1 when diag Sigma_s is not finite): both output rows of s are NaN, the other
+ * states are unaffected.  An output element depends on its own state and query point only and is reduced in an order fixed
+ * by T: the same bits for any Q, any position in xq, any S. */
+#define HGP_BANDS_WS_DOUBLES(S, T) ((size_t)((T) > HGP_MAX_T_WAVE ? 3 : 2) * (size_t)(S) * (T) * (T) + (size_t)5 * (S))
+int hgp_pred_bands_f64(const double* x_basis, int T, const double* theta3, const double* mean, const double* Sigma,
+                       const int32_t* sigma_idx, int S, const double* xq, int Q, double* mean_q, double* var_q, int32_t* info,
+                       double* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
