@@ -3,8 +3,9 @@ error behaviour); all arithmetic runs in HIP kernels through hdpgpc_amd.ops.
 
 Built: the kernel object (scikit-learn's ConstantKernel*RBF + WhiteKernel, GPI_HDP.py:164-166),
 IterativeGaussianProcess.pred_dist (GPI.py:457-503), pred_latent_dist (GPI.py:505-560),
-log_marginal_likelihood (GPI.py:976-1056, value and gradient), KL_divergence (GPI.py:1058-1094).  Not built here: posterior / backward (the LDS recursion,
-SURVEY.md 8f-1) and fit_torch (gpytorch, 8f-2).
+log_marginal_likelihood (GPI.py:976-1056, value and gradient), KL_divergence (GPI.py:1058-1094), sample_y (GPI.py:564-608, same
+distribution from torch's normals, see its docstring).  Not built here: posterior / backward (the LDS recursion)
+and fit_torch (gpytorch, 8f-2).
 """
 import math
 
@@ -139,6 +140,33 @@ class IterativeGaussianProcess:
         term_data = ops.gemm_batched(K_X_Xs, sol_K, transA=True)
         term_prior = ops.gemm_batched(K_X_Xs, solve(ops.gemm_batched(cov_prior, sol_K)), transA=True)
         return f_star, K_Xs_Xs - term_data + term_prior
+
+    def standard_normals(self, shape, random_state=0):
+        """The normals every sample_* method of the mirror draws from: torch.randn of `shape` from a torch.Generator on this
+        device seeded with `random_state` (an int).  torch is the random-number generator and the container, nothing else."""
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(int(random_state))
+        return torch.randn(tuple(shape), generator=gen, dtype=torch_f64, device=self.device)
+
+    def sample_y(self, f_mean, f_cov, C, Sigma, n_samples=1, random_state=0):
+        """GPI.py:564-608: n_samples observations y ~ N(C f_mean, C f_cov C^T + Sigma), [T, n_samples] for a 1-D f_mean and
+        [T, D, n_samples] for [T, D] (every column its own draws, one covariance), in one device call (ops.sample_states).
+        Parity with the reference is SAME DISTRIBUTION, NOT THE SAME NUMBERS: numpy's multivariate_normal draws from its own
+        stream and factors the covariance by SVD, so even identical normals would give other curves.  What is matched is the
+        map z -> mean + chol(cov) z and the moments fed to it; z = standard_normals([n, T]) ([D, n, T] for D columns)."""
+        f_mean = self.cond_to_torch(f_mean)
+        one = f_mean.dim() == 1
+        F = f_mean.reshape(f_mean.shape[0], -1).contiguous()                     # [T, D]
+        T, D = F.shape
+        C = self.cond_to_torch(C).reshape(T, T).contiguous()
+        P = self.cond_to_torch(f_cov).reshape(T, T).contiguous()
+        Sigma = self.cond_to_torch(Sigma).reshape(T, T).contiguous()
+        mean = ops.gemm_batched(F, C, transA=True, transB=True).contiguous()     # [D, T] = (C F)^T
+        cov = ops.gemm_batched(ops.gemm_batched(C, P), C, transB=True, add=Sigma).reshape(1, T, T)
+        z = self.standard_normals([n_samples, T] if one else [D, n_samples, T], random_state)
+        idx = torch.zeros(D, dtype=torch.int32, device=self.device)
+        out, _ = ops.sample_states(mean, cov, z, cov_idx=idx)                    # [D, n, T]
+        return out[0].T if one else out.permute(2, 0, 1)
 
     def KL_divergence(self, mean1, cov1, mean2, cov2):
         """GPI.py:1058-1094: symmetric Kullback-Leibler divergence of two Gaussians, the 1 x 1 case of ops.kl_sym (Cholesky

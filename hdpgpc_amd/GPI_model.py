@@ -371,6 +371,37 @@ class GPI_model:
         S = ops.gemm_batched(ops.gemm_batched(C, P), C, transB=True, add=Sig.contiguous())
         return ops.gemm_batched(C, f).reshape(-1, T), 0.5 * (S + S.transpose(1, 2))
 
+    # ------------------------------------------------------------------ a14: curves drawn from states
+    def sample_states(self, ts=None, num_samples=1, random_state=0, z=None, smoothed=True, latent=False):
+        """Curves drawn from the Gaussians of this cluster's states, [len(ts), n, T] on the device, in one call
+        (ops.sample_states): out[i, j] = mean_i + chol(cov_i) z_j.  ts=None is the one state sample_last reads, C[-1]
+        f_star_sm[-1] and C[-1] cov_f_sm[-1] C[-1]^T + Sigma[-1]; otherwise (mean, cov) = observed_moments(ts, smoothed, latent)
+        (latent=True: the latent f, P themselves).  z ([n,T] or [len(ts),n,T]) is used as given; otherwise z [n,T] =
+        gp.standard_normals(random_state), SHARED by all states: common random numbers across the steps of a cluster make an
+        evolution plot move smoothly instead of flickering with independent noise.
+        Parity with the reference (GPI_model.py:953-961, GPI.py:564-608) is same distribution, not the same numbers: see
+        IterativeGaussianProcess.sample_y."""
+        T = self.x_basis.shape[0]
+        if ts is None:
+            C, P = self.C[-1].contiguous(), self.cov_f_sm[-1].contiguous()
+            mean = ops.gemm_batched(C, self.f_star_sm[-1].reshape(T, 1)).reshape(1, T)
+            cov = ops.gemm_batched(ops.gemm_batched(C, P), C, transB=True, add=self.Sigma[-1].contiguous()).reshape(1, T, T)
+        else:
+            mean, cov = self.observed_moments(ts, smoothed, latent)
+        if z is None:
+            z = self.gp.standard_normals([int(num_samples), T], random_state)
+        else:
+            z = self.cond_to_torch(z).contiguous()
+        if mean.shape[0] == 0:
+            return torch.empty((0, z.shape[-2], T), dtype=f64, device=self.device)
+        out, _ = ops.sample_states(mean.contiguous(), cov.contiguous(), z)
+        return out
+
+    def sample_last(self, num_samples=1, random_state=0):
+        """GPI_model.py:953-961: num_samples curves drawn from the last smoothed state as observed, a list of length-T tensors
+        (views of one [n,T] result of sample_states(ts=None)).  Same distribution as the reference, not the same numbers."""
+        return list(self.sample_states(None, num_samples, random_state)[0])
+
     def _kl_moments_on(self, ts, smoothed, x_bas, latent=None):
         """observed_moments, or the observe(x_bas, t, params=...) route of GPI_model.py:923-925 when x_bas is another grid."""
         latent = self._kl_static() if latent is None else latent

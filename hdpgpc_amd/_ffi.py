@@ -63,6 +63,7 @@ def _load():
         "hgp_lml_grad_f64": (i32, [vp, vp, vp, i32, f64, f64, f64, vp, vp]),
         "hgp_kl_sym_f64": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]),
         "hgp_pred_bands_f64": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+        "hgp_sample_states_f64": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, f64, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header and library disagree

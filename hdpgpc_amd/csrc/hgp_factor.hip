@@ -17,11 +17,11 @@ __global__ __launch_bounds__(64 * WAVES) void k_wave_potrf(PotrfArgs a) {
   const int m = blockIdx.x * WAVES + wave;
   if (m >= a.b) return;
   double* scr = scr_all + wave * DIAG_SCR;
-  double* A = a.A + (size_t)m * a.T * a.T;
   const int T = a.T;
+  double* A = (a.Aout ? a.Aout : a.A) + (size_t)m * T * T;     // where L goes
   d4 U[NB * (NB + 1) / 2];
   d4 R[NB];
-  load_sym_upper<NB>(U, A, T, T, lane, scr);
+  load_sym_upper<NB>(U, a.A + (size_t)(a.src_idx ? a.src_idx[m] : m) * T * T, T, T, lane, scr);
   if (a.add != 0.0) add_diag<NB>(U, a.add, T, lane);
   if (a.jitter_rel != 0.0) {
     double dm = diag_abs_mean<NB>(U, T, lane);
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_potrf(PotrfArgs a) {
   const int T = a.T;
   double* A = (a.Aout ? a.Aout : a.A) + (size_t)m * T * T;     // where L goes
   d4 U[C::NT];
-  coop_load_sym_upper<NB>(U, a.A + (size_t)m * T * T, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
+  coop_load_sym_upper<NB>(U, a.A + (size_t)(a.src_idx ? a.src_idx[m] : m) * T * T, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
   __syncthreads();   // rowbuf served as per-wave staging for the loader
   {
     double sh = a.add;
@@ -532,6 +532,17 @@ int hgp_internal_chol_inverse(const PotrfArgs& a, int NB, hipStream_t st) {
   // one workgroup per block column (the trailing updates split over its four waves) halves the latency at T = 128
   if (NB == 8) return launch_coop_inv_only<8>(a, st);
   dispatch_nb_wave(16 * NB, [&](auto nb) { launch_wave_inv<decltype(nb)::value>(a, st); });
+  return launch_status();
+}
+
+int hgp_internal_potrf_ws(const double* A, const int32_t* idx, int T, int b, double jitter_rel, double* L, int32_t* info, hipStream_t st) {
+  PotrfArgs a{const_cast<double*>(A), T, b, jitter_rel, 0.0, nullptr, nullptr, info};
+  a.Aout = L;
+  a.src_idx = idx;
+  if (T > HGP_MAX_T_WAVE) return dispatch_nb_coop(T, [&](auto nb) { return launch_coop_potrf<decltype(nb)::value>(a, st); });
+  dispatch_nb_wave(T, [&](auto nb) {
+    hipLaunchKernelGGL(k_wave_potrf<decltype(nb)::value>, dim3((b + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a);
+  });
   return launch_status();
 }
 

@@ -99,8 +99,11 @@ struct PotrfArgs {
   int32_t* info;
   int inv_info = 0;   // k_wave_inv also reports info (used when no in-place factor follows)
   int symmetric = 0;  // the caller guarantees A == A^T bit for bit: only the upper tiles are read
-  double* Aout = nullptr;   // cooperative factor only: L goes here instead of over A (hgp_chol_inverse_ws_f64)
+  double* Aout = nullptr;   // factor kernels: L goes here instead of over A (hgp_chol_inverse_ws_f64, hgp_internal_potrf_ws)
+  const int32_t* src_idx = nullptr;   // factor kernels: item m reads matrix src_idx[m] of A (NULL: m); needs Aout
 };
+// L[b,T,T] = the a3 factor of A[idx[m]] (idx NULL: A[m]) for m < b, zeros above the diagonal; A is only read.  One launch.
+int hgp_internal_potrf_ws(const double* A, const int32_t* idx, int T, int b, double jitter_rel, double* L, int32_t* info, hipStream_t st);
 // Z = chol(A)^-1 for a plan of NB tiles (inverse factor only below NB = 12; A receives L from there on)
 int hgp_internal_chol_inverse(const PotrfArgs& a, int NB, hipStream_t st);
 // hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device), under a lock

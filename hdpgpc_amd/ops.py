@@ -509,6 +509,66 @@ def pred_bands(x_basis, theta, mean, Sigma, xq, sigma_idx=None, check=False):
     return mean_q, var_q, info
 
 
+# (device index, raw stream handle) -> workspace of hgp_sample_states_f64, kept like pred_bands's until sample_release()
+_sample_ws = {}
+
+
+def sample_release():
+    """Drop the cached workspaces of sample_states (the memory returns to torch's allocator once queued calls have finished)."""
+    _sample_ws.clear()
+
+
+def sample_ws_doubles(S, T):
+    """HGP_SAMPLE_WS_DOUBLES of include/hdpgpc_hip.h."""
+    return S * T * T + S
+
+
+def sample_states(mean, cov, z, cov_idx=None, jitter_rel=0.0, check=True):
+    """a14: draws from the Gaussians of S states in one call (hgp_sample_states_f64): out[s,j] = mean[s] + chol(A_s) z_j with
+    A_s = 0.5 (cov_m + cov_m^T) + jitter_rel mean|diag cov_m| I, m = cov_idx[s] (int32 device tensor; None: s).
+    mean [S,T]; cov a stack [*,T,T] (not modified); z standard normals, [n,T] shared by every state or [S,n,T].  Returns
+    (out [S,n,T], info [S]); a state with info != 0 (failing pivot; -1: non-finite diagonal) has NaN draws, the others are
+    unaffected.  The values of cov_idx must lie in [0, len(cov)): the kernels do not check them.  No synchronisation unless
+    check=True, which validates cov_idx on the host before the launch and raises on info after it."""
+    cov = _dev64(cov, "cov")
+    if cov.dim() != 3 or cov.shape[1] != cov.shape[2]:
+        raise ValueError("sample_states: cov must be a stack [*, T, T]")
+    T, dev = cov.shape[1], cov.device
+    mean = _dev64(mean, "mean")
+    if T == 0 or mean.numel() % T:
+        raise ValueError("sample_states: mean must be [S, T]")
+    mean = mean.reshape(-1, T)
+    S = mean.shape[0]
+    z = _dev64(z, "z")
+    if z.dim() not in (2, 3) or z.shape[-1] != T or (z.dim() == 3 and z.shape[0] != S):
+        raise ValueError("sample_states: z must be [n, T] (shared) or [S, n, T]")
+    n = z.shape[-2]
+    if cov_idx is None:
+        if cov.shape[0] != S:
+            raise ValueError("sample_states: without cov_idx the stack holds one covariance per state")
+    elif not (torch.is_tensor(cov_idx) and cov_idx.is_cuda and cov_idx.dtype == torch.int32 and cov_idx.is_contiguous()
+              and cov_idx.numel() == S):
+        raise TypeError("sample_states: cov_idx must be a contiguous int32 tensor [S] on the GPU")
+    out = torch.empty((S, n, T), dtype=torch.float64, device=dev)
+    info = torch.zeros(S, dtype=torch.int32, device=dev)
+    if S == 0 or n == 0:
+        return out, info
+    if check and cov_idx is not None and not bool(((cov_idx >= 0) & (cov_idx < cov.shape[0])).all()):
+        raise IndexError("sample_states: cov_idx out of range")
+    need = sample_ws_doubles(S, T)
+    with torch.cuda.device(dev):
+        stream = _stream()
+    key = (dev.index, stream.value)
+    ws = _sample_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _sample_ws[key] = torch.empty(need, dtype=torch.float64, device=dev)
+    _ffi.check(_ffi.lib.hgp_sample_states_f64(_ptr(mean), _ptr(cov), _ptr(cov_idx), T, S, _ptr(z), n, int(z.dim() == 2),
+                                              float(jitter_rel), _ptr(out), _ptr(info), _ptr(ws), stream), "sample_states")
+    if check:
+        raise_on_info(info, "sample_states")
+    return out, info
+
+
 def rts_chain(J, P, AM, M, Cv):
     """Sequential part of the RTS smoother for all steps in one launch (in place on M [n,T] and Cv [n,T,T]); T <= 96."""
     n, T = M.shape[0], Cv.shape[1]

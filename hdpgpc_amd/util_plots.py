@@ -76,6 +76,46 @@ def model_bands(sw_gp, selected_gpmodels=None, lead=0, step=0.1, width=1.9):
     return out
 
 
+def model_samples(sw_gp, selected_gpmodels=None, lead=0, num_samples=10, random_state=0):
+    """Curves drawn from every selected cluster of a lead (default sw_gp.selected_gpmodels(), or all of them where the driver
+    has no such method), each from its last smoothed state as observed - GPI_model.sample_last for all clusters from ONE
+    device call (ops.sample_states), with the same normals for every cluster.  Returns a dict of host arrays: `x_basis` [T],
+    `clusters` (their indices), `mean` [K,T] = C f_star_sm of the last state, `samples` [K,n,T].  Clusters on basis grids of
+    different lengths go in one call per length; `x_basis`, `mean` and `samples` are then lists with one entry per cluster.
+    Same distribution as the reference's sample_last, not the same numbers (IterativeGaussianProcess.sample_y)."""
+    from . import ops
+
+    models = sw_gp.gpmodels[lead]
+    if selected_gpmodels is None:
+        selected_gpmodels = sw_gp.selected_gpmodels() if hasattr(sw_gp, "selected_gpmodels") else range(len(models))
+    sel = [int(m) for m in selected_gpmodels]
+    gps = [models[m] for m in sel]
+    n = int(num_samples)
+    mean, samples = [None] * len(gps), [None] * len(gps)
+    by_T = {}
+    for k, gp in enumerate(gps):
+        by_T.setdefault(int(gp.x_basis.shape[0]), []).append(k)
+    for T, ks in by_T.items():
+        g0 = gps[ks[0]]
+        C = torch.stack([gps[k].C[-1] for k in ks]).contiguous()
+        P = torch.stack([gps[k].cov_f_sm[-1] for k in ks]).contiguous()
+        f = torch.stack([gps[k].f_star_sm[-1].reshape(T, 1) for k in ks]).contiguous()
+        Sig = torch.stack([gps[k].Sigma[-1] for k in ks]).contiguous()
+        mu = ops.gemm_batched(C, f).reshape(len(ks), T)
+        cov = ops.gemm_batched(ops.gemm_batched(C, P), C, transB=True, add=Sig)
+        out, _ = ops.sample_states(mu, cov, g0.gp.standard_normals([n, T], random_state))
+        mu, out = mu.cpu().numpy(), out.cpu().numpy()
+        for i, k in enumerate(ks):
+            mean[k], samples[k] = mu[i], out[i]
+    xb = [gp.x_basis.reshape(-1).cpu().numpy() for gp in gps]
+    res = {"x_basis": xb, "clusters": np.asarray(sel, dtype=np.int64), "mean": mean, "samples": samples}
+    if len(by_T) == 1:
+        res.update(x_basis=xb[0], mean=np.stack(mean), samples=np.stack(samples))
+    elif not gps:
+        res.update(x_basis=np.zeros(0), mean=np.zeros((0, 0)), samples=np.zeros((0, n, 0)))
+    return res
+
+
 def model_evolution(sw_gp, m, lead=0, step=0.1, ts=None):
     """The bands of one cluster at every member step (ts=None: all of them) - observe(x, t) of plot_partial_models
     (util_plots.py:451-476) for the whole history in one device call.  Returns a dict: `x`, `mean` and `var` [n_steps, Q],

@@ -344,6 +344,22 @@ int hgp_pred_bands_f64(const double* x_basis, int T, const double* theta3, const
                        const int32_t* sigma_idx, int S, const double* xq, int Q, double* mean_q, double* var_q, int32_t* info,
                        double* ws, void* stream);
 
+/* a14 - draws from the Gaussians of cluster states: what GPI_model.sample_last (GPI_model.py:953-961) and
+ * IterativeGaussianProcess.sample_y (GPI.py:564-608) take from numpy's multivariate_normal, as the map from standard normals
+ * to curves, for S states and n draws in two launches.  For state s with m = cov_idx ? cov_idx[s] : s:
+ *   A = 0.5 (cov_m + cov_m^T) + jitter_rel max(mean|diag cov_m|, eps) I   (a3, as hgp_potrf_batched_f64; jitter_rel = 0: nothing added),
+ *   A = L L^T, L lower,     out[s,j,:] = mean[s,:] + L z_j   for every draw j.
+ * mean [S,T], T <= HGP_MAX_T_COOP; cov a stack [*,T,T], only read (int32 cov_idx; NULL: s; the values are NOT range-checked: the
+ * caller guarantees 0 <= cov_idx[s] < the stack's length); z standard normals, [n,T] used by every state (z_shared != 0) or
+ * [S,n,T]; out [S,n,T]; info [S].
+ * ws: caller-provided workspace of HGP_SAMPLE_WS_DOUBLES(S, T) doubles (the factors and their status).
+ * info[s] != 0 (the first pivot that was not positive, or -1 when diag cov_m is not finite): all n T outputs of s are NaN, the
+ * other states are unaffected.  A draw depends on mean[s], cov_m and z_j only and is summed in an order fixed by T: the same bits
+ * for any S, n, z_shared, any position of the state in the call and of the draw in z. */
+#define HGP_SAMPLE_WS_DOUBLES(S, T) ((size_t)(S) * (T) * (T) + (size_t)(S))
+int hgp_sample_states_f64(const double* mean, const double* cov, const int32_t* cov_idx, int T, int S, const double* z, int n,
+                          int z_shared, double jitter_rel, double* out, int32_t* info, double* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
