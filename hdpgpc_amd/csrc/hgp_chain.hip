@@ -172,11 +172,7 @@ template <int NB>
 __global__ __launch_bounds__(64 * WAVES) void k_coop_inv_rhs(InvRhsArgs a) {
   using C = Coop<NB>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* rowbuf = smem;
-  double* Rbuf = rowbuf + NB * 256;
-  double* Wbuf = Rbuf + NB * 256;
-  double* scr = Wbuf + 256;
-  double* red = scr + DIAG_SCR;
+  const auto [rowbuf, Rbuf, Wbuf, scr, red, redi] = C::lds(smem);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int g = lane >> 4, c = lane & 15;
   const int T = a.T, nblk = (T + 15) >> 4;
@@ -192,11 +188,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_inv_rhs(InvRhsArgs a) {
   d4 U[C::NT];
   coop_load_sym_upper<NB>(U, A, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
   __syncthreads();   // rowbuf served as per-wave staging for the loader
-  {
-    double sh = a.add;
-    if (a.jitter_rel != 0.0) sh += a.jitter_rel * fmax(coop_diag_abs_mean<NB>(U, T, wave, lane, a.add, red), F64_EPS);
-    if (sh != 0.0) coop_add_diag<NB>(U, sh, T, wave, lane);
-  }
+  coop_regularise<NB>(U, a.add, a.jitter_rel, T, wave, lane, red);
   const double* B = is_rhs ? a.rhs + (size_t)m * T * T : nullptr;
   for (int K = wave; K < NB; K += WAVES) {
     d4 v;
@@ -223,7 +215,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_inv_rhs(InvRhsArgs a) {
   }
   if (Jq == (a.Linv ? 0 : nblk) && a.info) {   // the first panel sees every pivot
     int info;
-    (void)coop_logdet_info(pa, wave, lane, red, reinterpret_cast<int*>(red + 8), info);
+    (void)coop_logdet_info(pa, wave, lane, red, redi, info);
     if (threadIdx.x == 0) a.info[m] = info;
   }
 }
@@ -259,11 +251,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW) void k_cooph_inv_rhs(InvRhsArgs
 #pragma unroll
   for (int i_ = 0; i_ < C::NT; ++i_) U[i_] = (d4){0.0, 0.0, 0.0, 0.0};
   cooph_load_sym_upper<NB>(U, A, T, T, wave, lane, scr);
-  {
-    double sh = a.add;
-    if (a.jitter_rel != 0.0) sh += a.jitter_rel * fmax(cooph_diag_abs_mean<NB>(U, T, wave, lane, a.add, red), F64_EPS);
-    if (sh != 0.0) cooph_add_diag<NB>(U, sh, T, wave, lane);
-  }
+  cooph_regularise<NB>(U, a.add, a.jitter_rel, T, wave, lane, red);
   // my two tiles of the right-hand side panel: block rows JA = wave and JB = NB - 1 - wave
   const double* B = is_rhs ? a.rhs + (size_t)m * T * T : nullptr;
   d4 RA, RB;

@@ -22,6 +22,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_wave_potrf(PotrfArgs a) {
   d4 U[NB * (NB + 1) / 2];
   d4 R[NB];
   load_sym_upper<NB>(U, a.A + (size_t)(a.src_idx ? a.src_idx[m] : m) * T * T, T, T, lane, scr);
+  // TWO passes: add first, the mean of the diagonal so shifted, then the jitter - an entry rounds as (d + add) + jit
   if (a.add != 0.0) add_diag<NB>(U, a.add, T, lane);
   if (a.jitter_rel != 0.0) {
     double dm = diag_abs_mean<NB>(U, T, lane);
@@ -136,6 +137,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_wave_score(ScoreArgs a) {
   double* Wl = w_all + wave * NB * 256;
   load_sym_upper<NB>(U, S, a.ld_sigma, T, lane, scr);
   const double add = a.item_add ? a.item_add[it] : 0.0;
+  // TWO passes, as in k_wave_potrf: an entry rounds as (d + add) + jit
   if (add != 0.0) add_diag<NB>(U, add, T, lane);
   if (a.jitter_rel != 0.0) {
     double dm = diag_abs_mean<NB>(U, T, lane);
@@ -241,12 +243,7 @@ template <int NB>
 __global__ __launch_bounds__(64 * WAVES) void k_coop_score(ScoreArgs a) {
   using C = Coop<NB>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* rowbuf = smem;
-  double* Rbuf = rowbuf + NB * 256;
-  double* Wbuf = Rbuf + NB * 256;
-  double* scr = Wbuf + 256;
-  double* red = scr + DIAG_SCR;
-  int* redi = reinterpret_cast<int*>(red + 8);
+  const auto [rowbuf, Rbuf, Wbuf, scr, red, redi] = C::lds(smem);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int g = lane >> 4, c = lane & 15;
   const int it = blockIdx.x;
@@ -260,14 +257,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_score(ScoreArgs a) {
   for (int base = 0; base < cnt; base += 16) {     // every chunk of 16 segments refactors (rare for T > 128)
     coop_load_sym_upper<NB>(U, S, a.ld_sigma, T, wave, lane, rowbuf + wave * DIAG_SCR);
     __syncthreads();   // rowbuf served as per-wave staging for the loader
-    {
-      double sh = add;
-      if (a.jitter_rel != 0.0) {
-        const double dm = coop_diag_abs_mean<NB>(U, T, wave, lane, add, red);
-        sh += a.jitter_rel * fmax(dm, F64_EPS);
-      }
-      if (sh != 0.0) coop_add_diag<NB>(U, sh, T, wave, lane);
-    }
+    coop_regularise<NB>(U, add, a.jitter_rel, T, wave, lane, red);
     const int j = base + c;
     const bool live = j < cnt;
     const int seg = live ? (a.seg_ids ? a.seg_ids[off + j] : off + j) : 0;
@@ -311,12 +301,7 @@ template <int NB>
 __global__ __launch_bounds__(64 * WAVES) void k_coop_potrf(PotrfArgs a) {
   using C = Coop<NB>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* rowbuf = smem;
-  double* Rbuf = rowbuf + NB * 256;
-  double* Wbuf = Rbuf + NB * 256;
-  double* scr = Wbuf + 256;
-  double* red = scr + DIAG_SCR;
-  int* redi = reinterpret_cast<int*>(red + 8);
+  const auto [rowbuf, Rbuf, Wbuf, scr, red, redi] = C::lds(smem);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int m = blockIdx.x;
   const int T = a.T;
@@ -324,14 +309,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_potrf(PotrfArgs a) {
   d4 U[C::NT];
   coop_load_sym_upper<NB>(U, a.A + (size_t)(a.src_idx ? a.src_idx[m] : m) * T * T, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
   __syncthreads();   // rowbuf served as per-wave staging for the loader
-  {
-    double sh = a.add;
-    if (a.jitter_rel != 0.0) {
-      const double dm = coop_diag_abs_mean<NB>(U, T, wave, lane, a.add, red);
-      sh += a.jitter_rel * fmax(dm, F64_EPS);
-    }
-    if (sh != 0.0) coop_add_diag<NB>(U, sh, T, wave, lane);
-  }
+  coop_regularise<NB>(U, a.add, a.jitter_rel, T, wave, lane, red);
   __syncthreads();   // every wave has loaded its tiles before anyone overwrites A
   PivotAcc pa;
   pa.init();
@@ -431,11 +409,7 @@ template <int NB>
 __global__ __launch_bounds__(64 * WAVES) void k_coop_inv(PotrfArgs a) {
   using C = Coop<NB>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* rowbuf = smem;
-  double* Rbuf = rowbuf + NB * 256;
-  double* Wbuf = Rbuf + NB * 256;
-  double* scr = Wbuf + 256;
-  double* red = scr + DIAG_SCR;
+  const auto [rowbuf, Rbuf, Wbuf, scr, red, redi] = C::lds(smem);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int g = lane >> 4, c = lane & 15;
   const int m = blockIdx.x, Jc = blockIdx.y;
@@ -445,14 +419,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_inv(PotrfArgs a) {
   d4 U[C::NT];
   coop_load_sym_upper<NB>(U, A, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
   __syncthreads();   // rowbuf served as per-wave staging for the loader
-  {
-    double sh = a.add;
-    if (a.jitter_rel != 0.0) {
-      const double dm = coop_diag_abs_mean<NB>(U, T, wave, lane, a.add, red);
-      sh += a.jitter_rel * fmax(dm, F64_EPS);
-    }
-    if (sh != 0.0) coop_add_diag<NB>(U, sh, T, wave, lane);
-  }
+  coop_regularise<NB>(U, a.add, a.jitter_rel, T, wave, lane, red);
   for (int K = wave; K < NB; K += WAVES) {
     d4 v;
 #pragma unroll
@@ -474,7 +441,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_inv(PotrfArgs a) {
   }
   if (a.inv_info && Jc == 0) {   // inverse-only call: block column 0 saw every pivot
     int info;
-    (void)coop_logdet_info(pa, wave, lane, red, reinterpret_cast<int*>(red + 8), info);
+    (void)coop_logdet_info(pa, wave, lane, red, redi, info);
     if (threadIdx.x == 0 && a.info) a.info[m] = info;
   }
 }

@@ -155,12 +155,7 @@ __device__ __forceinline__ int matlik_factor(const double* __restrict__ S, int T
     __syncthreads();
   } else {
     using C = Coop<NB>;
-    double* rowbuf = smem;
-    double* Rbuf = rowbuf + NB * 256;
-    double* Wbuf = Rbuf + NB * 256;
-    double* scr = Wbuf + 256;
-    double* red = scr + DIAG_SCR;
-    int* redi = reinterpret_cast<int*>(red + 8);
+    const auto [rowbuf, Rbuf, Wbuf, scr, red, redi] = C::lds(smem);
     d4 U[C::NT];
     coop_load_sym_upper<NB>(U, S, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
     __syncthreads();   // rowbuf served as per-wave staging for the loader
@@ -320,12 +315,7 @@ __global__ __launch_bounds__((64 * MatlikLds<NB, DF>::NWK)) void k_coop_lat(LatC
     info = matlik_factor<NB, true>(a.Gamma + (size_t)m * tt, T, 0.0, 1e-8, smem, wave, lane, Lp, Wp);
   } else {   // (written out: through the helper the NB = 16 instance compiles 8 % slower - 0.54 vs 0.50 ms per 256 items)
     using C = Coop<NB>;
-    double* rowbuf = smem;
-    double* Rbuf = rowbuf + NB * 256;
-    double* Wbuf = Rbuf + NB * 256;
-    double* scr = Wbuf + 256;
-    double* redf = scr + DIAG_SCR;
-    int* redi = reinterpret_cast<int*>(redf + 8);
+    const auto [rowbuf, Rbuf, Wbuf, scr, redf, redi] = C::lds(smem);
     d4 U[C::NT];
     coop_load_sym_upper<NB>(U, a.Gamma + (size_t)m * tt, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
     __syncthreads();   // rowbuf served as per-wave staging for the loader

@@ -1028,11 +1028,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
 #undef HGP_CMMA
 
   // regularisation of the reference: +1e-6 I (GPI.py:501), + first, + 1e-8 mean|diag| I (GPI_model.py:83-87)
-  {
-    const double sh = 1e-6 + fn;
-    const double dm = cooph_diag_abs_mean<NB>(U, Ts, wave, lane, sh, red);   // (also orders the dvec writes: barrier)
-    cooph_add_diag<NB>(U, sh + 1e-8 * fmax(dm, F64_EPS), Ts, wave, lane);
-  }
+  cooph_regularise<NB>(U, 1e-6 + fn, 1e-8, Ts, wave, lane, red);   // (also orders the dvec writes: barrier)
   PivotAcc pa;
   pa.init();
   HGP_ACC(5);

@@ -747,7 +747,18 @@ struct Coop {
   // and the trailing updates of each elimination step are balanced the same way.
   __host__ __device__ static constexpr int col(int q, int wave) { return 4 * q + ((q & 1) ? 3 - wave : wave); }
   __host__ __device__ static constexpr int owner(int J) { return ((J >> 2) & 1) ? 3 - (J & 3) : (J & 3); }
-  static constexpr int LDS_DOUBLES = NB * 256 /*rowbuf*/ + NB * 256 /*Rbuf*/ + 256 /*Wbuf*/ + DIAG_SCR + 16;
+  // The dynamic LDS of a 4-wave cooperative kernel, carved in ONE place: `auto [rowbuf, Rbuf, Wbuf, scr, red, redi] = C::lds(smem)`.
+  // rowbuf / Rbuf: [NB] tiles each (rowbuf also serves the loader as per-wave staging), Wbuf: one tile, scr: the diag16 scratch,
+  // red[8] / redi[8 doubles]: the reductions.  The launchers reserve LDS_DOUBLES, the end of the last member.
+  struct Lds {
+    double *rowbuf, *Rbuf, *Wbuf, *scr, *red;
+    int* redi;
+  };
+  static constexpr int OFF_RBUF = NB * 256, OFF_WBUF = OFF_RBUF + NB * 256, OFF_SCR = OFF_WBUF + 256, OFF_RED = OFF_SCR + DIAG_SCR,
+                       OFF_REDI = OFF_RED + 8, LDS_DOUBLES = OFF_REDI + 8;
+  __device__ static __forceinline__ Lds lds(double* smem) {
+    return {smem, smem + OFF_RBUF, smem + OFF_WBUF, smem + OFF_SCR, smem + OFF_RED, reinterpret_cast<int*>(smem + OFF_REDI)};
+  }
 };
 
 __device__ __forceinline__ d4 lds_tile_load(const double* buf, int tile, int lane) {
@@ -848,6 +859,26 @@ __device__ __forceinline__ void coop_add_diag(d4 (&U)[Coop<NB>::NT], double shif
       }
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The regulariser of every kernel that factors a matrix:
+//     shift = add + jitter_rel * max(mean_i |A_ii + add|, eps),      A_ii += shift  for i < n
+// in ONE pass over the diagonal, so an entry rounds as d + (add + jit).  Returns the shift.  coop_regularise (Coop<NB>, red: the
+// layout's reduction slots) and cooph_regularise (CoopH<NB>, below) serve the cooperative kernels.  hgp_matlik_coop.hip and the
+// one-wave kernels keep the same three lines written out (their device code changes when the lines move into a function -
+// DESIGN.md 4.2 lists them, and the two kernels that round in TWO passes).
+// A literal add = 0.0 folds at the call site; so does the test of the shift when the jitter is a literal (the 1e-8 of the
+// likelihood kernels makes the shift positive).
+// ---------------------------------------------------------------------------------------------
+#define HGP_KNOWN_NONZERO(x) (__builtin_constant_p(x) && (x) != 0.0)
+template <int NB>
+__device__ __forceinline__ double coop_regularise(d4 (&U)[Coop<NB>::NT], double add, double jitter_rel, int n, int wave, int lane,
+                                                  double* red) {
+  double sh = add;
+  if (jitter_rel != 0.0) sh += jitter_rel * fmax(coop_diag_abs_mean<NB>(U, n, wave, lane, add, red), F64_EPS);
+  if (HGP_KNOWN_NONZERO(jitter_rel) || sh != 0.0) coop_add_diag<NB>(U, sh, n, wave, lane);
+  return sh;
 }
 
 // Factor (and eliminate the 16 right-hand sides held as tiles in Rbuf when RHS).  On exit Rbuf holds Z = L^{-1} R.
@@ -1079,6 +1110,16 @@ __device__ __forceinline__ void cooph_add_diag(d4 (&U)[CoopH<NB>::NT], double sh
       }
     }
   }
+}
+
+// coop_regularise for the tiles of CoopH<NB>; red[8]
+template <int NB>
+__device__ __forceinline__ double cooph_regularise(d4 (&U)[CoopH<NB>::NT], double add, double jitter_rel, int n, int wave, int lane,
+                                                   double* red) {
+  double sh = add;
+  if (jitter_rel != 0.0) sh += jitter_rel * fmax(cooph_diag_abs_mean<NB>(U, n, wave, lane, add, red), F64_EPS);
+  if (HGP_KNOWN_NONZERO(jitter_rel) || sh != 0.0) cooph_add_diag<NB>(U, sh, n, wave, lane);
+  return sh;
 }
 
 // 0.5 (A + A^T) of a row-major [n, ld] matrix into the CoopH tile layout of this wave (identity padding); scr_w: a 16 x 18 LDS

@@ -442,16 +442,35 @@ def kl_sym(meanA, covA, meanB=None, covB=None):
     return out
 
 
-# (device index, raw stream handle) -> workspace of hgp_pred_bands_f64.  One per stream, so calls queued on different streams of a
-# device never share K~ / Z buffers; it grows to the largest call seen and is kept until pred_bands_release() (S = 2 000 states at
-# T = 90 hold 259 MB).  The key is the raw stream handle: a stream that is created, used for a call and destroyed leaves its entry
-# behind until pred_bands_release().
-_bands_ws = {}
+class _StreamWorkspace:
+    """(device index, raw stream handle) -> fp64 workspace of one entry point.  One per stream, so calls queued on different streams
+    of a device never share buffers; it grows to the largest call seen and is kept until release() (pred_bands: S = 2 000 states at
+    T = 90 hold 259 MB).  The key is the raw stream handle: a stream that is created, used for a call and destroyed leaves its
+    entry behind until release()."""
+
+    def __init__(self):
+        self._ws = {}
+
+    def get(self, dev, need):
+        """(workspace of at least `need` doubles, current stream of dev)"""
+        with torch.cuda.device(dev):
+            stream = _stream()
+        key = (dev.index, stream.value)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, dtype=torch.float64, device=dev)
+        return ws, stream
+
+    def release(self):
+        self._ws.clear()
+
+
+_bands_ws = _StreamWorkspace()     # hgp_pred_bands_f64
 
 
 def pred_bands_release():
     """Drop the cached workspaces of pred_bands (the memory returns to torch's allocator once queued calls have finished)."""
-    _bands_ws.clear()
+    _bands_ws.release()
 
 
 def pred_bands_ws_doubles(S, T):
@@ -495,13 +514,7 @@ def pred_bands(x_basis, theta, mean, Sigma, xq, sigma_idx=None, check=False):
         return mean_q, var_q, info
     if check and sigma_idx is not None and not bool(((sigma_idx >= 0) & (sigma_idx < Sigma.shape[0])).all()):
         raise IndexError("pred_bands: sigma_idx out of range")
-    need = pred_bands_ws_doubles(S, T)
-    with torch.cuda.device(dev):
-        stream = _stream()
-    key = (dev.index, stream.value)
-    ws = _bands_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _bands_ws[key] = torch.empty(need, dtype=torch.float64, device=dev)
+    ws, stream = _bands_ws.get(dev, pred_bands_ws_doubles(S, T))
     _ffi.check(_ffi.lib.hgp_pred_bands_f64(_ptr(x_basis), T, _ptr(theta), _ptr(mean), _ptr(Sigma), _ptr(sigma_idx), S, _ptr(xq), Q,
                                            _ptr(mean_q), _ptr(var_q), _ptr(info), _ptr(ws), stream), "pred_bands")
     if check:
@@ -509,13 +522,12 @@ def pred_bands(x_basis, theta, mean, Sigma, xq, sigma_idx=None, check=False):
     return mean_q, var_q, info
 
 
-# (device index, raw stream handle) -> workspace of hgp_sample_states_f64, kept like pred_bands's until sample_release()
-_sample_ws = {}
+_sample_ws = _StreamWorkspace()    # hgp_sample_states_f64
 
 
 def sample_release():
     """Drop the cached workspaces of sample_states (the memory returns to torch's allocator once queued calls have finished)."""
-    _sample_ws.clear()
+    _sample_ws.release()
 
 
 def sample_ws_doubles(S, T):
@@ -555,13 +567,7 @@ def sample_states(mean, cov, z, cov_idx=None, jitter_rel=0.0, check=True):
         return out, info
     if check and cov_idx is not None and not bool(((cov_idx >= 0) & (cov_idx < cov.shape[0])).all()):
         raise IndexError("sample_states: cov_idx out of range")
-    need = sample_ws_doubles(S, T)
-    with torch.cuda.device(dev):
-        stream = _stream()
-    key = (dev.index, stream.value)
-    ws = _sample_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _sample_ws[key] = torch.empty(need, dtype=torch.float64, device=dev)
+    ws, stream = _sample_ws.get(dev, sample_ws_doubles(S, T))
     _ffi.check(_ffi.lib.hgp_sample_states_f64(_ptr(mean), _ptr(cov), _ptr(cov_idx), T, S, _ptr(z), n, int(z.dim() == 2),
                                               float(jitter_rel), _ptr(out), _ptr(info), _ptr(ws), stream), "sample_states")
     if check:

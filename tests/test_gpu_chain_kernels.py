@@ -146,3 +146,24 @@ def test_chol_inverse_only_up_to_256_with_caller_buffers(T):
     for m in range(2):
         ref = np.linalg.inv(np.linalg.cholesky(0.5 * (A[m] + A[m].T) + 1e-8 * np.eye(T)))
         assert np.allclose(Z[m].cpu().numpy(), ref, rtol=1e-10, atol=1e-12 * np.abs(ref).max())
+
+
+@pytest.mark.parametrize("T", [17, 96, 144, 200])
+def test_chol_inverse_shift_and_jitter_in_one_pass(T):
+    """add_diag and jitter_rel in ONE call: the kernels add shift = add + jitter max(mean |diag A + add|, eps) to the diagonal
+    once.  T = 17: one wave, padded rows; 96: the burst loader; 144: Coop<12>; 200: Coop<16> with padding.  Tolerance: that of
+    the other chol_inverse tests of this file."""
+    from hdpgpc_amd import ops
+    rng = np.random.default_rng(1000 + T)
+    add, jitter = 0.5, 1e-3
+    Q = rng.normal(size=(3, T, T))
+    N = rng.normal(size=(3, T, T))
+    A = torch.as_tensor(Q @ Q.transpose(0, 2, 1) / T + np.eye(T) + 1e-3 * (N - N.transpose(0, 2, 1)), dtype=torch.float64)
+    Z, info = ops.chol_inverse(A.cuda(), jitter, add)
+    torch.cuda.synchronize()
+    assert info.tolist() == [0, 0, 0]
+    mean = (torch.diagonal(A, dim1=1, dim2=2) + add).abs().mean(dim=1).clamp_min(torch.finfo(torch.float64).eps)
+    shift = add + jitter * mean
+    ref = torch.linalg.inv(torch.linalg.cholesky(0.5 * (A + A.transpose(1, 2)) + shift[:, None, None] * torch.eye(T, dtype=torch.float64)))
+    for m in range(3):
+        assert np.allclose(Z[m].cpu().numpy(), ref[m].numpy(), rtol=1e-10, atol=1e-12 * float(ref[m].abs().max()))
