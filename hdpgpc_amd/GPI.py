@@ -12,7 +12,7 @@ import math
 import numpy as np
 import torch
 
-from . import ops
+from . import _ffi, ops
 
 torch_f64 = torch.float64
 
@@ -201,7 +201,7 @@ class IterativeGaussianProcess:
         if not eval_gradient:
             return val
         # gradient w.r.t. the log-parameters (GPI.py:1046-1051): K^{-1} = Z^T Z with Z = chol(K)^{-1}
-        if T <= 128:
+        if T <= _ffi.MAX_T_WAVE:
             Z, _ = ops.chol_inverse(K)
         else:
             _, _, Z = ops.potrf_batched(K, 0.0, 0.0, want_inv=True)

@@ -1,17 +1,28 @@
-"""ctypes binding of libhdpgpc_hip.so (include/hdpgpc_hip.h).
+"""ctypes binding of libhdpgpc_hip.so, read from include/hdpgpc_hip.h: the header is the one statement of the boundary.
 
-The product path has no CPU fallback: importing this module without the built library raises.
+Signatures, struct layouts and the integer #defines all come from parse_header(); an entry point is added by declaring it
+there and wrapping it in ops.py.  The product path has no CPU fallback: importing this module without the built library raises.
 """
 import ctypes
 import os
 
 import torch  # noqa: F401  (first: the library must bind to the HIP runtime PyTorch-ROCm already loaded, not a second copy)
 
+from ._cheader import parse_header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HGP_LIB selects another build of the same library (only the diagnostic `make stamps` build uses it)
 LIB_PATH = os.environ.get("HGP_LIB") or os.path.join(_HERE, "lib", "libhdpgpc_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hdpgpc_hip.h")     # where csrc/hgp_internal.hpp includes it from
 
 c_dp = ctypes.c_void_p  # device pointers travel as integers
+
+
+def check_abi(library, header):
+    """hgp_abi_version() of the loaded library against HGP_ABI_VERSION of the header it is bound from."""
+    if library != header:
+        raise ImportError(f"{LIB_PATH} reports ABI version {library}, include/hdpgpc_hip.h declares {header}: "
+                          "library built from another header: rebuild")
 
 
 def _load():
@@ -19,82 +30,27 @@ def _load():
         raise ImportError(
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). hdpgpc_amd has no CPU fallback.")
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError(f"{HEADER_PATH} is missing: the binding of {LIB_PATH} is read from it. hdpgpc_amd runs from its source tree.")
+    with open(HEADER_PATH) as f:
+        funcs, structs, defines = parse_header(f.read())
     lib = ctypes.CDLL(LIB_PATH)
-    i32, i64, f64, vp, sz = ctypes.c_int, ctypes.c_long, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
-    sigs = {
-        "hgp_abi_version": (i32, []),
-        "hgp_debug_mfma_f64": (i32, [vp, vp, vp, vp]),
-        "hgp_debug_exp_neg_f64": (i32, [vp, i32, vp, vp]),
-        "hgp_gram_rbf_f64": (i32, [vp, i32, vp, i32, f64, f64, f64, vp, vp]),
-        "hgp_potrf_batched_f64": (i32, [vp, i32, i32, f64, f64, vp, vp, vp, vp]),
-        "hgp_chol_inverse_batched_f64": (i32, [vp, i32, i32, f64, f64, vp, vp, vp]),
-        "hgp_chol_inverse_ws_f64": (i32, [vp, i32, i32, f64, f64, vp, vp, vp, vp]),
-        "hgp_rts_chain_f64": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
-        "hgp_gemm_add_batched_f64": (i32, [i32, i32, i32, i32, i32, f64, vp, i32, i64, vp, i32, i64, f64, vp, i32, i64, vp, i32, i64, i32, vp]),
-        "hgp_score_groups_f64": (i32, [vp, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, i32, vp, f64, vp, vp, vp, vp]),
-        "hgp_score_each_f64": (i32, [vp, i32, vp, i64, vp, i64, i32, vp, vp, vp, i32, f64, i32, vp, vp, vp, vp]),
-        "hgp_pairs_plan_device_bytes": (sz, [i32, i32, i32]),
-        "hgp_pairs_plan_create": (i32, [ctypes.POINTER(vp), i32, i32, i32, ctypes.POINTER(f64), vp, sz]),
-        "hgp_pairs_plan_destroy": (None, [vp]),
-        "hgp_pairs_plan_update": (i32, [vp, vp, vp, vp, vp, vp]),
-        "hgp_pairs_plan_scalars": (vp, [vp]),
-        "hgp_pairs_plan_set_accuracy": (i32, [vp, f64]),
-        "hgp_pairs_plan_set_score_output": (i32, [vp, i32]),
-        "hgp_loglik_pairs_f64": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
-        "hgp_gemm_batched_f64": (i32, [i32, i32, i32, i32, i32, f64, vp, i32, i64, vp, i32, i64, f64, vp, i32, i64, i32, vp]),
-        "hgp_matrix_lik_ws_bytes": (sz, [i32, i32]),
-        "hgp_lat_error_f64": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]),
-        "hgp_mniw_loglik_f64": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, sz, vp]),
-        "hgp_warp_cov_f64": (i32, [vp, i32, f64, f64, f64, i32, vp, vp]),
-        "hgp_chol_rank1_f64": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
-        "hgp_trsv_lower_quad_f64": (i32, [vp, i32, vp, i32, vp, vp]),
-        "hgp_hmm_messages_f64": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
-        "hgp_hmm_local_terms_f64": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "hgp_loglik_rows_f64": (i32, [vp, i32, i32, vp, vp, vp]),
-        "hgp_assign_f64": (i32, [vp, vp, i32, i32, vp, vp, vp]),
-        "hgp_warp_batch_f64": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp]),
-        "hgp_gemm_list_f64": (i32, [vp, i32, i32, vp]),
-        "hgp_gemm_list_mapped_f64": (i32, [vp, i32, vp, i32, vp]),
-        "hgp_chol_inverse_rhs_batched_f64": (i32, [vp, i32, i32, f64, f64, vp, vp, vp, i32, vp, vp, vp]),
-        "hgp_copy_list_f64": (i32, [vp, i32, i64, vp]),
-        "hgp_lds_chain_gather2_batched_f64": (i32, [vp, i32, i32, vp]),
-        "hgp_lds_chain_finish2_batched_f64": (i32, [vp, i32, i32, vp]),
-        "hgp_trsv_lower_solve_f64": (i32, [vp, i32, vp, i32, vp, vp, vp]),
-        "hgp_lml_grad_f64": (i32, [vp, vp, vp, i32, f64, f64, f64, vp, vp]),
-        "hgp_kl_sym_f64": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]),
-        "hgp_pred_bands_f64": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
-        "hgp_sample_states_f64": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, f64, vp, vp, vp, vp]),
-    }
-    for name, (res, args) in sigs.items():
+    for name, (res, args) in funcs.items():
         fn = getattr(lib, name)  # AttributeError here = header and library disagree
         fn.restype = res
         fn.argtypes = args
-    return lib, sorted(sigs)
+    check_abi(lib.hgp_abi_version(), defines["HGP_ABI_VERSION"])
+    return lib, sorted(funcs), structs, defines
 
 
-lib, EXPORTS = _load()
+def _struct(name, c_name):
+    return type(name, (ctypes.Structure,), {"_fields_": _structs[c_name], "__doc__": f"{c_name} of include/hdpgpc_hip.h."})
 
 
-class GemmItem(ctypes.Structure):
-    """hgp_gemm_item of include/hdpgpc_hip.h."""
-    _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("D", ctypes.c_void_p), ("C", ctypes.c_void_p), ("C2", ctypes.c_void_p),
-                ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("lda", ctypes.c_int), ("ldb", ctypes.c_int),
-                ("ldc", ctypes.c_int), ("ldd", ctypes.c_int), ("tA", ctypes.c_int), ("tB", ctypes.c_int),
-                ("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("add_eye", ctypes.c_double)]
-
-
-class ChainGatherDesc(ctypes.Structure):
-    """hgp_chain_gather_desc of include/hdpgpc_hip.h."""
-    _fields_ = [("st", ctypes.c_void_p * 8), ("pos", ctypes.c_void_p), ("out", ctypes.c_void_p), ("Y", ctypes.c_void_p),
-                ("y_out", ctypes.c_void_p), ("W", ctypes.c_void_p), ("Rp", ctypes.c_void_p), ("y_row0", ctypes.c_long),
-                ("T", ctypes.c_int)]
-
-
-class ChainFinishDesc(ctypes.Structure):
-    """hgp_chain_finish_desc of include/hdpgpc_hip.h."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("f_post", "c_post", "f_sm_prev", "P_sm_prev", "y", "part", "Snew", "info1", "info2", "W",
-                                               "n0", "Nf", "bad_count", "stA", "stG", "stC", "stS", "stF", "stFsm", "stP", "stPsm", "pos",
-                                               "sync")] + [("T", ctypes.c_int), ("annealing", ctypes.c_int)]
+lib, EXPORTS, _structs, _defines = _load()
+ABI_VERSION, MAX_T_WAVE, MAX_T_COOP = (_defines[k] for k in ("HGP_ABI_VERSION", "HGP_MAX_T_WAVE", "HGP_MAX_T_COOP"))
+GemmItem, ChainGatherDesc = _struct("GemmItem", "hgp_gemm_item"), _struct("ChainGatherDesc", "hgp_chain_gather_desc")
+ChainFinishDesc, CopyItem = _struct("ChainFinishDesc", "hgp_chain_finish_desc"), _struct("CopyItem", "hgp_copy_item")
 
 
 class HgpError(RuntimeError):

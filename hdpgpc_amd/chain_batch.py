@@ -27,7 +27,7 @@ online pool (online_chain.py) runs too; here is the offline orchestration around
 import numpy as np
 import torch
 
-from . import ops
+from . import _ffi, ops
 from .member_step import Chain, finish_desc, gather_desc, member_step, shared_buffers, upload_descs
 
 f64 = torch.float64
@@ -48,7 +48,7 @@ def _graphable(job):
     the members on the basis grid, T <= 256."""
     gp = job.gp
     a = job.active
-    if len(a) < 4 or gp.x_basis.shape[0] > 256 or gp.estimation_limit != np.inf:
+    if len(a) < 4 or gp.x_basis.shape[0] > _ffi.MAX_T_COOP or gp.estimation_limit != np.inf:
         return False
     if not bool(torch.any(gp.Gamma[-1] != 0)) or not bool(torch.all(job.resp[a] == 1.0)):
         return False
@@ -81,7 +81,7 @@ def run(jobs):
         else:
             j.out = j.gp._full_pass_eager(j.x, j.y, j.resp, j.active)
     for T, g in by_T.items():
-        for group in ([g] if T <= 128 and len(g) >= 2 else [[j] for j in g]):
+        for group in ([g] if T <= _ffi.MAX_T_WAVE and len(g) >= 2 else [[j] for j in g]):
             _run_group(group)
     return [j.out for j in jobs]
 

@@ -99,7 +99,7 @@ class Chain:
         shared, c: this chain is chain c of shared_buffers (one batched inversion for all of them).  alloc(*shape) (optional):
         where the step's own buffers come from (a pool hands out slices of its arena); zeroed.  Needs self.ws."""
         T = self.T
-        riding = T <= 128
+        riding = T <= _ffi.MAX_T_WAVE
         tt = T * T
         dev = self.ws.device
         new = alloc or (lambda *shape: torch.zeros(shape, dtype=f64, device=dev))
@@ -206,7 +206,7 @@ def member_step(levels, shared, gdev, fdev, lo, hi, T, gather_first=True, no_smo
     gather / finish descriptors; gather_first=False: a gather() of this member was already issued; no_smoother: the chains of a
     step without the pair smoother, whose previous smoothed mean stands where f_sm_prev would."""
     sh = lambda k: shared[k][lo:hi].flatten(0, 1) if k in shared else None          # noqa: E731
-    riding = T <= 128
+    riding = T <= _ffi.MAX_T_WAVE
     if gather_first:
         gather(gdev, lo, hi, T)
     for l in range(4):

@@ -2,6 +2,7 @@
 takes fp64 CUDA (ROCm) tensors, enqueues HIP kernels on the current stream and returns tensors."""
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
@@ -16,7 +17,6 @@ def _ptr(t):
 
 
 def env_flag(name):
-    import os
     return os.environ.get(name, "0") not in ("", "0")
 
 
@@ -140,7 +140,8 @@ def chol_inverse(A, jitter_rel=0.0, add_diag=0.0, out=None, info=None, work=None
 
 
 def copy_list(items_dev, n_items, max_n):
-    """n_items copies dst[0..n) = src[0..n) described by the device-resident int64 table items_dev [n_items, 3] = (src, dst, n)."""
+    """n_items copies dst[0..n) = src[0..n) described by the device-resident int64 table items_dev [n_items, 3] = (src, dst, n),
+    the layout of hgp_copy_item (_ffi.CopyItem)."""
     _ffi.check(_ffi.lib.hgp_copy_list_f64(_ptr(items_dev), int(n_items), int(max_n), _stream()), "copy_list")
 
 
@@ -165,30 +166,37 @@ def build_items(mat_of_group, add_of_group, group_sizes):
             np.asarray(item_cnt, np.int32))
 
 
+def _up(a, dtype, dev):
+    return None if a is None else to_dev(a, dtype, dev)
+
+
+def _score_operands(Y, mean, Sigma, strides):
+    """(Y, mean, Sigma, mean stride, Sigma stride) of the a4 / a6 calls: dense stacks mean [S,T], Sigma [S,T,T], checked here, or
+    strides = (mean_stride, sigma_stride) in doubles: states that sit inside larger per-cluster records, taken as they are."""
+    Y = _dev64(Y, "Y")
+    T = Y.shape[1]
+    if strides is not None:
+        return Y, mean, Sigma, int(strides[0]), int(strides[1])
+    Sigma = _dev64(Sigma, "Sigma")
+    if Sigma.dim() == 2:
+        Sigma = Sigma.unsqueeze(0)
+    if mean is not None:
+        mean = _dev64(mean.reshape(-1, T), "mean")
+    return Y, mean, Sigma, T, T * T
+
+
 def score_groups(Y, mean, Sigma, item_mat, item_add, item_off, item_cnt, seg_ids=None, jitter_rel=1e-8,
                  want_logdet=False, want_info=True, item_mean=None, strides=None):
     """a4+a6: quad[n] = (Y[n]-mean[s])^T cov_s^{-1} (Y[n]-mean[s]) for the segments of each work item.
 
     Y [N,T]; mean [S,T] or None; Sigma [S,T,T]; item_* host or device int/float arrays; seg_ids [sum cnt] or None.
     """
-    Y = _dev64(Y, "Y")
+    Y, mean, Sigma, mstride, sstride = _score_operands(Y, mean, Sigma, strides)
     dev = Y.device
     N, T = Y.shape
-    if strides is None:       # strides = (mean_stride, sigma_stride) in doubles: states that sit inside larger per-cluster records
-        Sigma = _dev64(Sigma, "Sigma")
-        if Sigma.dim() == 2:
-            Sigma = Sigma.unsqueeze(0)
-        if mean is not None:
-            mean = _dev64(mean.reshape(-1, T), "mean")
-    mstride, sstride = (T, T * T) if strides is None else (int(strides[0]), int(strides[1]))
-
-    def up(a, dt):
-        return to_dev(a, dt, dev)
-
-    im, ia = up(item_mat, torch.int32), (None if item_add is None else up(item_add, torch.float64))
-    io, ic = up(item_off, torch.int32), up(item_cnt, torch.int32)
-    sid = None if seg_ids is None else up(seg_ids, torch.int32)
-    imean = None if item_mean is None else up(item_mean, torch.int32)
+    im, ia = _up(item_mat, torch.int32, dev), _up(item_add, torch.float64, dev)
+    io, ic = _up(item_off, torch.int32, dev), _up(item_cnt, torch.int32, dev)
+    sid, imean = _up(seg_ids, torch.int32, dev), _up(item_mean, torch.int32, dev)
     quad = torch.zeros(N, dtype=torch.float64, device=dev)
     logdet = torch.zeros(N, dtype=torch.float64, device=dev) if want_logdet else None
     info = torch.zeros(N, dtype=torch.int32, device=dev) if want_info else None
@@ -202,22 +210,11 @@ def score_each(Y, mean, Sigma, seg_mat, seg_mean=None, seg_add=None, jitter_rel=
                symmetric=False, strides=None):
     """a6 for member segments: segment i against its own state.  Y [n,T]; mean [S,T]; Sigma [S,T,T]; seg_* [n].
     symmetric=True promises Sigma == Sigma^T exactly (upper triangle read only)."""
-    Y = _dev64(Y, "Y")
+    Y, mean, Sigma, mstride, sstride = _score_operands(Y, mean, Sigma, strides)
     dev = Y.device
     n, T = Y.shape
-    if strides is None:
-        Sigma = _dev64(Sigma, "Sigma")
-        if mean is not None:
-            mean = _dev64(mean.reshape(-1, T), "mean")
-    mstride, sstride = (T, T * T) if strides is None else (int(strides[0]), int(strides[1]))
-
-    def up(a, dt):
-        if a is None:
-            return None
-        return to_dev(a, dt, dev)
-
-    sm, sme, sa = up(seg_mat, torch.int32), up(seg_mean, torch.int32), up(seg_add, torch.float64)
-    if T > 128:   # cooperative kernels: one work item (one workgroup) per segment
+    sm, sme, sa = _up(seg_mat, torch.int32, dev), _up(seg_mean, torch.int32, dev), _up(seg_add, torch.float64, dev)
+    if T > _ffi.MAX_T_WAVE:   # cooperative kernels: one work item (one workgroup) per segment
         ar = torch.arange(n, dtype=torch.int32, device=dev)
         return score_groups(Y, mean, Sigma, sm, sa, ar, torch.ones(n, dtype=torch.int32, device=dev), jitter_rel=jitter_rel,
                             want_logdet=want_logdet, want_info=want_info, item_mean=sme, strides=strides)
@@ -410,7 +407,7 @@ def _kl_precisions(cov, what):
     """cov^-1 = Z^T Z with Z = chol(0.5 (cov + cov^T))^-1, no jitter (the reference's KL_divergence inverts the covariance
     as it is, GPI.py:1080-1081); a covariance that is not positive-definite raises, naming the state."""
     T = cov.shape[1]
-    work = torch.empty_like(cov) if T > 128 else None
+    work = torch.empty_like(cov) if T > _ffi.MAX_T_WAVE else None
     Z, info = chol_inverse(cov, 0.0, 0.0, work=work)
     raise_on_info(info, f"kl_sym: covariance of {what}")
     return gemm_batched(Z, Z, transA=True)
@@ -465,6 +462,17 @@ class _StreamWorkspace:
         self._ws.clear()
 
 
+def _stack_index(who, stack, what, idx, idx_name, S, check):
+    """State s of S reads matrix idx[s] of the stack [*,T,T] (int32 device tensor [S]; None: s).  check: the values too (host sync)."""
+    if idx is None:
+        if stack.shape[0] != S:
+            raise ValueError(f"{who}: without {idx_name} the stack holds one {what} per state")
+    elif not (torch.is_tensor(idx) and idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == S):
+        raise TypeError(f"{who}: {idx_name} must be a contiguous int32 tensor [S] on the GPU")
+    elif check and not bool(((idx >= 0) & (idx < stack.shape[0])).all()):
+        raise IndexError(f"{who}: {idx_name} out of range")
+
+
 _bands_ws = _StreamWorkspace()     # hgp_pred_bands_f64
 
 
@@ -475,7 +483,7 @@ def pred_bands_release():
 
 def pred_bands_ws_doubles(S, T):
     """HGP_BANDS_WS_DOUBLES of include/hdpgpc_hip.h."""
-    return (3 if T > 128 else 2) * S * T * T + 5 * S
+    return (3 if T > _ffi.MAX_T_WAVE else 2) * S * T * T + 5 * S
 
 
 def pred_bands(x_basis, theta, mean, Sigma, xq, sigma_idx=None, check=False):
@@ -501,19 +509,12 @@ def pred_bands(x_basis, theta, mean, Sigma, xq, sigma_idx=None, check=False):
     theta = _dev64(theta, "theta")
     if tuple(theta.shape) != (S, 3):
         raise ValueError("pred_bands: theta must be [S, 3]")
-    if sigma_idx is None:
-        if Sigma.shape[0] != S:
-            raise ValueError("pred_bands: without sigma_idx the stack holds one Sigma per state")
-    elif not (torch.is_tensor(sigma_idx) and sigma_idx.is_cuda and sigma_idx.dtype == torch.int32 and sigma_idx.is_contiguous()
-              and sigma_idx.numel() == S):
-        raise TypeError("pred_bands: sigma_idx must be a contiguous int32 tensor [S] on the GPU")
+    _stack_index("pred_bands", Sigma, "Sigma", sigma_idx, "sigma_idx", S, check and Q > 0)    # an empty call launches nothing
     mean_q = torch.empty((S, Q), dtype=torch.float64, device=dev)
     var_q = torch.empty((S, Q), dtype=torch.float64, device=dev)
     info = torch.zeros(S, dtype=torch.int32, device=dev)
     if S == 0 or Q == 0:
         return mean_q, var_q, info
-    if check and sigma_idx is not None and not bool(((sigma_idx >= 0) & (sigma_idx < Sigma.shape[0])).all()):
-        raise IndexError("pred_bands: sigma_idx out of range")
     ws, stream = _bands_ws.get(dev, pred_bands_ws_doubles(S, T))
     _ffi.check(_ffi.lib.hgp_pred_bands_f64(_ptr(x_basis), T, _ptr(theta), _ptr(mean), _ptr(Sigma), _ptr(sigma_idx), S, _ptr(xq), Q,
                                            _ptr(mean_q), _ptr(var_q), _ptr(info), _ptr(ws), stream), "pred_bands")
@@ -555,18 +556,11 @@ def sample_states(mean, cov, z, cov_idx=None, jitter_rel=0.0, check=True):
     if z.dim() not in (2, 3) or z.shape[-1] != T or (z.dim() == 3 and z.shape[0] != S):
         raise ValueError("sample_states: z must be [n, T] (shared) or [S, n, T]")
     n = z.shape[-2]
-    if cov_idx is None:
-        if cov.shape[0] != S:
-            raise ValueError("sample_states: without cov_idx the stack holds one covariance per state")
-    elif not (torch.is_tensor(cov_idx) and cov_idx.is_cuda and cov_idx.dtype == torch.int32 and cov_idx.is_contiguous()
-              and cov_idx.numel() == S):
-        raise TypeError("sample_states: cov_idx must be a contiguous int32 tensor [S] on the GPU")
+    _stack_index("sample_states", cov, "covariance", cov_idx, "cov_idx", S, check and n > 0)  # an empty call launches nothing
     out = torch.empty((S, n, T), dtype=torch.float64, device=dev)
     info = torch.zeros(S, dtype=torch.int32, device=dev)
     if S == 0 or n == 0:
         return out, info
-    if check and cov_idx is not None and not bool(((cov_idx >= 0) & (cov_idx < cov.shape[0])).all()):
-        raise IndexError("sample_states: cov_idx out of range")
     ws, stream = _sample_ws.get(dev, sample_ws_doubles(S, T))
     _ffi.check(_ffi.lib.hgp_sample_states_f64(_ptr(mean), _ptr(cov), _ptr(cov_idx), T, S, _ptr(z), n, int(z.dim() == 2),
                                               float(jitter_rel), _ptr(out), _ptr(info), _ptr(ws), stream), "sample_states")
@@ -581,6 +575,12 @@ def rts_chain(J, P, AM, M, Cv):
     _ffi.check(_ffi.lib.hgp_rts_chain_f64(_ptr(J), _ptr(P), _ptr(AM), _ptr(M), _ptr(Cv), n, T, _stream()), "rts_chain")
 
 
+def _matrix_lik_ws(T, b, dev):
+    """(workspace, its bytes) of the a8 / a9 calls: none for T <= HGP_MAX_T_WAVE, where each term is one fused kernel."""
+    nws = _ffi.lib.hgp_matrix_lik_ws_bytes(T, b) if T > _ffi.MAX_T_WAVE else 0
+    return (torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None), nws
+
+
 def lat_error(f_cur, f_prev, A, Gamma, covprev):
     """a8 batched: returns (-0.5 (mahal + trace) [b], info [b]); the caller adds -0.5 T log 2pi."""
     f_cur, f_prev = _dev64(f_cur, "f_cur"), _dev64(f_prev, "f_prev")
@@ -588,8 +588,7 @@ def lat_error(f_cur, f_prev, A, Gamma, covprev):
     b, T = f_cur.shape
     out = torch.empty(b, dtype=torch.float64, device=A.device)
     info = torch.zeros(b, dtype=torch.int32, device=A.device)
-    nws = _ffi.lib.hgp_matrix_lik_ws_bytes(T, b) if T > 128 else 0     # T <= 128: one fused kernel, no workspace
-    ws = torch.empty(nws, dtype=torch.uint8, device=A.device) if nws else None
+    ws, nws = _matrix_lik_ws(T, b, A.device)
     _ffi.check(_ffi.lib.hgp_lat_error_f64(_ptr(f_cur), _ptr(f_prev), _ptr(A), _ptr(Gamma), _ptr(covprev), T, b, _ptr(out),
                                           _ptr(info), _ptr(ws), nws, _stream()), "lat_error")
     return out, info
@@ -609,8 +608,7 @@ def mniw_loglik(M, Sigma, m_mean, m_r_cov, scale, scale_is_diagonal=None):
         m_r_cov = _dev64(m_r_cov, "m_r_cov")
     out = torch.empty(b, dtype=torch.float64, device=M.device)
     info = torch.zeros(b, dtype=torch.int32, device=M.device)
-    nws = _ffi.lib.hgp_matrix_lik_ws_bytes(T, b) if T > 128 else 0     # T <= 128: one fused kernel, no workspace
-    ws = torch.empty(nws, dtype=torch.uint8, device=M.device) if nws else None
+    ws, nws = _matrix_lik_ws(T, b, M.device)
     _ffi.check(_ffi.lib.hgp_mniw_loglik_f64(_ptr(M), _ptr(Sigma), _ptr(m_mean), _ptr(m_r_cov), _ptr(scale), int(scale_is_diagonal), stride, T, b,
                                             _ptr(out), _ptr(info), _ptr(ws), nws, _stream()), "mniw_loglik")
     return out, info
@@ -696,7 +694,6 @@ class GemmList:
         return out
 
     def finalize(self):
-        import numpy as np
         arr = (_ffi.GemmItem * len(self._items))(*self._items)
         host = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy())
         self._dev = host.to(self.device)
