@@ -32,7 +32,7 @@ from . import hdp_global, ops
 from .GPI import RBFWhiteKernel
 from .GPI_model import GPI_model, _copy_list
 from .offline_loop import OfflineLoop
-from .online_loop import OnlineLoop
+from .online_loop import OnlineLoop, _log_trans, _np
 
 f64 = torch.float64
 _HDP_HYP = {"less": (0.01, 0.01, 0.01, 0.0), "balanced": (1.0, 1.0, 0.1, 0.0), "more": (10.0, 10.0, 1.0, 0.0)}
@@ -384,8 +384,7 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         for _ in range(2):
             self.transTheta, self.startTheta = self._calcThetaFull(transStateCount, startStateCount, M + 1)
             self.rho, self.omega = self.find_optimum_rhoOmega()
-        tt = _np(self.transTheta)
-        self.trans_A = torch.as_tensor(_digamma(tt[:M, :M]) - np.log(np.sum(np.exp(_digamma(tt[:M, :M + 1])), axis=1) + 1e-5)[:, None])
+        self.trans_A = torch.as_tensor(_log_trans(self.transTheta, M, 1e-5))
         self.resp_assigned.append(torch.where(resp == 1.0)[1])
         self.q_last, self.q_lat_last, self.snr_last = q, q_lat, snr
         self.startStateCount_last, self.transStateCount_last = startStateCount, transStateCount
@@ -465,6 +464,3 @@ def _to_device(o, dev, _seen=None):
         return tuple(_to_device(v, dev) for v in o)
     return o
 
-
-def _np(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)

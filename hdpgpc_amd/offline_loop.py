@@ -1,31 +1,44 @@
-"""The offline variational loop of GPI_HDP (hdpgpc/hdpgpc/GPI_HDP.py:805-943 ``include_batch`` and what it calls:
-``refill`` :1076, ``refill_resp`` :1141, ``new_group`` :1112, ``remove_last_group`` :1133,
-``variational_local_terms_batch`` :1170, ``estimate_q_first`` :1243, ``estimate_q_all`` :2844, ``compute_q_elbo`` :1796,
-``full_LDS_elbo`` :1838, ``elbo_Linears`` :1025, ``redefine_default`` :1866, ``compute_snr_ini`` :715) - host
-orchestration over the HIP kernels: every number that depends on the data comes from
+"""The offline variational loop of GPI_HDP (hdpgpc/hdpgpc/GPI_HDP.py:805-943 ``include_batch`` and what it calls: ``refill`` :1076,
+``refill_resp`` :1141, ``new_group`` :1112, ``remove_last_group`` :1133, ``variational_local_terms_batch`` :1170, ``estimate_q_first`` :1243,
+``estimate_q_all`` :2844, ``compute_q_elbo`` :1796, ``full_LDS_elbo`` :1838, ``elbo_Linears`` :1025, ``redefine_default`` :1866,
+``compute_snr_ini`` :715) - host orchestration over the HIP kernels: every number that depends on the data comes from
 
 * ``GPI_model.full_pass_weighted``  (member chain kernels + a6 / a8 scores),
 * ``GPI_model.compute_sq_err_all``  (a6: one shared-covariance launch for the N scores of a one-member proposal),
 * ``GPI_model.return_LDS_param_likelihood``  (a9),
 * ``ops.loglik_rows`` / ``ops.hmm_messages`` / ``ops.assign``  (switching-variable messages and the hard assignment),
 
-and the score matrices ``q``, ``q_lat``, ``snr`` ([N, M, n_outputs]) stay on the device between them.  What runs on the host
-is the decision logic (which clusters changed, accept / reject a proposal, bookkeeping of the one-hot responsibilities - N x M
-and N x M x M tables of zeros and ones) and the O(M) HDP terms (hdp_global.py).
+and the score matrices ``q``, ``q_lat``, ``snr`` ([N, M, n_outputs]) stay on the device between them.  What runs on the host is the decision
+logic (which clusters changed, accept / reject a proposal, bookkeeping of the one-hot responsibilities - N x M and N x M x M tables of zeros
+and ones) and the O(M) HDP terms (hdp_global.py).
 
-The reference's loop is written as three long methods that repeat the same blocks (assign -> rebuild changed clusters -> ELBO
--> iterate); here those blocks are helpers (``_assign``, ``_rebuild``, ``_elbo_of``, ``_pick_representatives``).  Quirks of
-the reference that change results are kept and marked ``# quirk``.  With ``warp=False`` the reference's 4-D ``y_trains_w`` is a
-broadcast view of ``y_trains`` and its ``liks`` are zeros (GPI_HDP.py:3441-3446), so neither is materialised; ``warp=True`` warps every
-segment onto every cluster's representative (``warp_batch_by_resp_amtgp_cached``, GPI_HDP.py:3412-3525: hgp_warp_batch_f64 + the a11
-prior score) and carries the 4-D tensor through the same helpers.
+The reference's loop is written as three long methods that repeat the same blocks (assign -> rebuild changed clusters -> ELBO -> iterate);
+here each block is stated once: ``_assign`` + ``_by_size`` (hard assignment, clusters largest first); the rebuild step - ``Column`` records
+(``_plan_columns``), ``_pass_specs`` + ``_passes`` to run the changed ones side by side, ``_take_pass`` to write one rebuilt column, while what
+an UNCHANGED column copies stays at its site -; ``_elbo_of``, ``_converge``, ``_drop_last_group`` (the emergency exits) and
+``_pick_representatives``; ``estimate_q_first`` is the sequence of its phases.  Quirks of the reference that change results are kept and marked
+``# quirk``.  With ``warp=False`` the reference's 4-D ``y_trains_w`` is a broadcast view of ``y_trains`` and its ``liks`` are zeros (GPI_HDP.py:
+3441-3446), so neither is materialised; ``warp=True`` warps every segment onto every cluster's representative (GPI_HDP.py:3412-3525,
+``warp_batch_by_resp_amtgp_cached``: hgp_warp_batch_f64 + the a11 prior score) and carries the 4-D tensor through the same helpers.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
 from . import chain_batch, hdp_global, ops
+from .online_loop import _by_size, _log_trans, _np, _tables
 
 f64 = torch.float64
+
+# column m of a proposal's tables on lead ld continues column r of the current ones with model gp; rebuild: gp (fresh) takes a full pass
+Column = namedtuple("Column", "ld m r gp rebuild")
+# what estimate_q_first starts from (batch, current tables, warps onto the current representatives), and the same tables with one more
+# (empty) column: q_def ... from the one-member scores, q__def ... from the scores themselves
+Current = namedtuple("Current", "x y resp respPair q_ q_lat_ snr_ startPi Yw liks reparam")
+Grown = namedtuple("Grown", "M f_ind_old resp_ q_def q_lat_def snr_aux_def q__def q_lat__def snr__def")
+Proposal = namedtuple("Proposal", "f_new m_chosen f_ind_old_temp q_simple_ q q_lat snr_aux q__ q_lat__ snr__ resp_temp respPair_temp "
+                                  "reorder gpmodels_temp cols Yp lp")          # one prepared birth
 
 
 def _isclose(a, b, rtol=1e-5, atol=1e-8):
@@ -239,12 +252,7 @@ class OfflineLoop:
         ar = torch.arange(K * K, device=flat.device).expand_as(flat)
         first = torch.min(torch.where(flat == mx, ar, torch.full_like(ar, K * K)), dim=1)[0]
         first = torch.where(first == K * K, torch.zeros_like(first), first)   # NaN rows: arg-max of the reference undefined
-        lab_h, first_h = labels.cpu(), first.cpu()
-        resp = torch.zeros((N, K), dtype=f64)
-        resp[torch.arange(N), lab_h] = 1.0
-        respPair = torch.zeros((N, K * K), dtype=f64)                         # the reference's table is float32: 0 / 1 either way
-        respPair[torch.arange(N), first_h] = 1.0
-        return resp, respPair.reshape(N, K, K)
+        return _tables(labels.cpu(), first.cpu(), K)
 
     def _fresh_copy(self, gp):
         """gpmodel_deepcopy + reinit of a fitted model (GPI_HDP.py:1289-1292 and its repeats): same kernel and priors, empty
@@ -292,12 +300,12 @@ class OfflineLoop:
         q_lat = torch.zeros((N, M, D), dtype=f64, device=dev)
         snr_aux = snr_.clone()
         resp_temp, respPair_temp = self._assign(self.weight_mean(q_, snr_aux), startPi)
-        reorder = torch.argsort(self._counts(resp_temp), descending=True)
-        resp_temp = resp_temp[:, reorder].clone()                              # quirk: the pair table keeps the old order
+        reorder, resp_temp = _by_size(resp_temp)
+        resp_temp = resp_temp.clone()                                          # quirk: the pair table keeps the old order
         f_ind_old = self.f_ind_old if f_ind_old is None else f_ind_old
         Yw, liks = self.warp_batch_by_resp_amtgp_cached(x_trains, y_trains, resp_temp, f_ind_old)   # columns in f_ind_old's order
         gpmodels_temp = [[] for _ in range(D)]
-        plan = []                                     # (ld, m, r, model, kind): kind 0 unchanged, 1 changed, 2 new with members, 3 new empty
+        plan = []                                     # (column, kind): kind 0 unchanged, 1 changed, 2 new with members, 3 new empty
         for ld in range(D):
             for m in range(M):
                 r = int(reorder[m])
@@ -316,20 +324,13 @@ class OfflineLoop:
                 else:
                     gp = self.create_gp_default(i=r)
                     kind = 2 if len(members) > 0 else 3
-                plan.append((ld, m, r, gp, kind))
+                plan.append((Column(ld, m, r, gp, kind in (1, 2)), kind))
                 gpmodels_temp[ld].append(gp)
-        outs = iter(self._passes(x_trains, y_trains, [(gp, self._ycol(Yw, y_trains, ld, r), resp_temp[:, m])
-                                                      for ld, m, r, gp, kind in plan if kind in (1, 2)]))
-        for ld, m, r, gp, kind in plan:
-            if kind in (1, 2):
-                out = next(outs)
-                self._note_full_pass(resp_temp[:, m], out)
-                if out is None:                       # no members: the previous columns (quirk: of the table being filled, for q_lat of a new model)
-                    out = (q_[:, r, ld], (q_lat_ if kind == 1 else q_lat)[:, r, ld])
-                q[:, m, ld], q_lat[:, m, ld] = out
-                if liks is not None:
-                    q[:, m, ld] += liks[:, r, ld]
-                snr_aux[:, m, ld] = self.compute_snr(self._ylead(Yw, y_trains, ld, r), gp)
+        outs = iter(self._passes(x_trains, y_trains, self._pass_specs([c for c, _ in plan], Yw, y_trains, resp_temp)))
+        for c, kind in plan:
+            ld, m, r = c.ld, c.m, c.r
+            if c.rebuild:            # no members: the previous columns (quirk: of the table being filled, for q_lat of a new model)
+                self._take_pass(c, outs, resp_temp, q, q_lat, snr_aux, y_trains, Yw, liks, (q_, q_lat_ if kind == 1 else q_lat))
             elif kind == 0:
                 q[:, m, ld] = q_[:, r, ld]
                 q_lat[:, m, ld] = q_lat_[:, r, ld]
@@ -350,17 +351,21 @@ class OfflineLoop:
             return resp, respPair, q_, q_lat_, snr_, gpmodels
         self._log(f">>> Possible emergency reallocation. Prev ----: Q_em: {q_def}, Elbo: {elbo_def}")
         if (q_def + elbo_def < q_bas_post + elbo_post) and (q_bas + elbo_bas < q_bas_post + elbo_post):
-            self._log("Emergency reallocation and removing last group.")
-            for ld in range(D):
-                gpmodels_temp[ld] = gpmodels_temp[ld][:-1]
-            self.gpmodels = gpmodels_temp
-            self.snr_norm = self.normalize_snr(snr_aux)
-            resp_temp, respPair_temp, q, q_lat, snr_aux = self.remove_last_group(resp_temp, respPair_temp, q, q_lat, snr_aux)
-            reorder = torch.argsort(self._counts(resp_temp), descending=True)
-            self.f_ind_old = self.f_ind_old[reorder]
+            resp_temp, respPair_temp, q, q_lat, snr_aux = self._drop_last_group(gpmodels_temp, resp_temp, respPair_temp, q, q_lat, snr_aux)
+            self.f_ind_old = self.f_ind_old[torch.argsort(self._counts(resp_temp), descending=True)]     # (the order after the removal)
             return resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp
         self._log("Bad estimation")
         return resp, respPair, q_, q_lat_, snr_, gpmodels
+
+    def _drop_last_group(self, gpmodels_temp, resp_temp, respPair_temp, q, q_lat, snr_aux, snr_seen=None):
+        """What the three emergency exits share: the proposal without its (empty) last cluster becomes the model; returns its tables without
+        their last column.  quirk: ``snr_norm`` comes from snr_aux WITH the dropped column at two exits, from ``snr_seen`` (without) at a birth's."""
+        self._log("Emergency reallocation and removing last group.")
+        for ld in range(self.n_outputs):
+            gpmodels_temp[ld] = gpmodels_temp[ld][:-1]
+        self.gpmodels = gpmodels_temp
+        self.snr_norm = self.normalize_snr(snr_aux if snr_seen is None else snr_seen)
+        return self.remove_last_group(resp_temp, respPair_temp, q, q_lat, snr_aux)
 
     # ------------------------------------------------------------------ warping inside the loop (GPI_HDP.py:3412-3525)
     def warp_batch_by_resp_amtgp_cached(self, x, y, resp_temp, f_ind_old=None, train_iter=50, batch_size=128):
@@ -428,6 +433,40 @@ class OfflineLoop:
         chain_batch.run(jobs)
         return [j.out if len(j.active) else None for j in jobs]
 
+    def _plan_columns(self, resp, resp_temp, reorder, m_chosen):
+        """Columns and model table of the proposal that assigns resp_temp: a cluster whose member set changed restarts from a fresh copy of its
+        model, the born one (past resp's last column) from the default model - with share_gp from the divided cluster m_chosen's."""
+        cols, gpmodels_temp = [], [[] for _ in range(self.n_outputs)]
+        for ld in range(self.n_outputs):
+            for m in range(resp_temp.shape[1]):
+                r = int(reorder[m])
+                born = r == resp.shape[1]
+                rebuild = born or not torch.equal(resp[:, r].long(), resp_temp[:, m].long())
+                if born:
+                    gp = self._fresh_copy(self.gpmodels[ld][m_chosen]) if self.share_gp else self.create_gp_default()
+                else:
+                    gp = self._fresh_copy(self.gpmodels[ld][r]) if rebuild else self.gpmodels[ld][r]
+                cols.append(Column(ld, m, r, gp, rebuild))
+                gpmodels_temp[ld].append(gp)
+        return cols, gpmodels_temp
+
+    def _pass_specs(self, cols, Yw, y, resp_temp):
+        """``_passes`` specs of the columns to rebuild, in plan order: the members of new column m, as warped for the column r it continues."""
+        return [(c.gp, self._ycol(Yw, y, c.ld, c.r), resp_temp[:, c.m]) for c in cols if c.rebuild]
+
+    def _take_pass(self, c, outs, resp_temp, q, q_lat, snr, y, Yw, liks, fallback):
+        """The next result of ``_passes`` is column ``c``'s: written into column m of q, q_lat (+ the warp prior) and snr.  A pass
+        without members keeps the previous columns instead: column r of the two tables ``fallback``."""
+        ld, m, r = c.ld, c.m, c.r
+        out = next(outs)
+        self._note_full_pass(resp_temp[:, m], out)
+        if out is None:
+            out = (fallback[0][:, r, ld], fallback[1][:, r, ld])
+        q[:, m, ld], q_lat[:, m, ld] = out
+        if liks is not None:
+            q[:, m, ld] += liks[:, r, ld]
+        snr[:, m, ld] = self.compute_snr(self._ylead(Yw, y, ld, r), c.gp)
+
     def _note_full_pass(self, resp_col, out):
         """Hook (tests): called once per full pass, in the order the reference's loop makes them."""
 
@@ -453,106 +492,117 @@ class OfflineLoop:
 
     # ------------------------------------------------------------------ estimate_q_first
     def estimate_q_first(self, M, x_trains, y_trains, resp, respPair, q_, q_lat_, snr_, startPi, reallocate_=False, reparam=False):
-        """GPI_HDP.py:1243-1794: first try to move segments between the existing clusters; failing that, propose births
-        seeded by badly explained segments and keep the first one that improves the bound.
-        Returns (resp, respPair, q, q_lat, snr, reallocate)."""
-        x, y = x_trains, y_trains
-        N, D, dev = y.shape[0], self.n_outputs, self.device
-        empty_estimation = False
-        Yw, liks = self.warp_batch_by_resp_amtgp_cached(x, y, resp, self.f_ind_old)
+        """GPI_HDP.py:1243-1794: first try to move segments between the existing clusters; failing that, propose births seeded by badly
+        explained segments and keep the first one that improves the bound.  Returns (resp, respPair, q, q_lat, snr, reallocate)."""
+        Yw, liks = self.warp_batch_by_resp_amtgp_cached(x_trains, y_trains, resp, self.f_ind_old)
         if float(torch.mean(q_)) == 0.0:                     # nothing scored yet: cluster 0 takes the whole batch
-            snr_ = torch.zeros((N, M, D), dtype=f64, device=dev)
-            if self.share_gp and D > 1:
-                raise NotImplementedError("share_gp with several leads is not part of this build")
-            firsts = [self.create_gp_default() for _ in range(D)]
-            for ld, out in enumerate(self._passes(x, y, [(firsts[ld], self._ycol(Yw, y, ld, 0), resp[:, 0]) for ld in range(D)])):
-                self._note_full_pass(resp[:, 0], out)
-                q_[:, 0, ld], q_lat_[:, 0, ld] = out
-                if liks is not None:
-                    q_[:, 0, ld] += liks[:, 0, ld]
-                snr_[:, 0, ld] = self.compute_snr(self._ylead(Yw, y, ld, 0), firsts[ld])
-                self.gpmodels[ld][0] = firsts[ld]
-        reallocate = False
+            snr_ = self._seed_first_cluster(x_trains, y_trains, resp, q_, q_lat_, Yw, liks, M)
+        cur = Current(x_trains, y_trains, resp, respPair, q_, q_lat_, snr_, startPi, Yw, liks, reparam)
         indexes_ = []
         for m in range(M):
             idx = torch.as_tensor(self.gpmodels[0][m].indexes, dtype=torch.int64)
             indexes_.append(idx if idx.numel() else torch.where(resp[:, m] == 1.0)[0])
         f_ind_old = self.f_ind_old.clone()
+        q_simple = self._representative_scores(cur, M, f_ind_old, indexes_)
+        final, empty_estimation = self._try_reallocation(cur, M, q_simple, f_ind_old) if M > 1 else (None, False)
+        if final is not None:
+            return final
 
-        # every cluster re-seeded with its representative segment only: how well does that one segment explain the batch?
-        q_simple = q_.clone()
-        for ld in range(D):
+        # ---- birth proposals, from tables with one more (empty) cluster column -----------------------------------------
+        resp_, _, q_def, q_lat_def, snr_aux_def = self.new_group(resp, respPair, q_simple.clone(), q_lat_.clone(), snr_.clone())
+        _, _, q__def, q_lat__def, snr__def = self.new_group(resp, respPair, q_.clone(), q_lat_.clone(), snr_.clone())
+        f_ind_grown = torch.zeros(M + 1, dtype=torch.int64)
+        f_ind_grown[:self.f_ind_old.shape[0]] = self.f_ind_old
+        grown = Grown(M + 1, f_ind_grown, resp_, q_def, q_lat_def, snr_aux_def, q__def, q_lat__def, snr__def)
+        # the candidates are PREPARED together (_prepare_birth), their cluster rebuilds run side by side, the decisions follow in order
+        props = [self._prepare_birth(cur, grown, f_new, m_chosen, empty_estimation)
+                 for f_new, m_chosen in self._select_seeds(cur, grown, q_simple, f_ind_old, indexes_, empty_estimation)]
+        # ... the rebuilds in two batches: the first candidate alone (it is the one most often accepted), then all the others.
+        for ip, P in enumerate(props):
+            if ip < 2:
+                outs = iter(self._passes(cur.x, cur.y, [spec for p in (props[:1] if ip == 0 else props[1:])
+                                                        for spec in self._pass_specs(p.cols, p.Yp, cur.y, p.resp_temp)]))
+            final = self._decide_birth(cur, grown, P, outs)
+            if final is not None:
+                return final
+        return resp, respPair, q_, q_lat_, snr_, True
+
+    def _seed_first_cluster(self, x, y, resp, q_, q_lat_, Yw, liks, M):
+        """A fresh model per lead absorbs the whole batch as cluster 0; q_, q_lat_ are filled in place, the new snr table is returned."""
+        D = self.n_outputs
+        snr_ = torch.zeros((y.shape[0], M, D), dtype=f64, device=self.device)
+        if self.share_gp and D > 1:
+            raise NotImplementedError("share_gp with several leads is not part of this build")
+        cols = [Column(ld, 0, 0, self.create_gp_default(), True) for ld in range(D)]
+        outs = iter(self._passes(x, y, self._pass_specs(cols, Yw, y, resp)))
+        for c in cols:
+            self._take_pass(c, outs, resp, q_, q_lat_, snr_, y, Yw, liks, None)     # (every segment is a member)
+            self.gpmodels[c.ld][0] = c.gp
+        return snr_
+
+    def _representative_scores(self, cur, M, f_ind_old, indexes_):
+        """Every cluster re-seeded with its representative segment only: how well does that one segment explain the batch?"""
+        x, y, Yw, liks = cur.x, cur.y, cur.Yw, cur.liks
+        q_simple = cur.q_.clone()
+        for ld in range(self.n_outputs):
             for m in range(M):
                 q_simple[:, m, ld], _ = self._one_member_scores(self.gpmodels[ld][m], x, y, ld, int(f_ind_old[m]),
                                                                 include=len(indexes_[m]) > 0, ycol=self._ycol(Yw, y, ld, m))
                 if liks is not None:
                     q_simple[:, m, ld] += liks[:, m, ld]
+        return q_simple
 
-        if M > 1:
-            q_aux, snr_aux = q_simple.clone(), snr_.clone()
-            if self._counts(resp)[-1] == 0:
-                q_aux[:, -1, :] = torch.min(q_aux) * 2.0
-                snr_aux[:, -1, :] = torch.min(snr_aux) * 2.0
-            resp_temp, respPair_temp = self._assign(self.weight_mean(q_aux, snr_aux), startPi)
-            reorder = torch.argsort(self._counts(resp_temp), descending=True)
-            resp_temp = resp_temp[:, reorder]
-            q, q_lat = q_.clone(), q_lat_.clone()
-            gpmodels_temp = [[] for _ in range(D)]
-            plan = []
-            for ld in range(D):
-                for m in range(M):
-                    r = int(reorder[m])
-                    changed = not torch.equal(resp[:, r].long(), resp_temp[:, m].long())
-                    gp = self._fresh_copy(self.gpmodels[ld][r]) if changed else self.gpmodels[ld][r]
-                    plan.append((ld, m, r, gp, changed))
-                    gpmodels_temp[ld].append(gp)
-            outs = iter(self._passes(x, y, [(gp, self._ycol(Yw, y, ld, r), resp_temp[:, m]) for ld, m, r, gp, changed in plan if changed]))
-            for ld, m, r, gp, changed in plan:
-                if changed:
-                    out = next(outs)
-                    self._note_full_pass(resp_temp[:, m], out)
-                    q[:, m, ld], q_lat[:, m, ld] = out if out is not None else (q[:, r, ld], q_lat[:, r, ld])
-                    if liks is not None:
-                        q[:, m, ld] += liks[:, r, ld]
-                    snr_aux[:, m, ld] = self.compute_snr(self._ylead(Yw, y, ld, r), gp)
-                else:
-                    q[:, m, ld] = q_[:, r, ld].clone()                    # quirk: q_lat keeps column m of the old table
-                    snr_aux[:, m, ld] = snr_[:, r, ld].clone()
-            q_b, e_b = self._elbo_of(resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, M, False)
-            q_def__, elbo_def__ = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, M, False)
-            resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, base_ = self._converge(
-                M, x, y, resp_temp, respPair_temp, q, q_lat, snr_aux, startPi, q_def__, elbo_def__, gpmodels_temp, reparam,
-                q_b + e_b, 20, False, False)
-            self._log(">>> Prev -------")
-            q_bas, elbo_bas = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, M, False)
-            self._log(">>> Post -------")
-            q_bas_post, elbo_post = self._elbo_of(resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, M, False)
-            if int(torch.sum(self._counts(resp_temp) < 1.0)) == 0:
-                if q_bas + elbo_bas < q_bas_post + elbo_post and q_bas != q_bas_post:
-                    self._log("Reallocating beats into existing groups.")
-                    self.gpmodels = gpmodels_temp
-                    self.y_train = self.select_assigned_warp(Yw, y, resp_temp, reorder)
-                    self.f_ind_old = self._pick_representatives(resp_temp, self.weight_mean(q_simple, snr_aux), M, f_ind_old)
-                    self.snr_norm = self.normalize_snr(snr_aux)
-                    return resp_temp, respPair_temp, q, q_lat, snr_aux, True
-                self._log("Not reallocating, trying to generate new group.")
+    def _try_reallocation(self, cur, M, q_simple, f_ind_old):
+        """Re-assign with the one-member scores, rebuild the clusters that changed, iterate estimate_q_all.  Returns (estimate_q_first's result,
+        _) when the attempt ends the round - accepted, or the emergency exit -, (None, empty_estimation) when the birth proposals follow."""
+        x, y, resp, respPair, q_, q_lat_, snr_ = cur.x, cur.y, cur.resp, cur.respPair, cur.q_, cur.q_lat_, cur.snr_
+        q_aux, snr_aux = q_simple.clone(), snr_.clone()
+        if self._counts(resp)[-1] == 0:
+            q_aux[:, -1, :] = torch.min(q_aux) * 2.0
+            snr_aux[:, -1, :] = torch.min(snr_aux) * 2.0
+        resp_temp, respPair_temp = self._assign(self.weight_mean(q_aux, snr_aux), cur.startPi)
+        reorder, resp_temp = _by_size(resp_temp)
+        q, q_lat = q_.clone(), q_lat_.clone()
+        cols, gpmodels_temp = self._plan_columns(resp, resp_temp, reorder, None)
+        outs = iter(self._passes(x, y, self._pass_specs(cols, cur.Yw, y, resp_temp)))
+        for c in cols:
+            if c.rebuild:
+                self._take_pass(c, outs, resp_temp, q, q_lat, snr_aux, y, cur.Yw, cur.liks, (q, q_lat))
             else:
-                self._log(">>> Possible emergency reallocation. Prev ----")
-                q_bas, elbo_bas = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, self.M, False)
-                if q_bas + elbo_bas < base_:
-                    self._log("Emergency reallocation and removing last group.")
-                    for ld in range(D):
-                        gpmodels_temp[ld] = gpmodels_temp[ld][:-1]
-                    self.gpmodels = gpmodels_temp
-                    self.snr_norm = self.normalize_snr(snr_aux)
-                    resp_temp, respPair_temp, q, q_lat, snr_aux = self.remove_last_group(resp_temp, respPair_temp, q, q_lat, snr_aux)
-                    reorder = torch.argsort(self._counts(resp_temp), descending=True)
-                    self.f_ind_old = self.f_ind_old[reorder]
-                    return resp_temp, respPair_temp, q, q_lat, snr_aux, True
-                self._log("Bad estimation")
-                empty_estimation = True
+                q[:, c.m, c.ld] = q_[:, c.r, c.ld].clone()            # quirk: q_lat keeps column m of the old table
+                snr_aux[:, c.m, c.ld] = snr_[:, c.r, c.ld].clone()
+        q_b, e_b = self._elbo_of(resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, M, False)
+        q_def__, elbo_def__ = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, M, False)
+        resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, base_ = self._converge(
+            M, x, y, resp_temp, respPair_temp, q, q_lat, snr_aux, cur.startPi, q_def__, elbo_def__, gpmodels_temp, cur.reparam,
+            q_b + e_b, 20, False, False)
+        self._log(">>> Prev -------")
+        q_bas, elbo_bas = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, M, False)
+        self._log(">>> Post -------")
+        q_bas_post, elbo_post = self._elbo_of(resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, M, False)
+        if int(torch.sum(self._counts(resp_temp) < 1.0)) == 0:
+            if q_bas + elbo_bas < q_bas_post + elbo_post and q_bas != q_bas_post:
+                self._log("Reallocating beats into existing groups.")
+                self.gpmodels = gpmodels_temp
+                self.y_train = self.select_assigned_warp(cur.Yw, y, resp_temp, reorder)
+                self.f_ind_old = self._pick_representatives(resp_temp, self.weight_mean(q_simple, snr_aux), M, f_ind_old)
+                self.snr_norm = self.normalize_snr(snr_aux)
+                return (resp_temp, respPair_temp, q, q_lat, snr_aux, True), False
+            self._log("Not reallocating, trying to generate new group.")
+            return None, False
+        self._log(">>> Possible emergency reallocation. Prev ----")
+        q_bas, elbo_bas = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, self.M, False)
+        if q_bas + elbo_bas < base_:
+            resp_temp, respPair_temp, q, q_lat, snr_aux = self._drop_last_group(gpmodels_temp, resp_temp, respPair_temp, q, q_lat, snr_aux)
+            self.f_ind_old = self.f_ind_old[torch.argsort(self._counts(resp_temp), descending=True)]     # (the order after the removal)
+            return (resp_temp, respPair_temp, q, q_lat, snr_aux, True), False
+        self._log("Bad estimation")
+        return None, True
 
-        # ---- birth proposals: candidate seeds = segments their own cluster explains worst ---------------------------
+    def _select_seeds(self, cur, grown, q_simple, f_ind_old, indexes_, empty_estimation):
+        """The round's candidates [(seed segment, its cluster)]: segments their own cluster explains worst - half of the
+        n_explore_steps by the one-member score, half by the current scores; no representative, no near-duplicate of the one before."""
+        resp, M = cur.resp, grown.M - 1
         lab = torch.argmax(resp, dim=1)
 
         def own(t3):          # weight_mean(t)[where(resp == 1)], scaled to [-1, 0] (GPI_HDP.py:1462-1467)
@@ -561,7 +611,7 @@ class OfflineLoop:
 
         q_rank = own(q_simple)
         by_rank = torch.argsort(q_rank)
-        by_total = torch.argsort(own(q_) + own(q_lat_))
+        by_total = torch.argsort(own(cur.q_) + own(cur.q_lat_))
         near_cache = {}
 
         def near(i):          # segments whose rank is within 1 % of segment i's (GPI_HDP.py:1474)
@@ -591,154 +641,119 @@ class OfflineLoop:
 
         fill(by_rank, 0, half)
         fill(by_total, half, n_steps)
-
-        resp_, respPair_, q_def, q_lat_def, snr_aux_def = self.new_group(resp, respPair, q_simple.clone(), q_lat_.clone(), snr_.clone())
-        _, _, q__def, q_lat__def, snr__def = self.new_group(resp, respPair, q_.clone(), q_lat_.clone(), snr_.clone())
-        M = M + 1
-        f_ind_old = torch.zeros(M, dtype=torch.int64)
-        f_ind_old[:self.f_ind_old.shape[0]] = self.f_ind_old
-        # The candidates of one round do not depend on each other's outcome (the reference tries them one by one and stops at the
-        # first it accepts; nothing it computes for candidate j feeds candidate j + 1).  They are therefore PREPARED together
-        # (host logic + one one-member score and one message pass each), all the cluster rebuilds they need run side by side as
-        # one batch of independent chains, and the accept / reject decisions are then taken in the reference's order.
-        props = []
-        step, last = 0, {-1}
+        chosen, step, last = [], 0, {-1}
         for f_new in seeds.tolist():
             if step == n_steps:
                 break
-            m_chosen = cluster_of(f_new, M - 1)
-            if f_new == int(f_ind_old[m_chosen]) or last <= near(f_new):
+            m_chosen = cluster_of(f_new, M)
+            if f_new == int(grown.f_ind_old[m_chosen]) or last <= near(f_new):
                 continue
-            P = {"f_new": f_new, "m_chosen": m_chosen, "f_ind_old_temp": None, "q_simple_": None}
-            if not empty_estimation:
-                P["f_ind_old_temp"] = f_ind_old.clone()
-                P["f_ind_old_temp"][-1] = f_new
-                q_simple_ = q_def.clone()
-                q, q_lat, snr_aux = q_def.clone(), q_lat_def.clone(), snr_aux_def.clone()
-                q__, q_lat__, snr__ = q__def.clone(), q_lat__def.clone(), snr__def.clone()
+            if not empty_estimation:                 # (quirk: a round after a failed emergency exit counts no steps)
                 last = near(f_new)
                 step += 1
                 self._log(f"Step {step}/{n_steps}- Trying to divide: {m_chosen} with beat {f_new}")
-                Yp, lp = self.warp_batch_by_resp_amtgp_cached(x, y, resp_, P["f_ind_old_temp"])     # + the column warped onto the seed
-                for ld in range(D):
-                    q_simple_[:, -1, ld], g1 = self._one_member_scores(self.gpmodels[ld][m_chosen], x, y, ld, f_new,
-                                                                       ycol=self._ycol(Yp, y, ld, -1))
-                    if lp is not None:
-                        q_simple_[:, -1, ld] += lp[:, -1, ld]
-                    snr_aux[:, -1, ld] = self.compute_snr(self._ylead(Yp, y, ld, -1), g1)
-                P["q_simple_"] = q_simple_
-                resp_temp, respPair_temp = self._assign(self.weight_mean(q_simple_, snr_aux), startPi)
-            else:
-                q, q_lat, snr_aux = q__def.clone(), q_lat__def.clone(), snr__def.clone()
-                q__, q_lat__, snr__ = q__def.clone(), q_lat__def.clone(), snr__def.clone()
-                q[:, -1, :] = torch.min(q) * 2.0
-                q__[:, -1, :] = torch.min(q__) * 2.0
-                snr_aux[:, -1, :] = torch.min(snr_aux) * 2.0
-                q__[f_new, -1, :] = 0.0
-                resp_temp, respPair_temp = self._assign(self.weight_mean(q__, snr_aux), startPi)
-                Yp, lp = Yw, liks                    # (the reference keeps the round's warps on this path)
-            reorder = torch.argsort(self._counts(resp_temp), descending=True)
-            resp_temp = resp_temp[:, reorder]
-            gpmodels_temp = [[] for _ in range(D)]
-            plan = []
-            for ld in range(D):
-                for m in range(M):
-                    r = int(reorder[m])
-                    if r == M - 1:
-                        gp = self._fresh_copy(self.gpmodels[ld][m_chosen]) if self.share_gp else self.create_gp_default()
-                        rebuild = True
-                    else:
-                        rebuild = not torch.equal(resp[:, r].long(), resp_temp[:, m].long())
-                        gp = self._fresh_copy(self.gpmodels[ld][r]) if rebuild else self.gpmodels[ld][r]
-                    plan.append((ld, m, r, gp, rebuild))
-                    gpmodels_temp[ld].append(gp)
-            P.update(q=q, q_lat=q_lat, snr_aux=snr_aux, q__=q__, q_lat__=q_lat__, snr__=snr__, resp_temp=resp_temp,
-                     respPair_temp=respPair_temp, reorder=reorder, gpmodels_temp=gpmodels_temp, plan=plan, Yp=Yp, lp=lp)
-            props.append(P)
-        # ... in two batches: the first candidate alone (it is the one most often accepted), then all the others.
-        def rebuilds(ps):
-            return iter(self._passes(x, y, [(gp, self._ycol(P["Yp"], y, ld, r), P["resp_temp"][:, m])
-                                            for P in ps for ld, m, r, gp, rebuild in P["plan"] if rebuild]))
+            chosen.append((f_new, m_chosen))
+        return chosen
 
-        outs = None
-        for ip, P in enumerate(props):
-            if ip < 2:
-                outs = rebuilds(props[:1] if ip == 0 else props[1:])
-            f_new, m_chosen, q_simple_, f_ind_old_temp = P["f_new"], P["m_chosen"], P["q_simple_"], P["f_ind_old_temp"]
-            q, q_lat, snr_aux, q__, q_lat__, snr__ = P["q"], P["q_lat"], P["snr_aux"], P["q__"], P["q_lat__"], P["snr__"]
-            resp_temp, respPair_temp, reorder, gpmodels_temp = P["resp_temp"], P["respPair_temp"], P["reorder"], P["gpmodels_temp"]
-            Yp, lp = P["Yp"], P["lp"]
-            for ld, m, r, gp, rebuild in P["plan"]:
-                if rebuild:
-                    out = next(outs)
-                    self._note_full_pass(resp_temp[:, m], out)
-                    q[:, m, ld], q_lat[:, m, ld] = out if out is not None else (q__[:, r, ld], q_lat__[:, r, ld])
-                    if lp is not None:
-                        q[:, m, ld] += lp[:, r, ld]
-                    snr_aux[:, m, ld] = self.compute_snr(self._ylead(Yp, y, ld, r), gp)
-                else:
-                    q[:, m, ld] = q__[:, r, ld].clone()
-                    q_lat[:, m, ld] = q_lat__[:, r, ld].clone()
-                    snr_aux[:, m, ld] = snr__[:, r, ld].clone()
-            q_b, e_b = self._elbo_of(resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, M, True)
-            counts_t = self._counts(resp_temp)
-            if int(torch.argmax(counts_t)) == M - 1:
-                self._log("Bad estimation")
-                continue
-            if int(torch.sum(counts_t < 1.0)) > 0:
-                self._log(">>> Possible emergency reallocation. Prev ----")
-                q_bas, elbo_bas = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, self.M, False)
-                if q_bas + elbo_bas < q_b + e_b:
-                    self._log("Emergency reallocation and removing last group.")
-                    for ld in range(D):
-                        gpmodels_temp[ld] = gpmodels_temp[ld][:-1]
-                    resp_temp, respPair_temp, q, q_lat, snr_aux = self.remove_last_group(resp_temp, respPair_temp, q, q_lat, snr_aux)
-                    self.gpmodels = gpmodels_temp
-                    for ld in range(D):
-                        self.wp_sys[ld] = self.wp_sys[ld][:-1]                    # quirk: only this exit drops a warper
-                    self.f_ind_old = f_ind_old[reorder]
-                    self.y_train = self.select_assigned_warp(Yp, y, resp_temp, reorder)
-                    self.snr_norm = self.normalize_snr(snr_aux)
-                    return resp_temp, respPair_temp, q, q_lat, snr_aux, True
-                self._log("Bad estimation")
-                continue
-            q_def__, elbo_def__ = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, self.M, False)
-            resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, _ = self._converge(
-                M, x, y, resp_temp, respPair_temp, q, q_lat, snr_aux, startPi, q_def__, elbo_def__, gpmodels_temp, reparam,
-                q_b + e_b, 10, True, True, f_ind_old=f_ind_old_temp)
-            self._log(f"- Trying to divide: {m_chosen} with beat {f_new}")
-            self._log(">>> Prev -------")
-            q_bas, elbo_bas = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, self.M, False)
-            self._log(">>> Post -------")
-            q_bas_post, elbo_post = self._elbo_of(resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, M, True)
-            counts_t = self._counts(resp_temp)
-            if bool(torch.all(counts_t >= 1.0)) and int(torch.argmax(counts_t)) != resp_temp.shape[1] - 1:
-                if q_bas + elbo_bas < q_bas_post + elbo_post:
-                    self._log(f"Chosen to divide: {m_chosen} with beat {f_new}")
-                    self.gpmodels = gpmodels_temp
-                    for ld in range(D):
-                        self.wp_sys[ld].append(self.create_wp_sys_default())
-                    self.y_train = self.select_assigned_warp(Yp, y, resp_temp, reorder)
-                    self.f_ind_old = self._pick_representatives(resp_temp, self.weight_mean(q_simple_, snr_aux), M, f_ind_old)
-                    self.snr_norm = self.normalize_snr(snr_aux)
-                    return resp_temp, respPair_temp, q, q_lat, snr_aux, reallocate
+    def _prepare_birth(self, cur, grown, f_new, m_chosen, empty_estimation):
+        """One candidate up to where its clusters need rebuilding: the seed's one-member score as the new column, the assignment, the columns.
+        The candidates of a round do not depend on each other's outcome (the reference tries them one by one and stops at the first it accepts;
+        nothing computed for candidate j feeds candidate j + 1), so all are prepared (one one-member score + message pass each) before a decision."""
+        x, y, resp, startPi, D = cur.x, cur.y, cur.resp, cur.startPi, self.n_outputs
+        f_ind_old_temp = q_simple_ = None
+        q__, q_lat__, snr__ = grown.q__def.clone(), grown.q_lat__def.clone(), grown.snr__def.clone()
+        if not empty_estimation:
+            f_ind_old_temp = grown.f_ind_old.clone()
+            f_ind_old_temp[-1] = f_new
+            q_simple_ = grown.q_def.clone()
+            q, q_lat, snr_aux = grown.q_def.clone(), grown.q_lat_def.clone(), grown.snr_aux_def.clone()
+            Yp, lp = self.warp_batch_by_resp_amtgp_cached(x, y, grown.resp_, f_ind_old_temp)     # + the column warped onto the seed
+            for ld in range(D):
+                q_simple_[:, -1, ld], g1 = self._one_member_scores(self.gpmodels[ld][m_chosen], x, y, ld, f_new,
+                                                                   ycol=self._ycol(Yp, y, ld, -1))
+                if lp is not None:
+                    q_simple_[:, -1, ld] += lp[:, -1, ld]
+                snr_aux[:, -1, ld] = self.compute_snr(self._ylead(Yp, y, ld, -1), g1)
+            resp_temp, respPair_temp = self._assign(self.weight_mean(q_simple_, snr_aux), startPi)
+        else:
+            q, q_lat, snr_aux = grown.q__def.clone(), grown.q_lat__def.clone(), grown.snr__def.clone()
+            q[:, -1, :] = torch.min(q) * 2.0
+            q__[:, -1, :] = torch.min(q__) * 2.0
+            snr_aux[:, -1, :] = torch.min(snr_aux) * 2.0
+            q__[f_new, -1, :] = 0.0
+            resp_temp, respPair_temp = self._assign(self.weight_mean(q__, snr_aux), startPi)
+            Yp, lp = cur.Yw, cur.liks            # (the reference keeps the round's warps on this path)
+        reorder, resp_temp = _by_size(resp_temp)
+        cols, gpmodels_temp = self._plan_columns(resp, resp_temp, reorder, m_chosen)
+        return Proposal(f_new=f_new, m_chosen=m_chosen, f_ind_old_temp=f_ind_old_temp, q_simple_=q_simple_, q=q, q_lat=q_lat, snr_aux=snr_aux,
+                        q__=q__, q_lat__=q_lat__, snr__=snr__, resp_temp=resp_temp, respPair_temp=respPair_temp, reorder=reorder,
+                        gpmodels_temp=gpmodels_temp, cols=cols, Yp=Yp, lp=lp)
+
+    def _decide_birth(self, cur, grown, P, outs):
+        """Take the proposal's rebuilt columns from ``outs``, iterate estimate_q_all and accept / reject.  Returns the tuple
+        estimate_q_first returns when the proposal ends the round (accepted, or the emergency exit), None to go on."""
+        x, y, resp, respPair, q_, q_lat_, snr_ = cur.x, cur.y, cur.resp, cur.respPair, cur.q_, cur.q_lat_, cur.snr_
+        M, D, f_ind_old = grown.M, self.n_outputs, grown.f_ind_old
+        q, q_lat, snr_aux, resp_temp, respPair_temp, gpmodels_temp = P.q, P.q_lat, P.snr_aux, P.resp_temp, P.respPair_temp, P.gpmodels_temp
+        for c in P.cols:
+            if c.rebuild:
+                self._take_pass(c, outs, resp_temp, q, q_lat, snr_aux, y, P.Yp, P.lp, (P.q__, P.q_lat__))
             else:
-                self._log("Bad estimation")
-        return resp, respPair, q_, q_lat_, snr_, True
+                q[:, c.m, c.ld] = P.q__[:, c.r, c.ld].clone()
+                q_lat[:, c.m, c.ld] = P.q_lat__[:, c.r, c.ld].clone()
+                snr_aux[:, c.m, c.ld] = P.snr__[:, c.r, c.ld].clone()
+        q_b, e_b = self._elbo_of(resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, M, True)
+        counts_t = self._counts(resp_temp)
+        if int(torch.argmax(counts_t)) == M - 1:
+            self._log("Bad estimation")
+            return None
+        if int(torch.sum(counts_t < 1.0)) > 0:
+            self._log(">>> Possible emergency reallocation. Prev ----")
+            q_bas, elbo_bas = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, self.M, False)
+            if q_bas + elbo_bas < q_b + e_b:
+                resp_temp, respPair_temp, q, q_lat, snr_aux = self._drop_last_group(gpmodels_temp, resp_temp, respPair_temp, q, q_lat, snr_aux,
+                                                                                    snr_seen=snr_aux[:, :-1, :])
+                for ld in range(D):
+                    self.wp_sys[ld] = self.wp_sys[ld][:-1]                    # quirk: only this exit drops a warper
+                self.f_ind_old = f_ind_old[P.reorder]                           # quirk: the extended table, the proposal's order
+                self.y_train = self.select_assigned_warp(P.Yp, y, resp_temp, P.reorder)
+                return resp_temp, respPair_temp, q, q_lat, snr_aux, True
+            self._log("Bad estimation")
+            return None
+        q_def__, elbo_def__ = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, self.M, False)
+        resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, _ = self._converge(
+            M, x, y, resp_temp, respPair_temp, q, q_lat, snr_aux, cur.startPi, q_def__, elbo_def__, gpmodels_temp, cur.reparam,
+            q_b + e_b, 10, True, True, f_ind_old=P.f_ind_old_temp)
+        self._log(f"- Trying to divide: {P.m_chosen} with beat {P.f_new}")
+        self._log(">>> Prev -------")
+        q_bas, elbo_bas = self._elbo_of(resp, respPair, q_, q_lat_, snr_, self.gpmodels, self.M, False)
+        self._log(">>> Post -------")
+        q_bas_post, elbo_post = self._elbo_of(resp_temp, respPair_temp, q, q_lat, snr_aux, gpmodels_temp, M, True)
+        counts_t = self._counts(resp_temp)
+        if bool(torch.all(counts_t >= 1.0)) and int(torch.argmax(counts_t)) != resp_temp.shape[1] - 1:
+            if q_bas + elbo_bas < q_bas_post + elbo_post:
+                self._log(f"Chosen to divide: {P.m_chosen} with beat {P.f_new}")
+                self.gpmodels = gpmodels_temp
+                for ld in range(D):
+                    self.wp_sys[ld].append(self.create_wp_sys_default())
+                self.y_train = self.select_assigned_warp(P.Yp, y, resp_temp, P.reorder)
+                self.f_ind_old = self._pick_representatives(resp_temp, self.weight_mean(P.q_simple_, snr_aux), M, f_ind_old)
+                self.snr_norm = self.normalize_snr(snr_aux)
+                return resp_temp, respPair_temp, q, q_lat, snr_aux, False
+        else:
+            self._log("Bad estimation")
+        return None
 
     # ------------------------------------------------------------------ one EM iteration
     def _log_pis(self, M, transTheta, startTheta):
         """log transition matrix / start vector handed to the proposals (GPI_HDP.py:1188-1194); the messages themselves
         always rebuild the transition matrix from ``self.transTheta`` (GPI_HDP.py:3580)."""
-        tt, st = _np(transTheta), _np(startTheta)
-        dg = hdp_global.digamma
-        transPi = dg(tt[:M, :M]) - np.log(np.sum(np.exp(dg(tt[:M, :M + 1])), axis=1) + 1e-5)[:, None]
+        st, dg = _np(startTheta), hdp_global.digamma
         startPi = dg(st[:M]) - np.log(np.sum(np.exp(dg(st[:M + 1]))) + 1e-5)
-        return torch.as_tensor(transPi, dtype=f64), torch.as_tensor(startPi, dtype=f64)
+        return torch.as_tensor(_log_trans(transTheta, M, 1e-5), dtype=f64), torch.as_tensor(startPi, dtype=f64)
 
     def variational_local_terms_batch(self, M, x_trains, y_trains, transTheta, startTheta, resp, respPair, q, q_lat, snr, reallocate):
-        """GPI_HDP.py:1170-1241: proposals (estimate_q_first) when the last cluster is in use, then estimate_q_all until the
-        bound converges."""
+        """GPI_HDP.py:1170-1241: proposals (estimate_q_first) when the last cluster is in use, then estimate_q_all until the bound converges."""
         transTheta = self.transTheta if transTheta is None else transTheta
         startTheta = self.startTheta if startTheta is None else startTheta
         self.trans_A, startPi = self._log_pis(M, transTheta, startTheta)
@@ -791,7 +806,6 @@ class OfflineLoop:
         self.compute_snr_ini(y)
         M = self.M
         self.x_train = x
-        iteration = 0
         resp = torch.zeros((N, M), dtype=f64)
         respPair = torch.zeros((N, M, M), dtype=f64)
         respPair[:, 0, 0] = 1.0
@@ -825,9 +839,7 @@ class OfflineLoop:
             else:
                 transStateCount, startStateCount = np.ones((M + 1, M + 1)), np.ones(M + 1)
             self._update_global(M, transStateCount, startStateCount)
-            tt = _np(self.transTheta)
-            dg = hdp_global.digamma
-            self.trans_A = torch.as_tensor(dg(tt[:M, :M]) - np.log(np.sum(np.exp(dg(tt[:M, :M + 1])), axis=1))[:, None])
+            self.trans_A = torch.as_tensor(_log_trans(self.transTheta, M))               # quirk: no 1e-5 here
             if self.T <= 1:
                 break
             elbo_ = self.calcELBO_NonlinearTerms(resp, respPair)
@@ -839,26 +851,22 @@ class OfflineLoop:
             iteration += 1
             self._log(f"\n-------Start lower Bound Iteration {iteration}-------")
             labels = torch.argmax(resp, dim=1)               # = torch.where(resp == 1.0)[1] for one-hot rows
-            if (it_limit is not None and iteration >= it_limit) or (first_batch and self.M == self.max_models):
-                self.train_elbo.append(elbo_)
-                self.resp_assigned.append(labels)
-                break
             self.train_elbo.append(elbo_)
             self.resp_assigned.append(labels)
+            if (it_limit is not None and iteration >= it_limit) or (first_batch and self.M == self.max_models):
+                break
             if first_batch:
                 self.q.append(q)
                 self.elbo_last = elbo_
             self.q_last, self.q_lat_last, self.snr_last = q, q_lat, snr
             self.startStateCount_last, self.transStateCount_last = startStateCount, transStateCount
             self.resp_last, self.respPair_last = resp, respPair
+            if not first_batch:
+                self.y_train = y
             ra = self.resp_assigned
             if (int(torch.sum(self._counts(resp) == 0.0)) > 1 or
                     (len(ra) > 1 and ra[-2].shape[0] == ra[-1].shape[0] and bool(torch.all(ra[-2] == ra[-1])))):
-                if not first_batch:
-                    self.y_train = y
                 break
-            if not first_batch:
-                self.y_train = y
 
     def cluster_new_batch_learning(self, x_new, y_new, it_limit=None):
         """GPI_HDP.py:3002-3151, ``cluster_new_batch(learning=True)``: classify the new segments with the frozen models, append
@@ -877,20 +885,14 @@ class OfflineLoop:
         resp = torch.cat([self.resp_last, resp_new])
         respPair = torch.cat([self.respPair_last, respPair_new])
         self.snr_norm = torch.cat([self.snr_norm, self.normalize_snr(snr_new)])
-        reorder = torch.argsort(self._counts(resp), descending=True)
-        resp = resp[:, reorder]                                                # quirk: the pair table keeps the old order
+        reorder, resp = _by_size(resp)                                    # quirk: the pair table keeps the old order
         q = torch.zeros((N, self.M, D), dtype=f64, device=dev)
         q_lat, snr = torch.zeros_like(q), torch.zeros_like(q)
-        models = [[self._fresh_copy(self.gpmodels[ld][int(reorder[m])]) for m in range(self.M)] for ld in range(D)]
-        outs = iter(self._passes(x, y, [(models[ld][m], y[:, :, [ld]], resp[:, m]) for ld in range(D) for m in range(self.M)]))
-        for ld in range(D):
-            for m in range(self.M):
-                out = next(outs)
-                self._note_full_pass(resp[:, m], out)
-                if out is not None:
-                    q[:, m, ld], q_lat[:, m, ld] = out
-                snr[:, m, ld] = self.compute_snr(y[:, :, ld], models[ld][m])
-        self.gpmodels = models
+        cols = [Column(ld, m, m, self._fresh_copy(self.gpmodels[ld][int(reorder[m])]), True) for ld in range(D) for m in range(self.M)]
+        outs = iter(self._passes(x, y, self._pass_specs(cols, None, y, resp)))
+        for c in cols:
+            self._take_pass(c, outs, resp, q, q_lat, snr, y, None, None, (q, q_lat))     # without members: its own (zero) columns
+        self.gpmodels = [[c.gp for c in cols if c.ld == ld] for ld in range(D)]
         resp, respPair = self._assign(self.weight_mean(q, snr), startPi)
         self.x_train = x
         self._em_loop(x, y, resp, respPair, q, q_lat, snr, resp[0].numpy().copy(), torch.sum(respPair, dim=0).numpy(), it_limit,
@@ -903,6 +905,3 @@ class OfflineLoop:
             self.transTheta, self.startTheta = self._calcThetaFull(transStateCount, startStateCount, M + 1)
             self.rho, self.omega = self.find_optimum_rhoOmega()
 
-
-def _np(a):
-    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)

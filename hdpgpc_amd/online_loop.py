@@ -47,8 +47,7 @@ class OnlineLoop:
 
     def reorder(self, resp, respPair, q, q_lat):
         """GPI_HDP.py:1091-1110: clusters sorted by size, largest first (tables, score matrices and the model list)."""
-        order = torch.argsort(torch.sum(resp, dim=0), descending=True)
-        resp = resp[:, order]
+        order, resp = _by_size(resp)
         respPair = respPair[:, order, :][:, :, order]
         od = ops.to_dev(order, torch.int64, q.device)
         q, q_lat = q.index_select(1, od), q_lat.index_select(1, od)
@@ -114,16 +113,6 @@ class OnlineLoop:
             if np.isfinite(mx):
                 last[b] -= mx
         return lab, prs, last, labels
-
-    @staticmethod
-    def _tables(labels, pairs, K):
-        """One-hot host tables resp [T, K], respPair [T, K, K] of a hard assignment (what _one_hot_tables builds)."""
-        N = labels.shape[0]
-        resp = torch.zeros((N, K), dtype=f64)
-        resp[torch.arange(N), torch.as_tensor(labels)] = 1.0
-        respPair = torch.zeros((N, K * K), dtype=f64)
-        respPair[torch.arange(N), torch.as_tensor(pairs)] = 1.0
-        return resp, respPair.reshape(N, K, K)
 
     def _bound_from_labels(self, labels, pairs, K, n_rows, n_cols, q_sum, lat_sum, lds, post):
         """compute_q_elbo(resp[:n_rows, :n_cols], respPair[:n_rows, :n_cols, :n_cols], ..., one_sample=True) (GPI_HDP.py:1796-1836)
@@ -309,7 +298,7 @@ class OnlineLoop:
                     if q_bas_post + elbo_bas_post > q_prev_post + elbo_prev_post:
                         chosen = 2 + r
                         break
-            resp, respPair = self._tables(lab[chosen], prs[chosen], K)
+            resp, respPair = _tables(lab[chosen], prs[chosen], K)
             _tick("bounds")
             resplog = last[chosen]
             q_chos, q_lat_chos = Qall[chosen].unsqueeze(-1).clone(), Lall[chosen].unsqueeze(-1).clone()
@@ -369,8 +358,7 @@ class OnlineLoop:
                 self.transTheta, self.startTheta = self._calcThetaFull(transStateCount, startStateCount, M)
                 self.rho, self.omega = self.find_optimum_rhoOmega()
         _tick("rho_omega")
-        tt = _np(self.transTheta)
-        self.trans_A = torch.as_tensor(_digamma(tt[:M, :M]) - np.log(np.sum(np.exp(_digamma(tt[:M, :M + 1])), axis=1))[:, None])
+        self.trans_A = torch.as_tensor(_log_trans(self.transTheta, M))
         resp_mod = resp[-1].numpy()
         model = int(np.argmax(resp_mod))
         if force_model is not None:
@@ -394,8 +382,35 @@ class OnlineLoop:
         self.q.append(q_chos)
 
 
+# ---------------------------------------------------------------------- small host-side pieces both loops use (offline_loop imports them)
 def _np(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)
+
+
+def _log_trans(transTheta, M, eps=None):
+    """log transition matrix of the leading M states from the Dirichlet pseudo-counts, rows normalised over M + 1 columns
+    (GPI_HDP.py:1188 and its repeats).  quirk: some of the reference's copies add 1e-5 inside the logarithm and some do not -
+    every caller passes its own (offline_loop.py, GPI_HDP.reload_model_from_labels, include_sample)."""
+    tt = _np(transTheta)
+    norm = np.sum(np.exp(_digamma(tt[:M, :M + 1])), axis=1)
+    return _digamma(tt[:M, :M]) - np.log(norm if eps is None else norm + eps)[:, None]
+
+
+def _by_size(resp):
+    """Clusters largest first: (the permutation, the one-hot table resp with its columns permuted)."""
+    order = torch.argsort(torch.sum(resp, dim=0), descending=True)
+    return order, resp[:, order]
+
+
+def _tables(labels, pairs, K):
+    """One-hot host tables resp [N, K], respPair [N, K, K] of a hard assignment (labels [N], flat pair indexes [N]: host tensors
+    or arrays) - where OfflineLoop._one_hot_tables and include_sample both end."""
+    N = labels.shape[0]
+    resp = torch.zeros((N, K), dtype=f64)
+    resp[torch.arange(N), torch.as_tensor(labels)] = 1.0
+    respPair = torch.zeros((N, K * K), dtype=f64)                             # the reference's table is float32: 0 / 1 either way
+    respPair[torch.arange(N), torch.as_tensor(pairs)] = 1.0
+    return resp, respPair.reshape(N, K, K)
 
 
 # phase timing of include_sample (tools/time_online.py --phases): HGP_ONLINE_TIMING=1 synchronises at every phase boundary
