@@ -157,6 +157,19 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         gp._def_diag_key, gp._def_diag = (id(gp.Sigma_def), id(gp.Gamma_def)), True
         return gp
 
+    def fit_kernels(self, y_trains, lead=0):
+        """The kernel hyper-parameters a cluster born on each of the given beats would start with: what
+        GPI_model.fit_kernel_params stores after the fit of GPI.py:610-770 under bound_sigma_def - (outputscale, 1.2, noise clamped
+        into the bounds) per beat, [n,3] - from ONE batched device fit (kernel_fit.fit_kernels_batch) instead of one host-driven
+        fit per beat.  y_trains [n,T] or [n,T,n_outputs] (lead selects the output).  The model is not modified: use it to choose
+        fixed_theta or to inspect candidate beats."""
+        from .kernel_fit import fit_kernels_batch
+        y = y_trains.detach().cpu().numpy() if torch.is_tensor(y_trains) else np.asarray(y_trains, dtype=np.float64)
+        y = y[:, :, lead] if y.ndim == 3 else y.reshape(-1, self.x_basis_ini.shape[0])
+        lo, hi = self.bound_sigma_def
+        theta, _ = fit_kernels_batch(self.x_basis_ini.reshape(-1), y, (lo, hi), device=self.device)
+        return np.stack([theta[:, 0], np.full(len(theta), 1.2), np.clip(theta[:, 2], lo, hi)], axis=1)
+
     def create_wp_sys_default(self):
         """GPI_HDP.py:573-583: a fresh time-warp fitter with the default options (one per lead and cluster)."""
         from .amtgp_warping_system import Warping_system

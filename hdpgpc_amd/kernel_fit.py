@@ -12,6 +12,9 @@ The value and the gradient of the log-likelihood come from the a10 kernels (Gram
 hgp_lml_grad_f64); only four scalars per iteration reach the host.  gpytorch is absent in the build container, so this
 step has no golden vector ("parity unpinned"): tests check it against a NumPy restatement of the same
 optimiser on the oracle's log-likelihood, and that the bounds hold and the loss settles.
+
+fit_kernels_batch runs the same optimisation for B segments at once with every iteration on the device
+(hgp_kernel_fit_steps_f64, include/hdpgpc_hip_fit.h): nothing returns to the host but one status vector per chunk of iterations.
 """
 import math
 
@@ -83,3 +86,55 @@ def fit_kernel_adam(x, y, noise_bounds, device="cuda", max_iter=4000, lr=0.1, mi
             break
     theta = (_softplus(p[2]), _softplus(p[3]), lo + (hi - lo) * _sigmoid(p[0]), p[1])
     return (theta, np.asarray(losses)) if return_trace else theta
+
+
+def theta_of_state(state, noise_bounds):
+    """theta [B,4] = (outputscale, lengthscale, noise, mean), as fit_kernel_adam defines them, of the raw parameters in the
+    state rows [B, FIT_STATE_DOUBLES] of ops.kernel_fit_steps (host arrays)."""
+    nb = np.asarray(noise_bounds, dtype=np.float64).reshape(-1, 2)
+    return np.array([(_softplus(p[2]), _softplus(p[3]), lo + (hi - lo) * _sigmoid(p[0]), p[1])
+                     for p, (lo, hi) in zip(np.asarray(state, dtype=np.float64).tolist(), nb.tolist())]).reshape(-1, 4)
+
+
+def fit_kernels_batch(x, Y, noise_bounds, device="cuda", max_iter=4000, lr=0.1, min_iter=1000, chunk=250, return_trace=False,
+                      check=True, return_state=False):
+    """fit_kernel_adam for B segments Y [B,T] (numpy or a device tensor) in one batch on the device (ops.kernel_fit_steps): the
+    iterations run in calls of `chunk`, nothing returns to the host inside a call, and the status of the fits is read once per
+    call to stop when none is running.  x [T] or [B,T]; noise_bounds one pair or [B,2].
+    Returns theta [B,4] = (outputscale, lengthscale, noise, mean) and n_iter [B] (numpy); with return_trace also a list of each
+    fit's losses, trimmed to its n_iter; with return_state also (state, status) as the device left them.
+    A fit that failed (K not positive-definite, or a non-finite value) keeps the parameters of its last good iteration and does
+    not disturb the others; check=True raises torch.linalg.LinAlgError naming the failed fits."""
+    Yd = ops.to_dev(Y, f64, device)
+    if Yd.dim() != 2:
+        raise ValueError("fit_kernels_batch: Y must be [B, T]")
+    B, T = Yd.shape
+    nb = np.ascontiguousarray(np.broadcast_to(np.asarray(noise_bounds, dtype=np.float64).reshape(-1, 2), (B, 2)))
+    if B == 0:
+        out = (np.zeros((0, 4)), np.zeros(0, dtype=np.int64))
+        out += ([],) if return_trace else ()
+        return out + ((None, None),) if return_state else out
+    xd = ops.to_dev(x, f64, device)
+    xd = xd.reshape(B, T) if xd.numel() == B * T and xd.dim() == 2 else xd.reshape(-1)
+    bd = ops.to_dev(nb, f64, device)
+    state = torch.zeros((B, ops._ffi.FIT_STATE_DOUBLES), dtype=f64, device=Yd.device)
+    status = torch.zeros(B, dtype=torch.int32, device=Yd.device)
+    losses = torch.zeros((B, max_iter), dtype=f64, device=Yd.device) if return_trace else None
+    done, chunk = 0, max(int(chunk), 1)
+    while done < max_iter:
+        n = min(chunk, max_iter - done)
+        ops.kernel_fit_steps(xd, Yd, bd, state, status, n, lr=lr, min_iter=min_iter, max_iter=max_iter, loss_out=losses)
+        done += n
+        if not bool((status == 0).any()):        # the one read per call
+            break
+    st_h, status_h = state.cpu().numpy(), status.cpu().numpy()
+    if check and (status_h < 0).any():
+        bad = np.nonzero(status_h < 0)[0].tolist()
+        raise torch.linalg.LinAlgError(f"kernel fit: fits {bad} failed (status {status_h[bad].tolist()}: -1 = K(theta) is not "
+                                       "positive-definite, -2 = a non-finite value)")
+    n_iter = st_h[:, 12].astype(np.int64)
+    out = (theta_of_state(st_h, nb), n_iter)
+    if return_trace:
+        lh = losses.cpu().numpy()
+        out += ([lh[b, :n_iter[b]].copy() for b in range(B)],)
+    return out + ((state, status),) if return_state else out

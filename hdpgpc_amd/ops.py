@@ -569,6 +569,50 @@ def sample_states(mean, cov, z, cov_idx=None, jitter_rel=0.0, check=True):
     return out, info
 
 
+_fit_ws = _StreamWorkspace()       # hgp_kernel_fit_steps_f64
+
+
+def kernel_fit_release():
+    """Drop the cached workspaces of kernel_fit_steps (the memory returns to torch's allocator once queued calls have finished)."""
+    _fit_ws.release()
+
+
+def kernel_fit_ws_doubles(B, T):
+    """HGP_FIT_WS_DOUBLES of include/hdpgpc_hip_fit.h."""
+    return 2 * B * T * T + B
+
+
+def kernel_fit_steps(x, Y, bounds, state, status, n_steps, lr=0.1, min_iter=1000, max_iter=4000, loss_out=None):
+    """8f-2, batched (hgp_kernel_fit_steps_f64): advance every running fit of Y [B,T] by up to n_steps Adam iterations, in place
+    in state [B, FIT_STATE_DOUBLES] / status [B] (int32; all zeros = the start of a fit).  x [T] (one grid for all) or [B,T];
+    bounds [B,2] = the noise interval of each fit; loss_out (optional) [B, ld]: iteration it writes column it - 1.
+    Nothing is synchronised and nothing returns to the host."""
+    Y = _dev64(Y, "Y")
+    if Y.dim() != 2:
+        raise ValueError("kernel_fit_steps: Y must be [B, T]")
+    B, T = Y.shape
+    x = _dev64(x, "x")
+    if tuple(x.shape) not in ((T,), (B, T)):
+        raise ValueError("kernel_fit_steps: x must be [T] or [B, T]")
+    bounds, state = _dev64(bounds, "bounds"), _dev64(state, "state")
+    if tuple(bounds.shape) != (B, 2) or tuple(state.shape) != (B, _ffi.FIT_STATE_DOUBLES):
+        raise ValueError("kernel_fit_steps: bounds must be [B, 2] and state [B, FIT_STATE_DOUBLES]")
+    if not (torch.is_tensor(status) and status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == B):
+        raise TypeError("kernel_fit_steps: status must be a contiguous int32 tensor [B] on the GPU")
+    ld = 0
+    if loss_out is not None:
+        loss_out = _dev64(loss_out, "loss_out")
+        if loss_out.dim() != 2 or loss_out.shape[0] != B:
+            raise ValueError("kernel_fit_steps: loss_out must be [B, ld]")
+        ld = loss_out.shape[1]
+    if B == 0 or n_steps == 0:
+        return
+    ws, stream = _fit_ws.get(Y.device, kernel_fit_ws_doubles(B, T))
+    _ffi.check(_ffi.lib.hgp_kernel_fit_steps_f64(_ptr(x), 0 if x.dim() == 1 else T, _ptr(Y), T, B, _ptr(bounds), float(lr), int(n_steps),
+                                                 int(min_iter), int(max_iter), _ptr(state), _ptr(status),
+                                                 _ptr(loss_out) if ld else None, ld, _ptr(ws), stream), "kernel_fit_steps")
+
+
 def rts_chain(J, P, AM, M, Cv):
     """Sequential part of the RTS smoother for all steps in one launch (in place on M [n,T] and Cv [n,T,T]); T <= 96."""
     n, T = M.shape[0], Cv.shape[1]
