@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _ffi, ops
-from .member_step import Chain, finish_desc, gather_desc, member_step, shared_buffers, upload_descs
+from .member_step import Chain, finish_desc, gather_desc, member_step, shared_buffers, upload_descs, ws_size
 
 f64 = torch.float64
 UNROLL = 8                                   # member steps per captured hipGraph
@@ -107,7 +107,7 @@ def _run_group(jobs):
     chs = []
     for c, j in enumerate(jobs):
         ch = Chain.from_model(j.gp, len(j.gp.f_star) + len(j.rest))
-        ch.ws = torch.empty(6 * T * T + 2 * T, dtype=f64, device=dev)     # gathered previous state
+        ch.ws = torch.empty(ws_size(T), dtype=f64, device=dev)            # gathered previous state
         ch.bad = torch.zeros(2, dtype=torch.int32, device=dev)            # [MNIW updates skipped, first step whose filter failed]
         ch.sync = torch.zeros(1, dtype=torch.int32, device=dev)           # inter-block counter of the finish kernel
         # observations of the run; the step reads row (pos - y_row0) inside its gather kernel

@@ -18,6 +18,26 @@ f64 = torch.float64
 _p = ops._ptr
 _STACKS = ("A", "G", "C", "S", "Psm", "P", "F", "Fsm")          # order of hgp_chain_gather_desc.st
 _LISTS = {"A": "A", "G": "Gamma", "C": "C", "S": "Sigma", "Psm": "cov_f_sm", "P": "cov_f", "F": "f_star", "Fsm": "f_star_sm"}
+# a chain's gathered previous state `ws` (written by the gather kernel): six T x T matrices, then two T-vectors
+_WS = ("A", "G", "C", "S", "Psm", "c0", "m0", "Fsm")
+_WS_MATS = 6
+
+
+def ws_size(T):
+    return _WS_MATS * T * T + (len(_WS) - _WS_MATS) * T
+
+
+def ws_offset(name, T):
+    """Where `name` of _WS starts in a chain's ws (doubles)."""
+    i = _WS.index(name)
+    return i * T * T if i < _WS_MATS else _WS_MATS * T * T + (i - _WS_MATS) * T
+
+
+def ws_view(ws, name, T):
+    o = ws_offset(name, T)
+    return ws[o:o + T * T].view(T, T) if name in _WS[:_WS_MATS] else ws[o:o + T]
+
+
 # T <= 128: the right-hand sides ride the inversions; 128 < T <= 256: Z rhs is one more list level behind each of them
 LV_RHS4, LV_RHS2 = 10, 11
 
@@ -100,12 +120,9 @@ class Chain:
         where the step's own buffers come from (a pool hands out slices of its arena); zeroed.  Needs self.ws."""
         T = self.T
         riding = T <= _ffi.MAX_T_WAVE
-        tt = T * T
         dev = self.ws.device
         new = alloc or (lambda *shape: torch.zeros(shape, dtype=f64, device=dev))
-        ws = self.ws
-        A, G, C, S, Psm, c0 = (ws[i * tt:(i + 1) * tt].view(T, T) for i in range(6))
-        m0, Fsm = ws[6 * tt:6 * tt + T], ws[6 * tt + T:]
+        A, G, C, S, Psm, c0, m0, Fsm = (ws_view(self.ws, k, T) for k in _WS)
         X4, RH4, Z4, Y4 = (shared[k][c] for k in ("X4", "RH4", "Z4", "Y4"))   # [P, Sk, R0', R1'], riding RHS, Z, Z rhs
         S__, S_, Zs, Y3 = (shared[k][c] for k in ("S__", "S_", "Zs", "Y3"))
         part = new(2, T, T)
@@ -219,7 +236,7 @@ def member_step(levels, shared, gdev, fdev, lo, hi, T, gather_first=True, no_smo
     for l in range(4, 8):
         levels.run(l, lo, hi)
     for ch in no_smoother:
-        ch.bufs["f_sm_prev"].copy_(ch.ws[6 * T * T + T:6 * T * T + 2 * T])
+        ch.bufs["f_sm_prev"].copy_(ws_view(ch.ws, "Fsm", T))
     levels.run(8, lo, hi)
     if riding:
         ops.chol_inverse_rhs(sh("S__"), sh("Zs"), sh("S_"), sh("Y3"), sh("i2"), rhs_trans=True, add_diag=1e-8)

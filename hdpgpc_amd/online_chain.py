@@ -22,15 +22,34 @@ Nothing a candidate computes feeds another one.  Here every cluster model of a l
   MNIW update and the previous row is left alone (finish flag 4).
 """
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import _ffi, ops
 from .GPI_model import LOG2PI
-from .member_step import Chain, finish_desc, gather, gather_desc, member_step, shared_buffers, upload_descs
+from .member_step import (Chain, finish_desc, gather, gather_desc, member_step, shared_buffers, upload_descs, ws_offset, ws_size,
+                          ws_view)
 
 f64 = torch.float64
+# every cluster with the beat added, in CLUSTER order: est [M] device (estimate_new's score), cols [T_all, M] device (the
+# candidates' latent-transition columns), lds [M] host floats (return_LDS_param_likelihood); the would-be NEW cluster's single
+# latent-transition score (device scalar) and parameter likelihood (host float), None when `extra` was not taken
+Candidates = namedtuple("Candidates", "est cols lds extra_lat extra_lds")
+
+
+def _defs_diagonal(g):
+    """Are the model's default scales (the MNIW priors' Sigma_def, Gamma_def) diagonal?"""
+    if getattr(g, "_def_diag_key", None) == (id(g.Sigma_def), id(g.Gamma_def)):
+        return g._def_diag
+    return all(bool(torch.equal(s_, torch.diag(torch.diagonal(s_)))) for s_ in (g.Sigma_def, g.Gamma_def))
+
+
+def _copy_rows(rows, src, dbuf, item, n):
+    """One more block of the copy-list table `rows`: n doubles from byte address src[i] to item item[i] (n doubles each) of dbuf."""
+    src, item = np.atleast_1d(np.asarray(src, dtype=np.int64)), np.atleast_1d(np.asarray(item, dtype=np.int64))
+    rows.append(np.stack([src, dbuf.data_ptr() + item * (8 * n), np.full(len(src), n, dtype=np.int64)], axis=1))
 
 
 class _LevelLists:
@@ -75,7 +94,7 @@ class _LevelLists:
 
 
 class _Slot:
-    __slots__ = ("g", "ch", "rows", "N", "ini_noise", "def_diag", "bad0")
+    __slots__ = ("g", "ch", "rows", "N", "def_diag", "bad0")
 
 
 class OnlinePool:
@@ -94,7 +113,7 @@ class OnlinePool:
         T, dev = self.T, self.device
         new = lambda *shape: torch.zeros(shape, dtype=f64, device=dev)            # noqa: E731
         self.cap = cap
-        self.WS = 6 * T * T + 2 * T
+        self.WS = ws_size(T)
         self.ws_all = new(cap, self.WS)
         self.shared = shared_buffers(cap, T, dev, work=True)
         self.bad_all = torch.zeros((cap, 2), dtype=torch.int32, device=dev)      # committed steps
@@ -131,7 +150,7 @@ class OnlinePool:
         ch.ws = self.ws_all[c]
         ch.bad, ch.sync = self.bad_all[c], self.sync_all[c:c + 1]
         ch.Y, ch.y_row0 = self.ybuf, -1
-        arena, used = self.arena[c], [0]
+        arena, used = self.arena[c], [0]                       # build_lists must stay inside it (asserted below)
         arena.zero_()
 
         def alloc(*shape):
@@ -141,11 +160,11 @@ class OnlinePool:
             return out
 
         ch.build_lists(self.shared, c, alloc)
-        T, tt = self.T, self.T * self.T
-        Cw = ch.ws[2 * tt:3 * tt].view(T, T)
+        assert used[0] <= self.ARENA, "online pool: the step buffers of Chain.build_lists outgrew the slot's arena"
+        Cw = ws_view(ch.ws, "C", self.T)
         ch.lv[6].add(Cw, ch.bufs["f_post"], self.est_mean[c])                # C_last f_post: the mean estimate_new scores against
         lvm = ops.GemmList(self.device)                                      # C_last f_last: the mean the beat is scored against
-        lvm.add(Cw, ch.ws[6 * tt:6 * tt + T], self.mean_last[c])
+        lvm.add(Cw, ws_view(ch.ws, "m0", self.T), self.mean_last[c])
         self.lv_mean_last = len(ch.lv)                                       # the pool's own level, behind the step's
         self.lists.set_slot(c, ch.lv + [lvm])
         self._base[c] = ch.stack_ptrs()
@@ -169,6 +188,11 @@ class OnlinePool:
         same = lambda a, b: a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape) or bool(torch.equal(a, b))   # noqa: E731
         return same(g.f_star[-1], g.f_star_sm[-1]) and same(g.cov_f[-1], g.cov_f_sm[-1])
 
+    def holds(self, g):
+        """Does a slot of this pool carry the model g?"""
+        c = getattr(g, "_slot", None)
+        return c is not None and c < len(self.slots) and self.slots[c].g is g
+
     def adopt(self, g):
         """Move the model's per-step lists into a slot's stacks (the model keeps reading them through views)."""
         if len(self.slots) == self.cap:
@@ -177,11 +201,7 @@ class OnlinePool:
         sl = _Slot()
         sl.g, sl.N, sl.rows = g, L - 1, max(8, 2 * L)
         sl.ch = Chain.from_model(g, sl.rows)
-        sl.ini_noise = None                                   # log_sq_error's `first` inflation: on the device (self.ini_noise_all)
-        if getattr(g, "_def_diag_key", None) == (id(g.Sigma_def), id(g.Gamma_def)):
-            sl.def_diag = g._def_diag
-        else:
-            sl.def_diag = all(bool(torch.equal(s_, torch.diag(torch.diagonal(s_)))) for s_ in (g.Sigma_def, g.Gamma_def))
+        sl.def_diag = _defs_diagonal(g)
         sl.bad0 = 0
         self._bind(sl)
         self._rebind_lists(sl, float(g.internal_params.n0))
@@ -224,12 +244,22 @@ class OnlinePool:
                     gather_first=gather_first, no_smoother=() if dry else [sl.ch for sl in self.slots[lo:hi]])
 
     # ------------------------------------------------------------------ the beat under the clusters' last states
-    def begin_beat(self, y):
-        """Gather every cluster's last state (row pos of its stacks) and score the beat y [T] under it: log_sq_error(x, y, i=-1)
-        of GPI_HDP.py:1973 for all clusters in three launches.  Returns (scores, LAPACK infos) in SLOT order [M] (device); the
-        gathered state stays valid for candidates() of the same beat."""
+    def _score_gathered(self, mean, add=None):
+        """The beat in ybuf against (mean[c], the gathered Sigma_last of slot c) for every slot -> (scores, LAPACK infos) [M]."""
         M, T = len(self.slots), self.T
-        tt = T * T
+        ar = np.arange(M, dtype=np.int32)
+        quad, _, info = ops.score_each(self.ybuf.expand(M, T).contiguous(), mean, self.ws_all[0, ws_offset("S", T):], ar, ar, add,
+                                       strides=(T, self.WS))
+        return -0.5 * quad - 0.5 * T * LOG2PI, info
+
+    def begin_beat(self, y, models):
+        """Gather every cluster's last state (row pos of its stacks) and score the beat y [T] under it: log_sq_error(x, y, i=-1)
+        of GPI_HDP.py:1973 for all clusters in three launches.  models: the lead's cluster list - the one place where the
+        slot <-> cluster permutation of the beat is built; every result of this beat is in that CLUSTER order.  Returns
+        (scores [M] device, their LAPACK infos - any order); the gathered state stays valid for candidates() of the same beat."""
+        M, T = len(self.slots), self.T
+        self.slot_of = [g._slot for g in models]                               # slot of every cluster
+        self.slot_dev = ops.to_dev(self.slot_of, torch.int64, self.device)
         for sl in self.slots:
             if sl.N + 2 > sl.rows:
                 self._more_rows(sl)
@@ -238,45 +268,49 @@ class OnlinePool:
             self._prepare()
         gather(self.gdev, 0, M, T)
         self.lists.run(self.lv_mean_last, 0, M)                # mean_last = C_last f_last
-        ar = np.arange(M, dtype=np.int32)
-        quad, _, info = ops.score_each(self.ybuf.expand(M, T).contiguous(), self.mean_last, self.ws_all[0, 3 * tt:], ar, ar, None,
-                                       strides=(T, self.WS))
-        return -0.5 * quad - 0.5 * T * LOG2PI, info
+        sc, info = self._score_gathered(self.mean_last)
+        return sc[self.slot_dev], info
 
     # ------------------------------------------------------------------ candidates
-    def candidates(self, t_new, q_lat_cols, indexes, extra=None):
-        """Every cluster with the beat of begin_beat(y) added (dry run).  q_lat_cols [T_all, M']: the clusters' current latent-transition
-        columns in SLOT order; indexes[c] = member segment ids of slot c.  Returns
-        (est [M] device: estimate_new's score, cols [T_all, M] device: the candidates' latent-transition columns,
-         lds [M] host floats: return_LDS_param_likelihood of the candidates).
-        extra (optional): the would-be NEW cluster (one member, GPI_HDP.py:1990-1996) - its single latent-transition score and its two
-        parameter likelihoods ride the same batched a8 / a9 calls; two more return values then: (its a8 score - device scalar, its
-        return_LDS_param_likelihood - host float)."""
-        M, T = len(self.slots), self.T
-        tt = T * T
+    def candidates(self, t_new, q_lat_cols, extra=None):
+        """Every cluster with the beat of begin_beat(y, models) added (dry run) -> Candidates, in the cluster order of `models`.
+        q_lat_cols [T_all, M]: the clusters' current latent-transition columns in that order.  extra (optional): the would-be
+        NEW cluster (one member, GPI_HDP.py:1990-1996) - its single latent-transition score and its two parameter likelihoods
+        ride the same batched a8 / a9 calls when there is room behind the last slot and it is the plain case (else the
+        result's extra_* are None: the caller's job)."""
+        M = len(self.slots)
         if extra is not None and (M >= self.cap or extra.N != 1 or not extra._dyn_prior()):
-            extra = None                                        # no room behind the last slot (or not the plain case): the caller's job
+            extra = None
+        est, info = self._dry_step()
+        table, nl, nm, diag = self._copy_table(extra)
+        lat, lds, extra_lds = self._score_copies(table, nl, nm, diag, info)
+        slot_cols = q_lat_cols[:, ops.to_dev(np.argsort(self.slot_of), torch.int64, self.device)]      # cluster of every slot
+        cols = self._candidate_columns(slot_cols, lat, t_new)
+        return Candidates(est[self.slot_dev], cols[:, self.slot_dev], [float(lds[c]) for c in self.slot_of],
+                          None if extra is None else lat[3 * M], extra_lds)
+
+    def _dry_step(self):
+        """The member step of every slot as a dry run on the state begin_beat gathered, and estimate_new: the beat against
+        (C_last f_post, Sigma_last), `first` inflation for one-member clusters.  Reads row N of every stack; writes row N + 1."""
+        M = len(self.slots)
         self.badc_all[:M].zero_()
-        self._step(0, M, dry=True, gather_first=False)               # begin_beat(y) of this beat gathered the state
-        # estimate_new: the beat against (C_last f_post, Sigma_last), `first` inflation for one-member clusters
-        Y = self.ybuf.expand(M, T).contiguous()
+        self._step(0, M, dry=True, gather_first=False)
         add = self.ini_noise_all[:M] * ops.to_dev(np.array([1.0 if sl.N == 1 else 0.0 for sl in self.slots]), f64, self.device)
-        ar = np.arange(M, dtype=np.int32)
-        quad, _, info = ops.score_each(Y, self.est_mean, self.ws_all[0, 3 * tt:], ar, ar, add, strides=(T, self.WS))
-        est = -0.5 * quad - 0.5 * T * LOG2PI
-        # a8 / a9 inputs by ONE copy-list launch.  Rows: N = members so far = index of the last row; N + 1 = the dry run's row
+        return self._score_gathered(self.est_mean, add)
+
+    def _copy_table(self, extra):
+        """The copy-list table that lays out the a8 / a9 inputs: three a8 items and two a9 items per slot, extra's one and two
+        behind them.  Rows read per slot (N = members so far = index of the last row): 1, N - 1, N, the dry run's N + 1, and
+        the step's f_post / f_sm_prev / P_sm_prev.  Returns (table [rows, 3] host, a8 items, a9 items, all default scales diagonal)."""
+        M, T, tt = len(self.slots), self.T, self.T * self.T
         N = np.array([sl.N for sl in self.slots], dtype=np.int64)
         one = N == 1
-        base, bufp = self._base[:M], self._bufp[:M]
+        base = self._base[:M]
         iA, iG, iC, iS, iPsm, iP, iF, iFsm = range(8)
         row = lambda k, r, n: base[:, k] + r * (8 * n)                           # noqa: E731  (byte address of a stack row)
-        f_post, f_smp, P_smp = bufp[:, 0], bufp[:, 1], bufp[:, 2]
-        src, dst, cnt = [], [], []
-
-        def put(s, dbuf, j, n):
-            src.append(s), dst.append(dbuf.data_ptr() + (np.arange(M, dtype=np.int64) * (dbuf.shape[0] // self.cap) + j) * (8 * n))
-            cnt.append(np.full(M, n, dtype=np.int64))
-
+        f_post, f_smp, P_smp = self._bufp[:M].T
+        rows = []
+        put = lambda s, dbuf, j, n: _copy_rows(rows, s, dbuf, np.arange(M) * (dbuf.shape[0] // self.cap) + j, n)    # noqa: E731
         # member 0: cur = prev = row 1, cov = row 1 (the re-smoothed one when it is also the previous member), par = the NEW row
         f1 = np.where(one, f_smp, row(iFsm, 1, T))
         put(f1, self.LF_cur, 0, T), put(f1, self.LF_prev, 0, T)
@@ -300,31 +334,27 @@ class OnlinePool:
             Ae, Ge, Ce, Se = (m_.contiguous() for m_ in (e.A[-1], e.Gamma[-1], e.C[-1], e.Sigma[-1]))
             defs = [m_.contiguous() for m_ in (e.C_def, e.Sigma_def, e.A_def, e.Gamma_def)]
             self._extra_keep = (fs, cs, Ae, Ge, Ce, Se, defs)
-            one_ = lambda t, buf, j, n: (src.append(np.array([t.data_ptr()], dtype=np.int64)),                       # noqa: E731
-                                         dst.append(np.array([buf.data_ptr() + j * 8 * n], dtype=np.int64)), cnt.append(np.array([n], dtype=np.int64)))
-            one_(fs, self.LF_cur, nl, T), one_(fs, self.LF_prev, nl, T), one_(Ae, self.LA, nl, tt), one_(Ge, self.LG, nl, tt), one_(cs, self.LC, nl, tt)
-            one_(Ce, self.MN_M, nm, tt), one_(Se, self.MN_S, nm, tt), one_(Ae, self.MN_M, nm + 1, tt), one_(Ge, self.MN_S, nm + 1, tt)
-            one_(defs[0], self.MN_mean, nm, tt), one_(defs[1], self.MN_scale, nm, tt)
-            one_(defs[2], self.MN_mean, nm + 1, tt), one_(defs[3], self.MN_scale, nm + 1, tt)
+            for t_, buf, j, n in ((fs, self.LF_cur, nl, T), (fs, self.LF_prev, nl, T), (Ae, self.LA, nl, tt), (Ge, self.LG, nl, tt),
+                                  (cs, self.LC, nl, tt), (Ce, self.MN_M, nm, tt), (Se, self.MN_S, nm, tt), (Ae, self.MN_M, nm + 1, tt),
+                                  (Ge, self.MN_S, nm + 1, tt), (defs[0], self.MN_mean, nm, tt), (defs[1], self.MN_scale, nm, tt),
+                                  (defs[2], self.MN_mean, nm + 1, tt), (defs[3], self.MN_scale, nm + 1, tt)):
+                _copy_rows(rows, t_.data_ptr(), buf, j, n)
             nl, nm = nl + 1, nm + 2
-            if getattr(e, "_def_diag_key", None) == (id(e.Sigma_def), id(e.Gamma_def)):
-                diag = diag and e._def_diag
-            else:
-                diag = diag and all(bool(torch.equal(s_, torch.diag(torch.diagonal(s_)))) for s_ in (e.Sigma_def, e.Gamma_def))
-        table = np.stack([np.concatenate(src), np.concatenate(dst), np.concatenate(cnt)], axis=1)
-        tdev = ops.to_dev(table, torch.int64, self.device)
-        ops.copy_list(tdev, table.shape[0], tt)
+            diag = diag and _defs_diagonal(e)
+        return np.concatenate(rows), nl, nm, diag
+
+    def _score_copies(self, table, nl, nm, diag, info):
+        """The copy-list launch, the batched a8 call (nl items) and a9 call (nm items), and ONE host round trip for everything
+        the loop branches on (info: estimate_new's statuses ride it).  Reads only what _copy_table laid out.  Returns
+        (lat [nl] device, lds [M] host in slot order, extra's lds or None)."""
+        M, T = len(self.slots), self.T
+        ops.copy_list(ops.to_dev(table, torch.int64, self.device), table.shape[0], T * T)
         lat, info_l = ops.lat_error(self.LF_cur[:nl], self.LF_prev[:nl], self.LA[:nl], self.LG[:nl], self.LC[:nl])
         lat = lat - 0.5 * T * LOG2PI
-        if diag:
-            mn, info_m = ops.mniw_loglik(self.MN_M[:nm], self.MN_S[:nm], self.MN_mean[:nm], None, self.MN_scale[:nm], scale_is_diagonal=True)
-        else:
-            mn, info_m = ops.mniw_loglik(self.MN_M[:nm], self.MN_S[:nm], self.MN_mean[:nm], None, self.MN_scale[:nm], scale_is_diagonal=False)
+        mn, info_m = ops.mniw_loglik(self.MN_M[:nm], self.MN_S[:nm], self.MN_mean[:nm], None, self.MN_scale[:nm], scale_is_diagonal=diag)
         lds_dev = torch.sum(mn.view(nm // 2, 2), dim=1) / T * 100.0
-        # one host round trip for everything the loop branches on
         flat = torch.cat([lds_dev, info.to(f64), info_l.to(f64), info_m.to(f64), self.badc_all[:M].reshape(-1).to(f64)]).cpu().numpy()
         nx = nm // 2
-        lds = flat[:M]
         if flat[nx:nx + M + nl + nm].any():       # score [M] / a8 [nl] / a9 [nm] infos
             bad = int(np.nonzero(flat[nx:nx + M + nl + nm])[0][0])
             what = "log_sq_error" if bad < M else ("log_lat_error" if bad < M + nl else "log_likelihood_MNIW")
@@ -332,22 +362,23 @@ class OnlinePool:
         badc = flat[nx + M + nl + nm:].reshape(M, 2)
         if badc[:, 1].any():
             raise torch.linalg.LinAlgError("posterior / backwards_pair: the input is not positive-definite (online candidate step)")
-        # the candidates' columns: the cluster's own column with (up to) three entries replaced
-        cols = q_lat_cols.clone()
+        return lat, flat[:M], float(flat[M]) if nx > M else None
+
+    def _candidate_columns(self, slot_cols, lat, t_new):
+        """The candidates' columns (slot order): the cluster's own column slot_cols[:, c] with (up to) three entries replaced by
+        the a8 scores lat[3 c : 3 c + 3] - rows = segment ids of member 0, of member N - 1 (N >= 2) and t_new."""
+        cols = slot_cols.clone()
         rr, cc, vv = [], [], []
         for c, sl in enumerate(self.slots):
-            idx = indexes[c]
+            idx = sl.g.indexes
             rr += [idx[0], t_new]
             cc += [c, c]
             vv += [3 * c, 3 * c + 2]
             if sl.N >= 2:
                 rr.append(idx[sl.N - 1]), cc.append(c), vv.append(3 * c + 1)
-        dev = self.device
-        ix = ops.to_dev(np.array([rr, cc, vv]), torch.int64, dev)
+        ix = ops.to_dev(np.array([rr, cc, vv]), torch.int64, self.device)
         cols[ix[0], ix[1]] = lat[ix[2]]
-        if extra is not None:
-            return est, cols, lds, lat[3 * M], float(flat[M])
-        return est, cols, lds
+        return cols
 
     # ------------------------------------------------------------------ commit
     @staticmethod
@@ -414,13 +445,3 @@ class OnlinePool:
                 print("Alg error matrix ill conditioned.")
             g.internal_params.n0 -= 1.0
             g.observation_params.n0 -= 1.0
-
-
-class CandidateView:
-    """What the one-sample bound asks of a candidate cluster (offline_loop.full_LDS_elbo): its MNIW parameter likelihood."""
-
-    def __init__(self, value):
-        self._v = float(value)
-
-    def lds_param_likelihood_value(self):
-        return self._v

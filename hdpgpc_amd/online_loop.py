@@ -11,11 +11,14 @@ Host orchestration over the same kernels as the offline loop; per beat the devic
   backwards_pair, bayesian_new_params) and the switching-variable messages over the whole history (ops.hmm_messages).
 ``with_warp=True`` (the time-warp fit of every beat) and ``classify=True`` (no caller in the reference) are not built.
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 from scipy.special import digamma as _digamma
 
-from . import ops
+from . import online_chain, ops
+from .online_chain import Candidates
 
 f64 = torch.float64
 
@@ -26,10 +29,7 @@ class OnlineLoop:
     def variational_local_terms(self, q, transTheta=None, startTheta=None, liks=None, classify=False):
         """GPI_HDP.py:586-630: hard state / pair assignments of the whole history from the score matrix q [T, K, D] (device).
         Returns (resp one-hot [T,K] host, log resp of the LAST row (numpy), respPair one-hot [T,K,K] host, None)."""
-        M = self.M
-        startTheta = self.startTheta if startTheta is None else startTheta
-        st = _np(startTheta)
-        startPi = torch.as_tensor(_digamma(st[:M]) - _digamma(np.sum(st[:M + 1])), dtype=f64)
+        startPi = self._start_pi(self.startTheta if startTheta is None else startTheta)
         q = q.clone()
         if liks is not None:
             q[-1] = q[-1] + torch.as_tensor(np.asarray(liks, dtype=np.float64), device=q.device)[:, None]
@@ -38,6 +38,11 @@ class OnlineLoop:
         resp, respPair = self._one_hot_tables(fmsg, bmsg, pair)
         last = torch.log(fmsg[-1] * bmsg[-1]).cpu().numpy()
         return resp, last - np.max(last) if np.isfinite(np.max(last)) else last, respPair, None
+
+    def _start_pi(self, startTheta):
+        """Expected log start probabilities of the M clusters under the Dirichlet pseudo-counts (GPI_HDP.py:610)."""
+        st, M = _np(startTheta), self.M
+        return torch.as_tensor(_digamma(st[:M]) - _digamma(np.sum(st[:M + 1])), dtype=f64)
 
     def estimate_new(self, t, gpmodel, x_train, y, h=1.0):
         """GPI_HDP.py:2830-2842: the segment's score under the state the model would have after absorbing it."""
@@ -63,11 +68,10 @@ class OnlineLoop:
             return None
         pools = self.__dict__.setdefault("_pools", {})
         if ld not in pools:
-            from .online_chain import OnlinePool
-            pools[ld] = OnlinePool(xb.shape[0], self.device, self.annealing_def)
+            pools[ld] = online_chain.OnlinePool(xb.shape[0], self.device, self.annealing_def)
         pool = pools[ld]
         for g in self.gpmodels[ld]:
-            if getattr(g, "_slot", None) is None or g._slot >= len(pool.slots) or pool.slots[g._slot].g is not g:
+            if not pool.holds(g):
                 if not pool.supports(g):
                     return None
                 pool.adopt(g)
@@ -95,10 +99,9 @@ class OnlineLoop:
         launch sequence for all of them (ops.hmm_local_terms), one host round trip.  Returns host arrays
         (labels [B, T], pair_first [B, T] - flat index into the K x K pair table, last [B, K] - log resp of the newest row,
         max-shifted as the reference's)."""
-        M, dev = self.M, self.device
+        dev = self.device
         B, N, K = Qw.shape
-        st = _np(self.startTheta)
-        startPi = torch.as_tensor(_digamma(st[:M]) - _digamma(np.sum(st[:M + 1])), dtype=f64)
+        startPi = self._start_pi(self.startTheta)
         if liks is not None:
             Qw = Qw.clone()
             Qw[:, -1, :] += ops.to_dev(np.asarray(liks, dtype=np.float64), f64, dev)[None, :]
@@ -143,11 +146,11 @@ class OnlineLoop:
         elbo_latent = lat_sum * self.dynamic_factor
         return q_bas, (elbo_lin + elbo_lds + elbo_latent) if self.hmm_switch else elbo_latent
 
-    def _eager_candidates(self, ld, t, x, y, q_lat, n_hist):
+    def _eager_candidates(self, ld, t, x, y, n_hist):
         """The candidates one by one (a copy of every cluster takes the beat: GPI_HDP.py:2040-2056) - the path for beats off the
-        basis grid; same return values as online_chain.OnlinePool.candidates, in CLUSTER order."""
+        basis grid; same result as online_chain.OnlinePool.candidates (the new cluster's own terms are left to the caller)."""
         est, cols, lds = [], [], []
-        for m, g in enumerate(self.gpmodels[ld]):
+        for g in self.gpmodels[ld]:
             cand = self.gpmodel_deepcopy(g)
             est.append(self.estimate_new(t, cand, x, y[:, [ld]], h=1.0))
             cand.include_weighted_sample(t, x, x, y[:, [ld]], 1.0)
@@ -155,12 +158,41 @@ class OnlineLoop:
             cand.bayesian_new_params(1.0)
             cols.append(cand.compute_q_lat_all(n_hist, h_ini=1.0))
             lds.append(cand.lds_param_likelihood_value())
-        return torch.stack(est), torch.stack(cols, dim=1), lds
+        return Candidates(torch.stack(est), torch.stack(cols, dim=1), lds, None, None)
 
+    # ------------------------------------------------------------------ include_sample, phase by phase (b: the beat's record)
     def include_sample(self, x_train, y, with_warp=True, force_model=None, minibatch=0, classify=False):
         """GPI_HDP.py:1906-2208.  Same decisions in the same order as the reference; what it evaluates one candidate after the
         other - the clusters with the beat added, and the local step + bound of every candidate's score table - is computed side
-        by side (online_chain.OnlinePool.candidates, _local_terms_many) before the accept / reject walk."""
+        by side (online_chain.OnlinePool.candidates, _local_terms_many) before the accept / reject walk.  One helper per phase,
+        in the reference's order; what a phase leaves for the later ones travels in the beat's record b (_begin_beat)."""
+        self._online_guards(with_warp, classify, minibatch)
+        _tick("outside")
+        b = self._begin_beat(x_train, y)
+        self._score_current(b)
+        _tick("scores")
+        if b.t > 0:
+            self._propose(b)
+            _tick("candidates")
+            self._score_tables(b)
+            _tick("local_terms")
+            self._walk_bounds(b)
+            _tick("bounds")
+        else:
+            b.q_chos, b.q_lat_chos = b.q_aux, b.q_lat
+            b.resp, b.resplog, b.respPair, _ = self.variational_local_terms(b.q_aux, self.transTheta, self.startTheta, b.liks)
+        self._apply_choice(b, force_model)
+        _tick("reorder")
+        # the members' update of this beat (GPI_HDP.py:2186-2196, after the global step there): nothing below up to that point
+        # reads the cluster models, and nothing in the update reads the HDP parameters, so its launches go out first and run
+        # under the host-side optimisation of (rho, omega); finish_commit (in _record) reads their status after it
+        committed = self._member_update(b)
+        self._global_step(b)
+        _tick("rho_omega")
+        self._record(b, committed)
+        _tick("commit")
+
+    def _online_guards(self, with_warp, classify, minibatch):
         if with_warp:
             # The reference itself cannot run this path: with one cluster (the second beat of any run) compute_warp_y's greedy
             # branch takes torch.max of an empty tensor (GPI_HDP.py:3313, liks[:-1] with M = 1) and raises RuntimeError -
@@ -175,211 +207,207 @@ class OnlineLoop:
         if not self.bayesian_params or minibatch:
             raise NotImplementedError("include_sample: only the Bayesian one-step parameter update is built (bayesian_params=True, "
                                       "minibatch=0); the reference's new_params_weighted path (GPI_HDP.py:2195) is not")
-        D, dev, ld = self.n_outputs, self.device, 0
-        _tick("outside")
+
+    def _begin_beat(self, x_train, y):
+        """Set-up: the beat joins the history; its record with the empty score tables q_aux (-inf; the history's rows from the
+        last beat) and q_lat (0), [T_all, M + 1, D] each - the last column is the would-be new cluster's."""
+        D, dev = self.n_outputs, self.device
         self._lin_memo = {}
-        t = self.T
-        self.T = self.T + 1
-        T_all = self.T
+        t, M = self.T, self.M
+        self.T = T_all = t + 1
         self.snr_norm = torch.ones((T_all, D), dtype=f64, device=dev)
-        M = self.M
-        K = M + 1
         y = self.cond_to_torch(y).reshape(-1, D)
         x = self.cond_to_torch(x_train).reshape(-1, 1)
-        liks = np.zeros(M + 1)
         self.y.append(y)
         self.x_train.append(x)
-        n_hist = torch.empty((T_all, 0))                                   # compute_q_lat_all only reads the history length
-        q_aux = torch.full((T_all, M + 1, D), -np.inf, dtype=f64, device=dev)
-        q_lat = torch.zeros((T_all, M + 1, D), dtype=f64, device=dev)
+        b = SimpleNamespace(ld=0, t=t, T_all=T_all, M=M, K=M + 1, x=x, y=y, liks=np.zeros(M + 1), pool=None, info0=None,
+                            n_hist=torch.empty((T_all, 0)),                # compute_q_lat_all only reads the history length
+                            q_aux=torch.full((T_all, M + 1, D), -np.inf, dtype=f64, device=dev),
+                            q_lat=torch.zeros((T_all, M + 1, D), dtype=f64, device=dev))
         if t > 0:
             prev = self.q[-1]
-            q_aux[:-1, :prev.shape[1], :] = prev
-        mods = self.gpmodels[ld]
-        pool = self._online_pool(ld, x) if t > 0 else None                 # the clusters as persistent chains (online_chain.py)
-        if M > 0:
-            q_lat[:, :M, ld] = torch.stack([gp.compute_q_lat_all(n_hist, h_ini=1.0) for gp in mods], dim=1)
-        info0 = None
-        if pool is not None:
-            slot_of = [g._slot for g in mods]
-            sl_dev = ops.to_dev(slot_of, torch.int64, dev)
-            sc, info0 = pool.begin_beat(y[:, ld])
-            q_aux[-1, :M, ld] = sc[sl_dev]
-        elif M > 0:
-            q_aux[-1, :M, ld] = self._last_scores(x, y, ld)
-        _tick("scores")
-        if t > 0:
-            # how well does each existing cluster explain the beat?  candidates are tried best first; the worst one lends its
-            # kernel and priors to the would-be new cluster
-            last_row = self.weight_mean(q_aux)[-1, :-1]
-            if info0 is not None:                                          # the scores' LAPACK status rides the same round trip
-                host = torch.cat([last_row, info0.to(f64)]).cpu()
-                if bool(host[M:].any()):
-                    ops.raise_on_info(info0, "log_sq_error")
-                last_row = host[:M]
-            q_ord = torch.argsort(last_row.cpu(), descending=True)
-            m_w = int(q_ord[-1])
-            q_prev, q_lat_prev = q_aux.clone(), q_lat.clone()
-            prov = self.gpmodel_deepcopy(self.gpmodels[ld][m_w])
-            prov.reinit_GP(save_last=False)
-            prov.reinit_LDS(save_last=False)
-            prov._defer_checks = True                                # its LAPACK statuses are read together, below
-            q_prev[-1, -1, ld] = prov.estimate_new_and_include(t, x, y[:, [ld]]) + liks[-1]
-            birth_best = int(torch.argmax(q_prev[-1])) == M          # the new cluster scores the beat best: is it worth it?
-            order = q_ord.tolist() if birth_best else []
-            lds_cur = [g.lds_param_likelihood_value() for g in self.gpmodels[ld]]
-            lds_cand = lds_prov = None
-            if order:
-                if pool is not None:
-                    # the new cluster's own latent-transition score and parameter likelihoods ride the candidates' batched calls
-                    m_of = np.argsort(slot_of)                         # cluster index of every slot
-                    res = pool.candidates(t, q_lat[:, ops.to_dev(m_of, torch.int64, dev), ld].contiguous(), [mods[m].indexes for m in m_of],
-                                          extra=prov)
-                    est, cols, lds_s = res[:3]
-                    est, cols, lds_cand = est[sl_dev], cols[:, sl_dev], [float(lds_s[c]) for c in slot_of]
-                    if len(res) == 5:
-                        q_lat_prev[t, -1, ld] = res[3]
-                        lds_prov = res[4]
-                else:
-                    est, cols, lds_cand = self._eager_candidates(ld, t, x, y, q_lat, n_hist)
-            if lds_prov is None:
-                q_lat_prev[:, -1, ld] = prov.compute_q_lat_all(n_hist, h_ini=1.0)
-                lds_prov = float(prov.return_LDS_param_likelihood())
-            prov._defer_checks = False
-            prov._check_pending()
-            _tick("candidates")
-            # score tables of every evaluation of this beat: [0] current clusters, [1] with the new cluster, [2 + r] the r best
-            # clusters tried so far with the beat added (the reference's q_post is cumulative over its loop, GPI_HDP.py:2040-2075)
-            Qb, Lb = self.weight_mean(q_aux), self.weight_mean(q_lat)
-            Qs, Ls = [Qb, self.weight_mean(q_prev)], [Lb, self.weight_mean(q_lat_prev)]
-            if order:
-                R = len(order)
-                od = ops.to_dev(order, torch.int64, dev)
-                tried = torch.zeros((R, K), dtype=torch.bool, device=dev)             # tried[r, m]: cluster m is among the r + 1 best
-                tried[:, od] = torch.tril(torch.ones((R, R), dtype=torch.bool, device=dev))
-                new_last = Qb[-1].clone()
-                new_last[:M] = est + ops.to_dev(liks[:M], f64, dev)
-                Qc = Qb.unsqueeze(0).repeat(R, 1, 1)
-                Qc[:, -1, :] = torch.where(tried, new_last[None, :], Qb[-1][None, :])
-                cols_full = Lb.clone()
-                cols_full[:, :M] = cols
-                Lc = torch.where(tried[:, None, :], cols_full[None], Lb[None])
-                Qs += list(Qc.unbind(0))
-                Ls += list(Lc.unbind(0))
-            Qall, Lall = torch.stack(Qs), torch.stack(Ls)
-            B = Qall.shape[0]
-            lab, prs, last, lab_dev = self._local_terms_many(Qall, liks)
-            _tick("local_terms")
-            # the sums of the bound over the assigned entries (all rows; all but the newest for the current clusters)
-            n_cols = torch.full((B, 1), M, dtype=torch.int64, device=dev)
-            n_cols[1] = M + 1
-            valid = lab_dev < n_cols
-            idx = torch.clamp(lab_dev, max=M)[..., None]
-            zero = torch.zeros((), dtype=f64, device=dev)
-            gq = torch.where(valid, Qall.gather(2, idx)[..., 0], zero)
-            gl = torch.where(valid, Lall.gather(2, idx)[..., 0], zero)
-            sums = torch.stack([torch.sum(gq[0, :-1]), torch.sum(gl[0, :-1])] + [v for b in range(1, B) for v in (torch.sum(gq[b]), torch.sum(gl[b]))])
-            sums = sums.cpu().numpy().reshape(B, 2)
-            q_all, elbo = self._bound_from_labels(lab[0], prs[0], K, T_all - 1, M, sums[0, 0], sums[0, 1], lds_cur, post=False)
-            q_prev_post, elbo_prev_post = self._bound_from_labels(lab[1], prs[1], K, T_all, M + 1, sums[1, 0], sums[1, 1],
-                                                                  lds_cur + [lds_prov], post=True)
-            elbo_prev_post -= elbo
-            q_prev_post -= q_all
-            chosen = 0                                                  # index into Qs of the table that is kept
-            if birth_best:
-                chosen = 1
-                for r, m in enumerate(order):
-                    lds_r = list(lds_cur)
-                    lds_r[m] = lds_cand[m]                              # only the cluster being tried is the candidate's (GPI_HDP.py:2071)
-                    q_bas_post, elbo_bas_post = self._bound_from_labels(lab[2 + r], prs[2 + r], K, T_all, M, sums[2 + r, 0], sums[2 + r, 1],
-                                                                        lds_r, post=False)
-                    elbo_bas_post -= elbo
-                    q_bas_post -= q_all
-                    if q_bas_post + elbo_bas_post > q_prev_post + elbo_prev_post:
-                        chosen = 2 + r
-                        break
-            resp, respPair = _tables(lab[chosen], prs[chosen], K)
-            _tick("bounds")
-            resplog = last[chosen]
-            q_chos, q_lat_chos = Qall[chosen].unsqueeze(-1).clone(), Lall[chosen].unsqueeze(-1).clone()
-        else:
-            q_chos, q_lat_chos = q_aux, q_lat
-            resp, resplog, respPair, _ = self.variational_local_terms(q_aux, self.transTheta, self.startTheta, liks)
+            b.q_aux[:-1, :prev.shape[1], :] = prev
+        return b
 
-        resp_mod = resp[-1].numpy()                      # a view: edits below land in the table, as in the reference
-        model = int(np.argmax(resp_mod))
+    def _score_current(self, b):
+        """The beat under the current clusters (GPI_HDP.py:1973): the last row of q_aux, the clusters' columns of q_lat."""
+        ld, M, mods = b.ld, b.M, self.gpmodels[b.ld]
+        b.pool = self._online_pool(ld, b.x) if b.t > 0 else None           # the clusters as persistent chains (online_chain.py)
+        if M > 0:
+            b.q_lat[:, :M, ld] = torch.stack([gp.compute_q_lat_all(b.n_hist, h_ini=1.0) for gp in mods], dim=1)
+        if b.pool is not None:
+            b.q_aux[-1, :M, ld], b.info0 = b.pool.begin_beat(b.y[:, ld], mods)
+        elif M > 0:
+            b.q_aux[-1, :M, ld] = self._last_scores(b.x, b.y, ld)
+
+    def _propose(self, b):
+        """The provisional new cluster (GPI_HDP.py:1990-1996) and, when it scores the beat best, every cluster with the beat
+        added (b.cand, else None).  How well does each existing cluster explain the beat?  candidates are tried best first
+        (b.order); the worst one lends its kernel and priors to the would-be new cluster."""
+        ld, M, t = b.ld, b.M, b.t
+        last_row = self.weight_mean(b.q_aux)[-1, :-1]
+        if b.info0 is not None:                                            # the scores' LAPACK status rides the same round trip
+            host = torch.cat([last_row, b.info0.to(f64)]).cpu()
+            if bool(host[M:].any()):
+                ops.raise_on_info(b.info0, "log_sq_error")
+            last_row = host[:M]
+        q_ord = torch.argsort(last_row.cpu(), descending=True)
+        b.q_prev, b.q_lat_prev = b.q_aux.clone(), b.q_lat.clone()
+        prov = self.gpmodel_deepcopy(self.gpmodels[ld][int(q_ord[-1])])
+        prov.reinit_GP(save_last=False)
+        prov.reinit_LDS(save_last=False)
+        prov._defer_checks = True                                    # its LAPACK statuses are read together, below
+        b.q_prev[-1, -1, ld] = prov.estimate_new_and_include(t, b.x, b.y[:, [ld]]) + b.liks[-1]
+        b.birth_best = int(torch.argmax(b.q_prev[-1])) == M          # the new cluster scores the beat best: is it worth it?
+        b.order = q_ord.tolist() if b.birth_best else []
+        b.lds_cur = [g.lds_param_likelihood_value() for g in self.gpmodels[ld]]
+        b.cand = None
+        if b.order and b.pool is not None:
+            # the new cluster's own latent-transition score and parameter likelihoods ride the candidates' batched calls
+            b.cand = b.pool.candidates(t, b.q_lat[:, :M, ld], extra=prov)
+        elif b.order:
+            b.cand = self._eager_candidates(ld, t, b.x, b.y, b.n_hist)
+        if b.cand is not None and b.cand.extra_lds is not None:
+            b.q_lat_prev[t, -1, ld], b.lds_prov = b.cand.extra_lat, b.cand.extra_lds
+        else:
+            b.q_lat_prev[:, -1, ld] = prov.compute_q_lat_all(b.n_hist, h_ini=1.0)
+            b.lds_prov = float(prov.return_LDS_param_likelihood())
+        prov._defer_checks = False
+        prov._check_pending()
+
+    def _score_tables(self, b):
+        """Score tables of every evaluation of this beat, b.Qall / b.Lall [2 + R, T_all, K]: [0] current clusters, [1] with the new
+        cluster, [2 + r] the r best clusters tried so far with the beat added (the reference's q_post is cumulative over its loop,
+        GPI_HDP.py:2040-2075) - and the local step of all of them at once (b.lab, b.prs, b.last host, b.lab_dev)."""
+        M, K, dev = b.M, b.K, self.device
+        Qb, Lb = self.weight_mean(b.q_aux), self.weight_mean(b.q_lat)
+        Qs, Ls = [Qb, self.weight_mean(b.q_prev)], [Lb, self.weight_mean(b.q_lat_prev)]
+        if b.order:
+            R = len(b.order)
+            od = ops.to_dev(b.order, torch.int64, dev)
+            tried = torch.zeros((R, K), dtype=torch.bool, device=dev)             # tried[r, m]: cluster m is among the r + 1 best
+            tried[:, od] = torch.tril(torch.ones((R, R), dtype=torch.bool, device=dev))
+            new_last = Qb[-1].clone()
+            new_last[:M] = b.cand.est + ops.to_dev(b.liks[:M], f64, dev)
+            Qc = Qb.unsqueeze(0).repeat(R, 1, 1)
+            Qc[:, -1, :] = torch.where(tried, new_last[None, :], Qb[-1][None, :])
+            cols_full = Lb.clone()
+            cols_full[:, :M] = b.cand.cols
+            Lc = torch.where(tried[:, None, :], cols_full[None], Lb[None])
+            Qs += list(Qc.unbind(0))
+            Ls += list(Lc.unbind(0))
+        b.Qall, b.Lall = torch.stack(Qs), torch.stack(Ls)
+        b.lab, b.prs, b.last, b.lab_dev = self._local_terms_many(b.Qall, b.liks)
+
+    def _walk_bounds(self, b):
+        """The sums of the bound over the assigned entries (all rows; all but the newest for the current clusters), the bound of
+        every table and the accept / reject walk in the reference's order.  Leaves the kept table's resp, respPair, resplog,
+        q_chos and q_lat_chos."""
+        M, K, T_all, dev = b.M, b.K, b.T_all, self.device
+        B = b.Qall.shape[0]
+        n_cols = torch.full((B, 1), M, dtype=torch.int64, device=dev)
+        n_cols[1] = M + 1
+        valid = b.lab_dev < n_cols
+        idx = torch.clamp(b.lab_dev, max=M)[..., None]
+        zero = torch.zeros((), dtype=f64, device=dev)
+        gq = torch.where(valid, b.Qall.gather(2, idx)[..., 0], zero)
+        gl = torch.where(valid, b.Lall.gather(2, idx)[..., 0], zero)
+        sums = torch.stack([torch.sum(gq[0, :-1]), torch.sum(gl[0, :-1])] + [v for i in range(1, B) for v in (torch.sum(gq[i]), torch.sum(gl[i]))])
+        sums = sums.cpu().numpy().reshape(B, 2)
+        bound = lambda i, rows, cols, lds, post: self._bound_from_labels(b.lab[i], b.prs[i], K, rows, cols, sums[i, 0], sums[i, 1], lds, post=post)   # noqa: E731
+        q_all, elbo = bound(0, T_all - 1, M, b.lds_cur, False)
+        q_prev_post, elbo_prev_post = bound(1, T_all, M + 1, b.lds_cur + [b.lds_prov], True)
+        elbo_prev_post -= elbo
+        q_prev_post -= q_all
+        chosen = 0                                                  # index into Qall of the table that is kept
+        if b.birth_best:
+            chosen = 1
+            for r, m in enumerate(b.order):
+                lds_r = list(b.lds_cur)
+                lds_r[m] = b.cand.lds[m]                            # only the cluster being tried is the candidate's (GPI_HDP.py:2071)
+                q_bas_post, elbo_bas_post = bound(2 + r, T_all, M, lds_r, False)
+                elbo_bas_post -= elbo
+                q_bas_post -= q_all
+                if q_bas_post + elbo_bas_post > q_prev_post + elbo_prev_post:
+                    chosen = 2 + r
+                    break
+        b.resp, b.respPair = _tables(b.lab[chosen], b.prs[chosen], K)
+        b.resplog = b.last[chosen]
+        b.q_chos, b.q_lat_chos = b.Qall[chosen].unsqueeze(-1).clone(), b.Lall[chosen].unsqueeze(-1).clone()
+
+    def _apply_choice(self, b, force_model):
+        """The newest row's cluster (b.force: forced by the caller or by the cap max_models, else None), birth, clusters by
+        size, and the counts of the global step (b.start_count, b.trans_count)."""
+        model = int(np.argmax(b.resp[-1].numpy()))
         if self.max_models is not None and model >= self.max_models:
-            force_model = int(np.argmax(resplog[:-1]))
-        if force_model is not None:
-            resp_mod[:] = 0.0
-            resp_mod[force_model] = 1.0
-            model = int(force_model)
-        order = torch.arange(resp.shape[1])
-        if model == self.M:
+            force_model = int(np.argmax(b.resplog[:-1]))
+        b.force = None if force_model is None else int(force_model)
+        if b.force is not None:
+            model = b.force
+            _assign_newest(model, b.resp[-1].numpy())                # a view: the edit lands in the table, as in the reference
+        birth = model == self.M
+        if birth:
             self._log("Birth of new model: ", self.M + 1)
-            self.M = M = self.M + 1
-            for ld in range(D):
+            self.M = self.M + 1
+            for ld in range(self.n_outputs):
                 self.gpmodels[ld].append(self.create_gp_default())
             self.x_basis.append(self.x_basis_ini)
-            resp, respPair, q_chos, q_lat_chos, order = self.reorder(resp, respPair, q_chos, q_lat_chos)
-            startStateCount, transStateCount = resp[0].numpy().copy(), torch.sum(respPair, dim=0).numpy()
-        else:
-            if force_model is None:
-                resp, respPair, q_chos, q_lat_chos, order = self.reorder(resp, respPair, q_chos, q_lat_chos)
-            startStateCount, transStateCount = resp[0, :M].numpy().copy(), torch.sum(respPair[:, :M, :M], dim=0).numpy()
-        _tick("reorder")
-        # the members' update of this beat (GPI_HDP.py:2186-2196, after the global step there): nothing below up to that point
-        # reads the cluster models, and nothing in the update reads the HDP parameters, so its launches go out first and run
-        # under the host-side optimisation of (rho, omega)
-        resp_mod = resp[-1].numpy()
-        if force_model is not None:
+        if birth or b.force is None:                     # quirk: a forced beat that opens no cluster leaves the clusters unsorted
+            b.resp, b.respPair, b.q_chos, b.q_lat_chos, _ = self.reorder(b.resp, b.respPair, b.q_chos, b.q_lat_chos)
+        M = self.M                                       # (after a birth the tables have exactly M columns)
+        b.start_count, b.trans_count = b.resp[0, :M].numpy().copy(), torch.sum(b.respPair[:, :M, :M], dim=0).numpy()
+
+    def _member_update(self, b):
+        """The beat joins its cluster (weight 1; the others take it with weight 0: GPI_HDP.py:2186-2196): on the cluster's
+        persistent chain when it has one.  Returns the pool with a commit in flight (finish_commit reads its status), or None."""
+        ld, D, pool = b.ld, self.n_outputs, b.pool
+        resp_mod = b.resp[-1].numpy()
+        if b.force is not None:
             resp_mod = resp_mod.copy()
-            resp_mod[:] = 0.0
-            resp_mod[int(force_model)] = 1.0
+            _assign_newest(b.force, resp_mod)
         committed = None
-        for m in range(M):
+        for m in range(self.M):
             h = float(resp_mod[m])
             gp = self.gpmodels[ld][m]
             chained = pool is not None and h == 1.0 and gp.N >= 1 and getattr(gp, "_slot", None) is not None
             if chained:               # the cluster's persistent chain takes the member step (Kalman + both MNIW updates)
-                pool.commit(gp, t, x, y[:, [ld]])
+                pool.commit(gp, b.t, b.x, b.y[:, [ld]])
                 committed = pool
             else:
-                gp.include_weighted_sample(t, x, x, y[:, [ld]], h)
+                gp.include_weighted_sample(b.t, b.x, b.x, b.y[:, [ld]], h)
             if h > 0.9:
-                row = y.reshape(1, -1, D)
+                row = b.y.reshape(1, -1, D)
                 self.y_train = row if self.y_train.numel() == 0 else torch.cat([self.y_train, row])
             if not chained:
                 gp.bayesian_new_params(h, model_type=self.model_type_def)
+        return committed
+
+    def _global_step(self, b):
+        """The HDP global step from the beat's counts (GPI_HDP.py:2115-2128) and the transition matrix."""
+        M = self.M
         if M > 2:
-            self.reinit_global_params(M - 1, transStateCount, startStateCount)
+            self.reinit_global_params(M - 1, b.trans_count, b.start_count)
         if M >= 2:
             for _ in range(4):
-                self.transTheta, self.startTheta = self._calcThetaFull(transStateCount, startStateCount, M)
+                self.transTheta, self.startTheta = self._calcThetaFull(b.trans_count, b.start_count, M)
                 self.rho, self.omega = self.find_optimum_rhoOmega()
-        _tick("rho_omega")
         self.trans_A = torch.as_tensor(_log_trans(self.transTheta, M))
-        resp_mod = resp[-1].numpy()
-        model = int(np.argmax(resp_mod))
-        if force_model is not None:
-            model = int(force_model)
-            resp_mod[:] = 0.0
-            resp_mod[model] = 1.0
-            q_chos[-1, model] = torch.max(q_chos[-1])
-            q_lat_chos[-1, model] = torch.max(q_lat_chos[-1])
-            respPair[-1, model, :] = 0.0
-            respPair[-1, :, model] = 0.0
-            respPair[-1, model, model] = 1.0
+
+    def _record(self, b, committed):
+        """The beat's state, its row of the tables (forced: in every table, GPI_HDP.py:2168-2178) and the history."""
+        M = self.M
+        model = int(np.argmax(b.resp[-1].numpy())) if b.force is None else b.force
+        if b.force is not None:
+            _assign_newest(model, b.resp[-1].numpy(), b.respPair, b.q_chos, b.q_lat_chos)
         self.actual_state = model
         self._log("Main model chosen:", model + 1)
         if committed is not None:
             committed.finish_commit()
-        _tick("commit")
         if self.verbose:
-            self.compute_q_elbo(resp[:, :M], respPair[:, :M, :M], self.weight_mean(q_chos)[:, :M], self.weight_mean(q_lat_chos)[:, :M],
+            self.compute_q_elbo(b.resp[:, :M], b.respPair[:, :M, :M], self.weight_mean(b.q_chos)[:, :M], self.weight_mean(b.q_lat_chos)[:, :M],
                                 self.gpmodels, self.M, snr='saved', post=False, one_sample=True)
-        self.resp_assigned.append(torch.argmax(resp, dim=1))
-        self.q.append(q_chos)
+        self.resp_assigned.append(torch.argmax(b.resp, dim=1))
+        self.q.append(b.q_chos)
 
 
 # ---------------------------------------------------------------------- small host-side pieces both loops use (offline_loop imports them)
@@ -411,6 +439,24 @@ def _tables(labels, pairs, K):
     respPair = torch.zeros((N, K * K), dtype=f64)                             # the reference's table is float32: 0 / 1 either way
     respPair[torch.arange(N), torch.as_tensor(pairs)] = 1.0
     return resp, respPair.reshape(N, K, K)
+
+
+def _assign_newest(model, resp_row, respPair=None, q=None, q_lat=None):
+    """The forced assignment of include_sample: the newest row belongs to `model` (the caller's force_model, or the best existing
+    cluster when the cap max_models forbids a birth), written into the tables given - resp_row: the newest row of resp (a view
+    edits the table; a copy leaves it alone), respPair, and the score matrices q / q_lat, where the row's maximum goes to the
+    forced cluster (GPI_HDP.py:2168-2178).  The reference itself raises on this path unless the beat opens a cluster
+    (GPI_HDP.py:2187: `reorder` is bound only by the two self.reorder(...) calls, which the forced no-birth branch skips -
+    UnboundLocalError); there the clusters keep their order, and that identity order is the definition (pinned by
+    tests/golden/include_sample_r102_forced_mirror.npz)."""
+    resp_row[:] = 0.0
+    resp_row[model] = 1.0
+    if q is not None:
+        q[-1, model] = torch.max(q[-1])
+        q_lat[-1, model] = torch.max(q_lat[-1])
+        respPair[-1, model, :] = 0.0
+        respPair[-1, :, model] = 0.0
+        respPair[-1, model, model] = 1.0
 
 
 # phase timing of include_sample (tools/time_online.py --phases): HGP_ONLINE_TIMING=1 synchronises at every phase boundary

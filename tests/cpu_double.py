@@ -163,7 +163,8 @@ def assign(fmsg, bmsg, want_resp=False):
 class EagerPool:
     """Stand-in for hdpgpc_amd.online_chain.OnlinePool with the same interface: the candidates and the committed step computed
     with the one-by-one GPI_model methods (through the stand-ins above), so that the CPU tier exercises the host logic
-    GPI_HDP.include_sample wraps around the pool (slot <-> cluster mapping, cumulative candidate tables, commit)."""
+    GPI_HDP.include_sample wraps around the pool (cumulative candidate tables, commit); like the pool it answers in the
+    cluster order of the model list given to begin_beat."""
 
     def __init__(self, T, device, annealing, cap=8):
         self.slots = []
@@ -172,23 +173,28 @@ class EagerPool:
     def supports(g):
         return g.N >= 1
 
+    def holds(self, g):
+        c = getattr(g, "_slot", None)
+        return c is not None and c < len(self.slots) and self.slots[c].g is g
+
     def adopt(self, g):
         import types
         g._slot = len(self.slots)
         self.slots.append(types.SimpleNamespace(g=g))
 
-    def begin_beat(self, y):
-        self._y = y.reshape(-1, 1)
-        sc = torch.stack([sl.g.log_sq_error(sl.g.x_basis, self._y, i=-1) for sl in self.slots])
-        return sc, torch.zeros(len(self.slots), dtype=torch.int32)
+    def begin_beat(self, y, models):
+        self._y, self._models = y.reshape(-1, 1), list(models)
+        sc = torch.stack([g.log_sq_error(g.x_basis, self._y, i=-1) for g in models])
+        return sc, torch.zeros(len(models), dtype=torch.int32)
 
-    def candidates(self, t_new, q_lat_cols, indexes, extra=None):
+    def candidates(self, t_new, q_lat_cols, extra=None):
         import types
         import hdpgpc_amd.GPI_HDP as H
+        from hdpgpc_amd.online_chain import Candidates
         est, cols, lds = [], [], []
         hist = torch.empty((q_lat_cols.shape[0], 0))
-        for sl in self.slots:
-            cand = H.GPI_HDP.gpmodel_deepcopy(types.SimpleNamespace(verbose=False), sl.g)
+        for g in self._models:
+            cand = H.GPI_HDP.gpmodel_deepcopy(types.SimpleNamespace(verbose=False), g)
             x, yy = cand.x_basis, self._y
             mean_, cov_, C_, Sigma_ = cand.smoother_weighted(x, yy, 1.0)
             est.append(cand.log_sq_error(x, yy, mean=mean_[-1], cov=cov_[-1], C=C_[-1], Sigma=Sigma_[-1], i=-1, first=len(cand.indexes) == 1))
@@ -197,7 +203,7 @@ class EagerPool:
             cand.bayesian_new_params(1.0)
             cols.append(cand.compute_q_lat_all(hist, h_ini=1.0))
             lds.append(cand.lds_param_likelihood_value())
-        return torch.stack(est), torch.stack(cols, dim=1), lds
+        return Candidates(torch.stack(est), torch.stack(cols, dim=1), lds, None, None)
 
     def commit(self, g, index, x_train, y):
         g.include_weighted_sample(index, x_train, x_train, y, 1.0)

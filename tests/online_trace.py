@@ -3,26 +3,82 @@ reference and compare, beat by beat, with the trace tests/golden/make_golden.py:
 import numpy as np
 
 
-def run_online(g, n=None):
+def _mirror(g, max_models=100):
+    """The mirror set up as hdpgpc/tests/test_online.py sets up the reference, with the fixture's injected kernel parameters."""
     import hdpgpc.GPI_HDP as hdpgp
 
     std, std_dif, bs0, bs1, bg0, bg1 = (float(v) for v in g["estimators"])
     data = np.asarray(g["y"], dtype=np.float64)[:, :, None]
-    n = data.shape[0] if n is None else n
-    T = data.shape[1]
-    xb = np.arange(float(T))[:, None]
+    xb = np.arange(float(data.shape[1]))[:, None]
     sw = hdpgp.GPI_HDP(xb, x_basis_warp=xb[::2], n_outputs=1, kernels=None, model_type="dynamic", ini_lengthscale=3.0,
                        bound_lengthscale=(1.0, 20.0), ini_gamma=std_dif, ini_sigma=std, ini_outputscale=300.0, noise_warp=std * 0.1,
                        bound_sigma=(bs0, bs1), bound_gamma=(bg0, bg1), bound_noise_warp=(std * 0.01, std * 0.02), warp_updating=False,
-                       method_compute_warp="greedy", verbose=False, hmm_switch=True, max_models=100, mode_warp="rough",
+                       method_compute_warp="greedy", verbose=False, hmm_switch=True, max_models=max_models, mode_warp="rough",
                        bayesian_params=True, inducing_points=False, estimation_limit=None, free_deg_MNIV=20)
     sw.fixed_theta = tuple(float(v) for v in g["theta_inject"])
+    return sw, xb, data
+
+
+def _beat(sw):
+    return (sw.actual_state, sw.M, sw.resp_assigned[-1].numpy().astype(np.int16), sw.q[-1].cpu().numpy().copy(),
+            np.array([len(m.indexes) for m in sw.gpmodels[0]]))
+
+
+def run_online(g, n=None):
+    sw, xb, data = _mirror(g)
     tr = []
-    for i in range(n):
+    for i in range(data.shape[0] if n is None else n):
         sw.include_sample(xb, data[i], with_warp=False)
-        tr.append((sw.actual_state, sw.M, sw.resp_assigned[-1].numpy().astype(np.int16), sw.q[-1].cpu().numpy().copy(),
-                   np.array([len(m.indexes) for m in sw.gpmodels[0]])))
+        tr.append(_beat(sw))
     return sw, tr
+
+
+# the two runs of tests/golden/include_sample_r102_forced_mirror.npz: (beats, max_models, force_model per beat)
+FORCED_RUNS = {"cap": (14, 4, {}), "force": (12, 100, {6: 1, 7: 1, 9: 0})}
+
+
+def run_forced(g, run):
+    """One of FORCED_RUNS on the first beats of g (include_sample_r102_n40.npz): the model cap or a caller's force_model decides
+    some beats.  Returns (sw, trace as run_online's, forced [n] bool).  A beat was forced when include_sample did not sort the
+    clusters by size (it skips reorder() exactly on its forced no-birth branch)."""
+    n, max_models, force = FORCED_RUNS[run]
+    sw, xb, data = _mirror(g, max_models)
+    calls, sort = [0], sw.reorder
+
+    def counted(*a):
+        calls[0] += 1
+        return sort(*a)
+
+    sw.reorder = counted
+    tr, forced = [], []
+    for i in range(n):
+        calls[0] = 0
+        sw.include_sample(xb, data[i], with_warp=False, force_model=force.get(i))
+        tr.append(_beat(sw))
+        forced.append(calls[0] == 0)
+    return sw, tr, np.array(forced)
+
+
+def record_forced_mirror(g, path):
+    """Write include_sample_r102_forced_mirror.npz: THIS PROJECT'S OWN behaviour on the forced path (the reference raises
+    UnboundLocalError there, GPI_HDP.py:2187), recorded on the CPU tier (cpu_double.install) in compare_online's format, one key
+    prefix per run of FORCED_RUNS."""
+    out = {}
+    for run in FORCED_RUNS:
+        _, tr, forced = run_forced(g, run)
+        out[f"{run}_state"], out[f"{run}_M"] = np.array([b[0] for b in tr]), np.array([b[1] for b in tr])
+        out[f"{run}_forced"] = forced
+        for i, (_, _, labels, q, counts) in enumerate(tr):
+            out[f"{run}_b{i}_labels"], out[f"{run}_b{i}_q"], out[f"{run}_b{i}_counts"] = labels, q, counts
+    np.savez_compressed(path, **out)
+
+
+def compare_forced(g, rec, tol):
+    """Replay both FORCED_RUNS against the recorded fixture rec: the forced beats and every decision identical, q within tol."""
+    for run in FORCED_RUNS:
+        _, tr, forced = run_forced(g, run)
+        assert np.array_equal(forced, rec[f"{run}_forced"]), f"run {run}: forced beats {forced} vs {rec[f'{run}_forced']}"
+        compare_online({k[len(run) + 1:]: rec[k] for k in rec.files if k.startswith(run + "_")}, tr, tol)
 
 
 def compare_online(g, tr, tol):

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import golden
-from online_trace import compare_online, run_online
+from online_trace import compare_forced, compare_online, run_online
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +49,14 @@ def test_include_sample_two_records_t256():
     worst = compare_online(g, tr, 1e-8)
     assert sum(1 for i in range(1, 32) if int(g["M"][i]) == int(g["M"][i - 1])) >= 2       # beats that join an existing cluster
     print(f"include_sample, 16 + 16 beats of records 100 / 102 at T=256: {wall:.2f} s (reference {float(g['secs'].sum()):.1f} s), worst {worst:.2e}")
+
+
+def test_include_sample_forced_mirror_t90():
+    """The forced assignment (model cap; force_model) on the HIP kernels - the pool's commit with a forced model - against
+    tests/golden/include_sample_r102_forced_mirror.npz: a record of THIS PROJECT'S OWN behaviour on the CPU tier, not of the
+    reference, which raises UnboundLocalError at the first forced beat (GPI_HDP.py:2187, `reorder` unbound).  Forced beats and
+    decisions identical, scores within the 1e-8 of the traces above."""
+    compare_forced(golden("include_sample_r102_n40.npz"), golden("include_sample_r102_forced_mirror.npz"), 1e-8)
 
 
 def test_online_rank1_factor_tracking_t256():

@@ -68,12 +68,12 @@ def test_candidates_and_commit_match_the_one_by_one_path(T):
         pool.adopt(g)
     cols0 = torch.stack([g.compute_q_lat_all(hist) for g in models], dim=1).contiguous()
     before = [[t.clone() for t in (g.f_star_sm[-1], g.cov_f_sm[-1], g.A[-1], g.Sigma[-1], g.internal_params.scale)] for g in models]
-    sc, info = pool.begin_beat(y[:, 0])
+    sc, info = pool.begin_beat(y[:, 0], models)
     assert int(info.abs().max()) == 0
     for c, g in enumerate(models):                 # the beat under every cluster's last state: log_sq_error(x, y, i=-1)
         want = float(g.log_sq_error(x, y, i=-1))
         assert abs(float(sc[c]) - want) <= 1e-9 * abs(want)
-    est, cols, lds = pool.candidates(t_new, cols0, [g.indexes for g in models])
+    est, cols, lds = pool.candidates(t_new, cols0)[:3]
     est, cols = est.cpu().numpy(), cols.cpu().numpy()
     for c, (e_ref, col_ref, lds_ref, _) in enumerate(ref):
         assert abs(est[c] - e_ref) <= 1e-9 * abs(e_ref), (c, est[c], e_ref)
@@ -107,8 +107,8 @@ def test_candidates_and_commit_match_the_one_by_one_path(T):
     ref2 = [_one_by_one(sw, g, x, y2, t_new + 1, T_all + 1) for g in models]
     hist2 = torch.empty((T_all + 1, 0))
     cols1 = torch.stack([g.compute_q_lat_all(hist2) for g in models], dim=1).contiguous()
-    pool.begin_beat(y2[:, 0])
-    est2, cols2, lds2 = pool.candidates(t_new + 1, cols1, [g.indexes for g in models])
+    pool.begin_beat(y2[:, 0], models)
+    est2, cols2, lds2 = pool.candidates(t_new + 1, cols1)[:3]
     for c, (e_ref, col_ref, lds_ref, _) in enumerate(ref2):
         assert abs(float(est2[c]) - e_ref) <= 1e-9 * abs(e_ref)
         got = cols2[:, c].cpu().numpy()

@@ -44,6 +44,16 @@ def test_include_sample_trace_cpu(monkeypatch):
     compare_online(g, tr, 1e-9)
 
 
+def test_include_sample_forced_mirror_cpu(monkeypatch):
+    """The forced assignment of the online step (the model cap max_models, a caller's force_model) against a record of THIS
+    PROJECT'S OWN behaviour, tests/golden/include_sample_r102_forced_mirror.npz (online_trace.record_forced_mirror, CPU tier) -
+    not the reference's: the reference raises UnboundLocalError at the first forced beat (GPI_HDP.py:2187, `reorder` unbound).
+    Forced beats and decisions identical, scores within the gate of test_include_sample_trace_cpu."""
+    from online_trace import compare_forced
+    cpu_double.install(monkeypatch)
+    compare_forced(golden("include_sample_r102_n40.npz"), golden("include_sample_r102_forced_mirror.npz"), 1e-9)
+
+
 def test_cluster_new_batch_learning_two_leads_cpu(monkeypatch):
     """Host logic with two leads (SNR-weighted combination, one model per (lead, cluster)): cluster_new_batch(learning=True)
     against the reference's trace; tolerance as in tests/test_gpu_include_batch.py."""
