@@ -613,6 +613,50 @@ def kernel_fit_steps(x, Y, bounds, state, status, n_steps, lr=0.1, min_iter=1000
                                                  _ptr(loss_out) if ld else None, ld, _ptr(ws), stream), "kernel_fit_steps")
 
 
+_mds_ws = _StreamWorkspace()       # hgp_smacof_steps_f64
+
+
+def smacof_release():
+    """Drop the cached workspaces of smacof_steps (the memory returns to torch's allocator once queued calls have finished)."""
+    _mds_ws.release()
+
+
+def smacof_ws_doubles(B, n, p):
+    """HGP_MDS_WS_DOUBLES of include/hdpgpc_hip_mds.h."""
+    return B * n * (p + 2)
+
+
+def smacof_steps(delta, X, state, status, stress, n_iter, n_steps, eps=1e-6, max_iter=300):
+    """a15 (hgp_smacof_steps_f64): advance every running start of X [B,n,p] (p = 1..3) on the distance matrix delta [n,n] (a
+    row-strided view [n, ld >= n] is taken as it is) by up to n_steps SMACOF passes, in place in X, state [B, MDS_STATE_DOUBLES]
+    and status [B] (int32; all zeros = the beginning).  A start that ends (status 1: stop rule, 2: max_iter, -2: non-finite
+    stress) leaves scikit-learn's X, stress [B] and n_iter [B] (int32); one that ends at max_iter has run max_iter + 1 passes.
+    Nothing is synchronised and nothing returns to the host."""
+    if not (torch.is_tensor(delta) and delta.is_cuda and delta.dtype == torch.float64 and delta.dim() == 2
+            and delta.shape[0] == delta.shape[1] and delta.shape[0] >= 1 and (delta.shape[0] == 1 or delta.stride(1) == 1)
+            and delta.stride(0) >= delta.shape[1]):
+        raise ValueError("smacof_steps: delta must be a square fp64 matrix on the GPU with unit column stride")
+    n = delta.shape[0]
+    ld = delta.stride(0) if n > 1 else max(delta.stride(0), 1)
+    X = _dev64(X, "X")
+    if X.dim() != 3 or X.shape[1] != n or not 1 <= X.shape[2] <= 3:
+        raise ValueError("smacof_steps: X must be [B, n, p] with p = 1, 2 or 3")
+    B, _, p = X.shape
+    state, stress = _dev64(state, "state"), _dev64(stress, "stress")
+    if tuple(state.shape) != (B, _ffi.MDS_STATE_DOUBLES) or stress.numel() != B:
+        raise ValueError("smacof_steps: state must be [B, MDS_STATE_DOUBLES] and stress [B]")
+    for t, name in ((status, "status"), (n_iter, "n_iter")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B):
+            raise TypeError(f"smacof_steps: {name} must be a contiguous int32 tensor [B] on the GPU")
+    if n_steps < 0:
+        raise ValueError("smacof_steps: n_steps < 0")
+    if B == 0 or n_steps == 0:
+        return
+    ws, stream = _mds_ws.get(X.device, smacof_ws_doubles(B, n, p))
+    _ffi.check(_ffi.lib.hgp_smacof_steps_f64(_ptr(delta), int(ld), n, p, B, _ptr(X), float(eps), int(n_steps), int(max_iter), _ptr(state),
+                                             _ptr(status), _ptr(stress), _ptr(n_iter), _ptr(ws), stream), "smacof_steps")
+
+
 def rts_chain(J, P, AM, M, Cv):
     """Sequential part of the RTS smoother for all steps in one launch (in place on M [n,T] and Cv [n,T,T]); T <= 96."""
     n, T = M.shape[0], Cv.shape[1]

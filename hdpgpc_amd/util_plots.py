@@ -2,7 +2,7 @@
 out of scope: every plot_* function computes and returns what its figure is drawn from and draws
 nothing - plot_models / plot_models_plotly / plot_partial_models the cluster templates with their predictive bands on the
 plotting grid (model_bands, model_evolution: one device call for all states, util_plots.py:335-476,755-772), plot_MDS /
-plot_MDS_plotly the distance matrix (util_plots.py:598-688)."""
+plot_MDS_plotly the distance matrix (util_plots.py:598-688); mds_embedding adds the MDS embedding of that matrix (mds.smacof)."""
 import numpy as np
 import torch
 
@@ -155,52 +155,95 @@ def plot_partial_models(sw_gp, selected_gpmodels, main_model=None, labels=None, 
     return data
 
 
-def kl_distance_matrix(sw_gp, lead=0, smoothed=False):
-    """The [sw_gp.T, sw_gp.T] matrix of symmetric Kullback-Leibler distances that plot_MDS / plot_MDS_plotly build
-    (util_plots.py:600-616): entry (ind1, ind2) compares the observed Gaussians of the member states that included segments
-    ind1 and ind2, over every cluster of `lead`, on the grid sw_gp.x_basis[0].  One device call for all pairs.  Rows and
-    columns of segments that belong to no cluster stay zero, the diagonal is zero and the matrix is symmetric."""
+def _kl_blocks(sw_gp, lead, smoothed):
+    """The blocks kl_distance_matrix places: (D on the device, segment index of each row, of each column), one device call each."""
     from . import ops
 
-    n_seg = int(sw_gp.T)
-    KL = np.zeros((n_seg, n_seg))
     x_bas = sw_gp.x_basis[0]
     models = [gp for gp in sw_gp.gpmodels[lead] if len(gp.indexes) > 0]
     if not models:
-        return KL
-
-    def scatter(D, seg1, seg2):
-        # the reference fills ind1 < ind2 and mirrors (util_plots.py:612-616)
-        ii, jj = np.nonzero(seg1[:, None] < seg2[None, :])
-        KL[seg1[ii], seg2[jj]] = D[ii, jj]
-        KL[seg2[jj], seg1[ii]] = D[ii, jj]
-
+        return
     segs = [np.asarray([int(i) for i in gp.indexes]) for gp in models]
     rule = {gp._kl_static() for gp in models}
     if len(rule) == 1:
         mom = [gp._kl_moments_on(range(len(gp.indexes)), smoothed, x_bas, latent=rule == {True}) for gp in models]
         D = ops.kl_sym(torch.cat([m for m, _ in mom]).contiguous(), torch.cat([c for _, c in mom]).contiguous())
         seg = np.concatenate(segs)
-        scatter(D.cpu().numpy(), seg, seg)
-        return KL
+        yield D, seg, seg
+        return
     # static and dynamic clusters in one lead: the model that holds the smaller segment index decides what is compared
     # (GPI_model.py:918-921), so the blocks are computed model pair by model pair
     for g1, s1 in zip(models, segs):
         for g2, s2 in zip(models, segs):
-            D = g1.kl_states(range(len(s1)), g2, range(len(s2)), smoothed=smoothed, x_bas=x_bas)
-            scatter(D.cpu().numpy(), s1, s2)
+            yield g1.kl_states(range(len(s1)), g2, range(len(s2)), smoothed=smoothed, x_bas=x_bas), s1, s2
+
+
+def kl_distance_matrix(sw_gp, lead=0, smoothed=False):
+    """The [sw_gp.T, sw_gp.T] matrix of symmetric Kullback-Leibler distances that plot_MDS / plot_MDS_plotly build
+    (util_plots.py:600-616): entry (ind1, ind2) compares the observed Gaussians of the member states that included segments
+    ind1 and ind2, over every cluster of `lead`, on the grid sw_gp.x_basis[0].  One device call for all pairs.  Rows and
+    columns of segments that belong to no cluster stay zero, the diagonal is zero and the matrix is symmetric."""
+    n_seg = int(sw_gp.T)
+    KL = np.zeros((n_seg, n_seg))
+    for D, seg1, seg2 in _kl_blocks(sw_gp, lead, smoothed):
+        # the reference fills ind1 < ind2 and mirrors (util_plots.py:612-616)
+        D = D.cpu().numpy()
+        ii, jj = np.nonzero(seg1[:, None] < seg2[None, :])
+        KL[seg1[ii], seg2[jj]] = D[ii, jj]
+        KL[seg2[jj], seg1[ii]] = D[ii, jj]
     return KL
 
 
+def kl_distance_matrix_device(sw_gp, lead=0, smoothed=False, device=None):
+    """kl_distance_matrix, the same values, placed on the device and left there (an fp64 tensor): the matrix never crosses to
+    the host.  `device` is only needed when no cluster of the lead has a member (default cuda:0)."""
+    n_seg = int(sw_gp.T)
+    KL = None
+    for D, seg1, seg2 in _kl_blocks(sw_gp, lead, smoothed):
+        if KL is None:
+            KL = torch.zeros((n_seg, n_seg), dtype=torch.float64, device=D.device)
+        ii, jj = np.nonzero(seg1[:, None] < seg2[None, :])
+        if ii.size == 0:
+            continue
+        a, b = (torch.as_tensor(v, dtype=torch.int64, device=D.device) for v in (seg1[ii], seg2[jj]))
+        vals = D[torch.as_tensor(ii, device=D.device), torch.as_tensor(jj, device=D.device)]
+        KL[a, b] = vals
+        KL[b, a] = vals
+    if KL is None:
+        KL = torch.zeros((n_seg, n_seg), dtype=torch.float64, device=device or "cuda:0")
+    return KL
+
+
+def mds_embedding(sw_gp, lead=0, smoothed=False, n_components=2, n_init=4, max_iter=300, eps=1e-6, random_state=None, KL=None):
+    """The compute part of plot_MDS / plot_MDS_plotly (util_plots.py:600-620): the distance matrix of kl_distance_matrix (or
+    `KL`, a host array or a device tensor) and its embedding MDS(dissimilarity='precomputed').fit_transform by mds.smacof; the
+    matrix goes from the one device call to the other without crossing to the host.  Returns a dict of host arrays: `X`
+    [sw_gp.T, n_components], `stress`, `n_iter` (of the best of n_init starts), `KL`, `cluster` [sw_gp.T] = the cluster of
+    `lead` that holds each segment (-1: none) and `order` = the segment indices in time order, the line the figure draws
+    through the points (util_plots.py:649-654)."""
+    from . import mds
+
+    n_seg = int(sw_gp.T)
+    if KL is None:
+        KL = kl_distance_matrix_device(sw_gp, lead=lead, smoothed=smoothed)
+    X, stress, n_iter, _ = mds.smacof(KL, n_components=n_components, n_init=n_init, max_iter=max_iter, eps=eps, random_state=random_state)
+    cluster = np.full(n_seg, -1, dtype=np.int64)
+    for m, gp in enumerate(sw_gp.gpmodels[lead]):
+        for i in gp.indexes:
+            cluster[int(i)] = m
+    return {"X": X, "stress": stress, "n_iter": n_iter, "KL": KL.cpu().numpy() if torch.is_tensor(KL) else np.asarray(KL, dtype=np.float64),
+            "cluster": cluster, "order": np.arange(n_seg, dtype=np.int64)}
+
+
 def plot_MDS(sw_gp, main_model, labels, N_0, lead=0, save=None):
-    """util_plots.py:598-654 without the MDS embedding and the figure: computes and returns the distance matrix."""
+    """util_plots.py:598-654 without the figure: computes and returns the distance matrix (mds_embedding: the embedding too)."""
     KL = kl_distance_matrix(sw_gp, lead=lead, smoothed=False)
-    print("plot_MDS: figures are not part of the MI355X build" + (f" (nothing written to {save})" if save else ""))
+    print("plot_MDS: figures are not part of the MI355X build (mds_embedding computes the embedding)" + (f" (nothing written to {save})" if save else ""))
     return KL
 
 
 def plot_MDS_plotly(sw_gp, main_model, labels, N_0, lead=0, save=None):
-    """util_plots.py:656-688 without the MDS embedding and the figure: computes and returns the distance matrix."""
+    """util_plots.py:656-688 without the figure: computes and returns the distance matrix (mds_embedding: the embedding too)."""
     KL = kl_distance_matrix(sw_gp, lead=lead, smoothed=False)
-    print("plot_MDS_plotly: figures are not part of the MI355X build" + (f" (nothing written to {save})" if save else ""))
+    print("plot_MDS_plotly: figures are not part of the MI355X build (mds_embedding computes the embedding)" + (f" (nothing written to {save})" if save else ""))
     return KL
