@@ -41,14 +41,25 @@ def test_gemm_list_heterogeneous_items():
         if eye:
             ref = ref + eye * np.eye(M)
         cases.append((out, out2, ref))
-    gl.run()
-    gl.run()                                            # a list is replayed (hipGraph): same result every time
-    gl.run_range(2, 3)                                  # a sub-range of the list is one launch too
-    torch.cuda.synchronize()
-    for out, out2, ref in cases:
-        assert np.allclose(out.cpu().numpy(), ref, rtol=1e-12, atol=1e-12 * np.abs(ref).max())
-        if out2 is not None:
-            assert np.array_equal(out2.cpu().numpy(), out.cpu().numpy())
+    def launch_and_check(launch, covered):
+        """Every launch starts from NaN outputs and is checked on its own: the items it covers are right, the others untouched."""
+        for out, out2, _ in cases:
+            out.fill_(np.nan)
+            if out2 is not None:
+                out2.fill_(np.nan)
+        launch()
+        torch.cuda.synchronize()
+        for i, (out, out2, ref) in enumerate(cases):
+            if i not in covered:
+                assert torch.isnan(out).all() and (out2 is None or torch.isnan(out2).all())
+                continue
+            assert np.allclose(out.cpu().numpy(), ref, rtol=1e-12, atol=1e-12 * np.abs(ref).max())
+            if out2 is not None:
+                assert np.array_equal(out2.cpu().numpy(), out.cpu().numpy())
+
+    launch_and_check(gl.run, range(len(cases)))
+    launch_and_check(gl.run, range(len(cases)))                # a list is replayed: same result every time
+    launch_and_check(lambda: gl.run_range(2, 3), range(2, 5))   # a sub-range of the list is one launch too
     with pytest.raises(ValueError):
         gl.add(dev(np.zeros((4, 5))), dev(np.zeros((6, 4))), torch.zeros((4, 4), dtype=torch.float64, device="cuda"))
     with pytest.raises(ValueError):
