@@ -30,7 +30,7 @@ from scipy.special import digamma as _digamma
 
 from . import hdp_global, ops
 from .GPI import RBFWhiteKernel
-from .GPI_model import GPI_model, _copy_list
+from .GPI_model import GPI_model
 from .offline_loop import OfflineLoop
 from .online_loop import OnlineLoop, _log_trans, _np
 
@@ -154,7 +154,7 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         gp.initial_conditions(ini_A=cond[0], ini_Gamma=cond[1], ini_C=cond[2], ini_Sigma=cond[3])
         gp.theta_source = self
         # the prior scales are gamma I / sigma I by construction (GPR_dynamic): spare return_LDS_param_likelihood its device test
-        gp._def_diag_key, gp._def_diag = (id(gp.Sigma_def), id(gp.Gamma_def)), True
+        gp._memo_put("def_diag", (), True, (gp.Sigma_def, gp.Gamma_def))
         return gp
 
     def fit_kernels(self, y_trains, lead=0):
@@ -182,7 +182,7 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         g = GPI_model(gpmodel.gp.kernel.clone_with_theta(gpmodel.gp.kernel.theta), gpmodel.x_basis.clone(), annealing=gpmodel.annealing,
                       bayesian=gpmodel.bayesian, free_deg_MNIV=gpmodel.free_deg_MNIV, verbose=self.verbose)
         for name in ("y_train", "x_train", "f_star", "f_star_sm", "cov_f", "cov_f_sm", "A", "Gamma", "C", "Sigma", "indexes"):
-            setattr(g, name, _copy_list(getattr(gpmodel, name)))
+            setattr(g, name, getattr(gpmodel, name).copy())
         g.N, g.fitted, g.ini_cov_def = gpmodel.N, gpmodel.fitted, gpmodel.ini_cov_def
         g.A_def, g.Gamma_def, g.C_def, g.Sigma_def = gpmodel.A_def, gpmodel.Gamma_def, gpmodel.C_def, gpmodel.Sigma_def
         g.internal_params, g.observation_params = gpmodel.internal_params, gpmodel.observation_params
@@ -190,10 +190,7 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         g.theta_source = gpmodel.theta_source
         g.rank1_scoring, g._Lobs = gpmodel.rank1_scoring, gpmodel._Lobs
         g.gp.fitted = gpmodel.gp.fitted
-        if getattr(gpmodel, "_def_diag_key", None) == (id(g.Sigma_def), id(g.Gamma_def)):     # same prior objects: same verdict
-            g._def_diag_key, g._def_diag = gpmodel._def_diag_key, gpmodel._def_diag
-        if getattr(gpmodel, "_dyn_def", None) is not None:
-            g._dyn_def = gpmodel._dyn_def
+        g._share_prior_memos(gpmodel)              # same prior objects: same verdicts
         return g
 
     def keep_last_all(self):
@@ -350,7 +347,7 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         idx = np.asarray(gp.indexes, dtype=np.int64)
         pos = np.searchsorted(idx, np.arange(n), side="right") - 1            # find_closest_lower(t): idx-1 if idx else 0
         j = np.minimum(np.maximum(np.maximum(pos, 0), 1), len(gp.f_star_sm) - 1)
-        F = gp._S("f_star_sm")[torch.as_tensor(j, device=self.device)][..., 0]
+        F = gp.f_star_sm.stack()[torch.as_tensor(j, device=self.device)][..., 0]
         eps = torch.finfo(f64).eps
         return 10.0 * torch.log10((torch.sum(F ** 2, -1) + eps) / (torch.sum((F - y_lead) ** 2, -1) + eps))
 

@@ -15,76 +15,20 @@ model, shared grid, h = 1 (what hdpgpc/tests run with warp=False).  The gpytorch
 ``fit_kernel_params`` takes theta from ``GPI_model.fixed_theta`` (parity-unpinned piece).
 """
 import math
-from collections.abc import MutableSequence
+from operator import attrgetter
 
 import numpy as np
 import torch
 
 from . import ops
 from .GPI import IterativeGaussianProcess, RBFWhiteKernel
+from .steplist import StepList
 
 f64 = torch.float64
 LOG2PI = math.log(2.0 * math.pi)   # GPI_model.py:89-90
 
 
-class StackList(MutableSequence):
-    """One per-step list of a model (f_star[i], Sigma[i], ... one entry per LDS step in the reference, a12) held as ONE stacked
-    device tensor [L, ...].  Reads behave like the reference's Python list of tensors (len, [i], [-1], slices, iteration,
-    ``+``); the first mutation (item assignment, append) turns it into a real list (copy-on-write), so a model and its
-    copies can share one.  A 2 272-step chain is 8 such lists: building 18 000 tensor objects per pass, and re-stacking
-    them for every batched kernel, was 10 % of the offline loop's wall-clock.  It is a collections.abc.MutableSequence (pop,
-    extend, insert, del, reversed, ``in`` come with it); torch.stack / torch.cat only take real lists and tuples: pass
-    ``list(m.f_star)`` or use ``m.f_star.stack()``."""
-    __slots__ = ("_st", "_ls")
-
-    def __init__(self, stack):
-        self._st, self._ls = stack, None
-
-    def _list(self):
-        if self._ls is None:
-            self._ls, self._st = list(self._st.unbind(0)), None
-        return self._ls
-
-    def stack(self):
-        return self._st if self._ls is None else torch.stack(self._ls).contiguous()
-
-    def __len__(self):
-        return self._st.shape[0] if self._ls is None else len(self._ls)
-
-    def __getitem__(self, i):
-        if self._ls is not None:
-            return self._ls[i]
-        if isinstance(i, slice):
-            return list(self._st[i].unbind(0))
-        return self._st[i]
-
-    def __setitem__(self, i, v):
-        self._list()[i] = v
-
-    def __delitem__(self, i):
-        del self._list()[i]
-
-    def insert(self, i, v):
-        self._list().insert(i, v)
-
-    def append(self, v):
-        self._list().append(v)
-
-    def __radd__(self, other):
-        return list(other) + list(self)
-
-    def __iter__(self):
-        return iter(self._st.unbind(0) if self._ls is None else self._ls)
-
-    def __add__(self, other):
-        return list(self) + list(other)
-
-    def copy(self):
-        return StackList(self._st) if self._ls is None else list(self._ls)
-
-
-def _copy_list(lst):
-    return lst.copy() if isinstance(lst, StackList) else list(lst)
+StackList = StepList          # the name member_step.py and callers know it by
 
 
 class matrix_normal_inv_wishart:
@@ -171,17 +115,18 @@ class GPI_model:
         self.rank1_scoring = False
         self._Lobs = None              # (observation_params object the factor belongs to, lower Cholesky factor of its scale)
         self.noise_bounds = (1e-10, 1e10)
-        self._stk = {}
+        self._memo = {}                # see _memo_get
         self._pending = []
         self._defer_checks = False
 
     # ------------------------------------------------------------------ pickling (GPI_HDP.save_swgp)
+    # the per-step lists: properties (below the class) whose setter wraps what is assigned in a StepList
     _TENSOR_LISTS = ("f_star", "f_star_sm", "cov_f", "cov_f_sm", "A", "Gamma", "C", "Sigma", "x_train", "y_train")
 
     def __getstate__(self):
         """Host copies of the state; caches, pending status words and the online pool's slot are dropped."""
-        d = {k: v for k, v in self.__dict__.items() if k not in ("_stk", "_pending", "_slot", "_dyn", "theta_source",
-                                                                  "_Lobs", "_def_diag_key", "_def_diag", "_dyn_def")}
+        drop = ("_memo", "_pending", "_slot", "theta_source", "_Lobs") + tuple("_" + name for name in self._TENSOR_LISTS)
+        d = {k: v for k, v in self.__dict__.items() if k not in drop}
         cpu = lambda t: t.detach().cpu() if torch.is_tensor(t) else t           # noqa: E731
         for name in self._TENSOR_LISTS:
             d[name] = [cpu(t) for t in getattr(self, name)]
@@ -196,8 +141,9 @@ class GPI_model:
 
     def __setstate__(self, d):
         fixed = d.pop("theta_owner_fixed", None)
-        self.__dict__.update(d)
-        self._stk, self._pending, self._Lobs, self.theta_source = {}, [], None, None
+        for k, v in d.items():             # (the ten lists through their setters)
+            setattr(self, k, v)
+        self._memo, self._pending, self._Lobs, self.theta_source = {}, [], None, None
         if self.fixed_theta is None:
             self.fixed_theta = fixed
 
@@ -215,7 +161,6 @@ class GPI_model:
             m = getattr(self, name)
             if m is not None:
                 setattr(self, name, matrix_normal_inv_wishart(mv(m.m_mean), mv(m.m_r_cov), m.n0, mv(m.scale)))
-        self._stk = {}
 
     # ------------------------------------------------------------------ state (a12)
     def cond_to_torch(self, x):
@@ -240,7 +185,6 @@ class GPI_model:
                                                                  unb(mat(cov_f_sm)))
         if cov_f is not None:
             self.cov_f = unb(mat(cov_f))
-        self._stk = {}
         self.indexes = [int(i) for i in indexes]
         self.N = len(self.indexes)
         one = lambda a: None if a is None else self.cond_to_torch(a).reshape(T, T).contiguous()  # noqa: E731
@@ -249,35 +193,54 @@ class GPI_model:
             self.internal_params = matrix_normal_inv_wishart(self.A_def, None, n0, self.Gamma_def)
         return self
 
-    def _S(self, name):
-        """Stacked [steps, ...] device tensor of one of the per-step lists (cached until the list changes; every method
-        that rewrites an entry in place resets ``_stk``)."""
-        lst = getattr(self, name)
-        key = self._stk.get(name)
-        if isinstance(lst, StackList) and lst._ls is None:          # already one tensor: no copy
-            if key is None or key[2] is not lst._st:
-                self._stk[name] = [len(lst), None, lst._st, None]
-            return lst._st
-        if key is None or key[0] != len(lst) or key[1] is not lst[-1]:
-            self._stk[name] = [len(lst), lst[-1], torch.stack(list(lst)).contiguous(), None]
-        return self._stk[name][2]
+    # ------------------------------------------------------------------ values memoised per state of the lists
+    def _memo_get(self, name, lists, extra=()):
+        """The value stored by _memo_put(name, lists, value, extra), or None once one of the per-step lists named in `lists`
+        has changed (StepList.stamp) or `extra` differs (tensors of it are compared with ``is``, everything else with ==).
 
-    def _S_symmetric(self, name):
-        """Is every matrix of the stack equal to its transpose bit for bit?  One device check per stack, stored WITH the
-        stack (it dies with it)."""
-        self._S(name)
-        ent = self._stk[name]
-        if ent[3] is None:
-            ent[3] = bool(torch.equal(ent[2], ent[2].transpose(1, 2)))
-        return ent[3]
+        What each memoised value reads, and so what it is keyed by:
+
+        =========  ==========================================================  =============================================
+        name       lists                                                       extra
+        =========  ==========================================================  =============================================
+        lat_all    f_star_sm, cov_f_sm, A, Gamma (_lat_all gathers rows of     h_ini, len(indexes) (_lat_indices)
+                   all four stacks by _lat_indices)
+        lat_col    -                                                           the lat_all tensor it scatters (with the
+                                                                               member ids `indexes` it was scattered by)
+        lds_lik    A, Gamma, C, Sigma (return_LDS_param_likelihood reads       the prior tensors A_def, Gamma_def, C_def,
+                   their last entries)                                         Sigma_def
+        dyn        Gamma (_is_dynamic reads Gamma[-1])                         -
+        dyn_def    -                                                           Gamma_def
+        def_diag   -                                                           Sigma_def, Gamma_def
+        =========  ==========================================================  =============================================
+
+        A value that reads only X[-1] is keyed by the whole list X: correct, merely conservative."""
+        ent = self._memo.get(name)
+        if ent is None:
+            return None
+        stamps, ex, value = ent
+        if len(stamps) != len(lists) or len(ex) != len(extra):
+            return None
+        for n, st in zip(lists, stamps):
+            if getattr(self, n).stamp != st:
+                return None
+        for a, b in zip(ex, extra):
+            if a is not b and (torch.is_tensor(a) or torch.is_tensor(b) or a != b):
+                return None
+        return value
+
+    def _memo_put(self, name, lists, value, extra=()):
+        self._memo[name] = (tuple(getattr(self, n).stamp for n in lists), tuple(extra), value)
+        return value
 
     # ------------------------------------------------------------------ a7: which state does step t read?
-    def _select(self, t):
-        """(C/Sigma index, f_star index) of GPI_model.observe with params=None, proj=False (GPI_model.py:626-669)."""
-        nC, nf = len(self.C), len(self.f_star)
-        if len(self.indexes) == 0:
+    def _select(self, t, lens=None):
+        """(C/Sigma index, f_star index) of GPI_model.observe with params=None, proj=False (GPI_model.py:626-669).  lens: (len(C),
+        len(f_star), len(indexes)) from a caller that asks for many steps."""
+        nC, nf, n_members = lens or (len(self.C), len(self.f_star), len(self.indexes))
+        if n_members == 0:
             return 0, 0
-        if len(self.indexes) <= t:
+        if n_members <= t:
             return nC - 1, nf - 1
         if self.estimation_limit <= t:
             return nC - 1, t % nf
@@ -326,9 +289,9 @@ class GPI_model:
                 return empty, empty.clone()
             cix = ops.to_dev(ci, torch.int64, self.device)
             fix = ops.to_dev([f for _, f in sel], torch.int64, self.device)
-            mean = ops.gemm_batched(self._S("C").index_select(0, cix).contiguous(),
-                                    self._S("f_star").reshape(-1, T, 1).index_select(0, fix).contiguous()).reshape(-1, T)
-        Sig = self._S("Sigma")
+            mean = ops.gemm_batched(self.C.stack().index_select(0, cix).contiguous(),
+                                    self.f_star.stack().reshape(-1, T, 1).index_select(0, fix).contiguous()).reshape(-1, T)
+        Sig = self.Sigma.stack()
         sidx = ops.to_dev(ci, torch.int32, self.device)
         if xq.shape == self.x_basis.reshape(-1).shape and torch.equal(xq, self.x_basis.reshape(-1)):
             return mean, torch.diagonal(Sig, dim1=1, dim2=2).index_select(0, sidx.to(torch.int64)).contiguous()
@@ -360,14 +323,14 @@ class GPI_model:
         if len(ts) == 0:
             return torch.empty((0, T), dtype=f64, device=self.device), torch.empty((0, T, T), dtype=f64, device=self.device)
         fi = torch.as_tensor([t + 1 for t in ts], dtype=torch.int64, device=self.device)
-        f = self._S("f_star_sm" if smoothed else "f_star").reshape(-1, T, 1).index_select(0, fi).contiguous()
-        P = self._S("cov_f_sm" if smoothed else "cov_f").index_select(0, fi).contiguous()
+        f = (self.f_star_sm if smoothed else self.f_star).stack().reshape(-1, T, 1).index_select(0, fi).contiguous()
+        P = (self.cov_f_sm if smoothed else self.cov_f).stack().index_select(0, fi).contiguous()
         if self._kl_static() if latent is None else latent:
             return f.reshape(-1, T), P
         nC = len(self.C)
         ci = torch.as_tensor([(t if self.estimation_limit > t else -1) % nC for t in ts], dtype=torch.int64, device=self.device)
-        C = self._S("C").index_select(0, ci).contiguous()
-        Sig = self._S("Sigma").index_select(0, ci)
+        C = self.C.stack().index_select(0, ci).contiguous()
+        Sig = self.Sigma.stack().index_select(0, ci)
         S = ops.gemm_batched(ops.gemm_batched(C, P), C, transB=True, add=Sig.contiguous())
         return ops.gemm_batched(C, f).reshape(-1, T), 0.5 * (S + S.transpose(1, 2))
 
@@ -467,7 +430,7 @@ class GPI_model:
         ini_A, ini_Gamma, ini_C, ini_Sigma = (self.cond_to_torch(m).contiguous() for m in (ini_A, ini_Gamma, ini_C, ini_Sigma))
         self.A, self.Gamma, self.C, self.Sigma = [ini_A], [ini_Gamma], [ini_C], [ini_Sigma]
         self.A_def, self.Gamma_def, self.C_def, self.Sigma_def = ini_A, ini_Gamma, ini_C, ini_Sigma
-        self.indexes, self.N, self.x_train, self.y_train, self._stk = [], 0, [], [], {}
+        self.indexes, self.N, self.x_train, self.y_train = [], 0, [], []
         self.internal_params = matrix_normal_inv_wishart(ini_A, None, self.free_deg_MNIV, ini_Gamma)
         self.observation_params = matrix_normal_inv_wishart(ini_C, None, self.free_deg_MNIV, ini_Sigma)
 
@@ -506,7 +469,6 @@ class GPI_model:
         self.internal_params.set_scale(self.Gamma[-1])
         self.internal_params.m_mean = self.A[-1]
         self.fitted = True
-        self._stk = {}
         return self.x_basis, ini_cov
 
     def _spd_inv(self, S, what):
@@ -643,7 +605,6 @@ class GPI_model:
             self.indexes = []
         self.y_train, self.x_train = [], []
         self.N = 0
-        self._stk = {}
 
     def reinit_LDS(self, save_last=False, save_last_diag=False):
         """GPI_model.py:437-457: back to the default LDS parameters (or keep the last ones) and fresh MNIW priors."""
@@ -658,7 +619,6 @@ class GPI_model:
         eye = self._eye()
         self.internal_params = matrix_normal_inv_wishart(ini[0], eye, self.free_deg_MNIV, ini[1])
         self.observation_params = matrix_normal_inv_wishart(ini[2], eye, self.free_deg_MNIV, ini[3])
-        self._stk = {}
 
     def include_sample(self, index, x_train, y, x_warped=None, h=1.0, posterior=True, embedding=True, include_index=False):
         """GPI_model.py:325-351."""
@@ -708,7 +668,6 @@ class GPI_model:
             self.f_star_sm[-2] = m0 + mm(J, m1 - mm(A, m0))
             self.cov_f_sm[-2] = c0 + mm(mm(J, c1 - P), J, transB=True)
             self.f_star_sm[-1], self.cov_f_sm[-1] = m1, c1
-            self._stk = {}
 
     def bayesian_new_params(self, h, model_type="dynamic", full_data=False, q=None, force=False, snr=1.0):
         """GPI_model.py:966-1115, one-step estimation (full_data=False), dynamic model, shared grid."""
@@ -716,7 +675,6 @@ class GPI_model:
             return
         if full_data:
             raise NotImplementedError("bayesian_new_params: only the one-step update (full_data=False) is built")
-        self._stk = {}
         if 1 < self.N < self.estimation_limit or force:
             infos = []
             new_int = self.internal_params.posterior(1, self.f_star_sm[-1], self.f_star_sm[-2], defer=infos)
@@ -785,7 +743,6 @@ class GPI_model:
         for i in range(len(means)):
             self.f_star_sm[i + 1] = means[i]
             self.cov_f_sm[i + 1] = covs[i]
-        self._stk = {}
 
     def _backwards_graphed(self):
         """GPI_model.backwards (full RTS) with the step captured once: index t runs down on the device."""
@@ -793,7 +750,7 @@ class GPI_model:
         L = len(self.f_star)
         if L - 1 < 2:
             return self.backwards()
-        st = lambda lst: (lst.stack() if isinstance(lst, StackList) else torch.stack(lst))[1:]     # noqa: E731
+        st = lambda lst: lst.stack()[1:]     # noqa: E731
         M, Cv = st(self.f_star).clone(), st(self.cov_f).clone()          # smoothed in place below: the filtered lists stay
         A, G = st(self.A).contiguous(), st(self.Gamma).contiguous()
         nA, n = A.shape[0], M.shape[0]
@@ -814,9 +771,8 @@ class GPI_model:
             self._check_pending()
             Mv = M.reshape(n, -1)
             ops.rts_chain(Jb, Pb, AMb.reshape(n - 1, -1).contiguous(), Mv, Cv)
-            self.f_star_sm = StackList(torch.cat([self.f_star_sm[0].unsqueeze(0), M]))
-            self.cov_f_sm = StackList(torch.cat([self.cov_f_sm[0].unsqueeze(0), Cv]))
-            self._stk = {}
+            self.f_star_sm = StepList(torch.cat([self.f_star_sm[0].unsqueeze(0), M]))
+            self.cov_f_sm = StepList(torch.cat([self.cov_f_sm[0].unsqueeze(0), Cv]))
             return
         # T > 96: the two-line recursion as product lists (hgp_gemm_list_f64), two dependent launches per step and no other
         # arithmetic: what only reads filtered quantities is folded into addends first,
@@ -838,7 +794,6 @@ class GPI_model:
         for i in range(M.shape[0]):
             self.f_star_sm[i + 1] = M[i]
             self.cov_f_sm[i + 1] = Cv[i]
-        self._stk = {}
 
     def full_pass_weighted(self, x_trains, y_trains, resp, q=None, q_lat=None, snr=None, use_graphs=True):
         """GPI_model.py:377-406: filter / smooth / re-estimate over the members (resp > 0.99), then score everything.
@@ -864,7 +819,6 @@ class GPI_model:
         if dynamic:
             self.backwards()
         self._check_pending()
-        self._stk = {}
         return self.compute_sq_err_all(x_trains, y_trains), self.compute_q_lat_all(x_trains)
 
     # ------------------------------------------------------------------ a3 / a4
@@ -953,7 +907,8 @@ class GPI_model:
         if len(self.indexes) == 0:
             return out
         i_vals, first = self._steps(n, no_first)
-        sel = np.array([self._select(int(t)) for t in np.unique(i_vals)])           # distinct steps -> (ci, fi)
+        lens = (len(self.C), len(self.f_star), len(self.indexes))
+        sel = np.array([self._select(int(t), lens) for t in np.unique(i_vals)])     # distinct steps -> (ci, fi)
         step_pos = np.searchsorted(np.unique(i_vals), i_vals)
         ci_seg, fi_seg = sel[step_pos, 0], sel[step_pos, 1]
         ini_noise = 1e-2 * float(torch.mean(torch.diagonal(self.Sigma[0])))
@@ -967,8 +922,8 @@ class GPI_model:
             rep = order[start]
             g_ci, g_fi = ci_seg[rep], fi_seg[rep]
             pairs, inv = np.unique(np.stack([g_ci, g_fi], 1), axis=0, return_inverse=True)
-            means = ops.gemm_batched(self._S("C")[torch.as_tensor(pairs[:, 0], device=self.device)],
-                                     self._S("f_star")[torch.as_tensor(pairs[:, 1], device=self.device)]).reshape(-1, T)
+            means = ops.gemm_batched(self.C.stack()[torch.as_tensor(pairs[:, 0], device=self.device)],
+                                     self.f_star.stack()[torch.as_tensor(pairs[:, 1], device=self.device)]).reshape(-1, T)
             adds = np.where(codes % 2 == 1, ini_noise, 0.0)
             inv = inv.reshape(-1)
             quad = torch.zeros(n, dtype=f64, device=self.device)
@@ -978,15 +933,15 @@ class GPI_model:
                 seg_list = np.concatenate([order[start[g]:start[g] + counts[g]] for g in gm]).astype(np.int32)
                 im, ia, io, ic = ops.build_items(g_ci[gm].tolist(), adds[gm].tolist(), counts[gm].tolist())
                 grp_of_item = np.repeat(np.arange(len(gm)), [-(-c // ops.MAX_CHUNK) for c in counts[gm]])
-                quad, _, info = ops.score_groups(Y, means.contiguous(), self._S("Sigma"), im, ia, io, ic, seg_ids=seg_list,
+                quad, _, info = ops.score_groups(Y, means.contiguous(), self.Sigma.stack(), im, ia, io, ic, seg_ids=seg_list,
                                                  item_mean=inv[gm][grp_of_item].astype(np.int32))
                 ops.raise_on_info(info, "compute_sq_err_all")
             single = ~multi
             if single.any():  # member segments: each has its own Sigma_i and a single right-hand side
                 gs = np.nonzero(single)[0]
                 segs = torch.as_tensor(rep[gs], device=self.device)
-                Sst = self._S("Sigma")
-                sym = self._S_symmetric("Sigma")      # exactly symmetric stacks take the half-traffic path
+                Sst = self.Sigma.stack()
+                sym = self.Sigma.symmetric()      # exactly symmetric stacks take the half-traffic path
                 q1, _, info1 = ops.score_each(Y[segs].contiguous(), means.contiguous(), Sst, g_ci[gs].astype(np.int32),
                                               inv[gs].astype(np.int32), adds[gs], symmetric=sym)
                 ops.raise_on_info(info1, "compute_sq_err_all")
@@ -995,9 +950,9 @@ class GPI_model:
         # general path (GPI_model.py:535-545): every segment against the state of ITS step, on its own grid
         pairs, col = np.unique(np.stack([ci_seg, fi_seg], 1), axis=0, return_inverse=True)
         col = col.reshape(-1)
-        means = ops.gemm_batched(self._S("C")[torch.as_tensor(pairs[:, 0], device=self.device)],
-                                 self._S("f_star")[torch.as_tensor(pairs[:, 1], device=self.device)]).reshape(-1, T)
-        Sig = self._S("Sigma")[torch.as_tensor(pairs[:, 0], device=self.device)].contiguous()
+        means = ops.gemm_batched(self.C.stack()[torch.as_tensor(pairs[:, 0], device=self.device)],
+                                 self.f_star.stack()[torch.as_tensor(pairs[:, 1], device=self.device)]).reshape(-1, T)
+        Sig = self.Sigma.stack()[torch.as_tensor(pairs[:, 0], device=self.device)].contiguous()
         plan = self._pairs_plan(Ts, len(pairs))
         plan.update(self.x_basis.reshape(-1).contiguous(), means.contiguous(), Sig)
         ops.raise_on_info(plan.info, "pred_dist")
@@ -1024,12 +979,12 @@ class GPI_model:
             cur, prev, par, cov = [cur[only]], [prev[only]], [par[only]], [cov[only]]
         T = self.x_basis.shape[0]
         ix = lambda a: ops.to_dev(a, torch.int64, self.device)  # noqa: E731
-        Gam = self._S("Gamma")[ix(par)].clone()
+        Gam = self.Gamma.stack()[ix(par)].clone()
         if only is None or only == 0:
             Gam[0] = Gam[0] * h_ini                                  # GPI_model.py:293
-        out, info = ops.lat_error(self._S("f_star_sm")[ix(cur)].reshape(-1, T).contiguous(),
-                                  self._S("f_star_sm")[ix(prev)].reshape(-1, T).contiguous(), self._S("A")[ix(par)].contiguous(), Gam,
-                                  self._S("cov_f_sm")[ix(cov)].contiguous())
+        out, info = ops.lat_error(self.f_star_sm.stack()[ix(cur)].reshape(-1, T).contiguous(),
+                                  self.f_star_sm.stack()[ix(prev)].reshape(-1, T).contiguous(), self.A.stack()[ix(par)].contiguous(), Gam,
+                                  self.cov_f_sm.stack()[ix(cov)].contiguous())
         self._raise(info, "log_lat_error")
         return out - 0.5 * T * LOG2PI
 
@@ -1042,34 +997,52 @@ class GPI_model:
         n = x_trains.shape[0]
         if self.N == 0 or not self._is_dynamic():
             return torch.zeros(n, dtype=f64, device=self.device)
-        ent = self._stk.get("_lat_all")          # members' scores are kept until the model changes (the online loop asks every
-        key = (h_ini, len(self.indexes), len(self.Gamma), self.f_star_sm[-1].data_ptr(), self.cov_f_sm[-1].data_ptr())
-        if ent is None or ent[0] != key:         # cluster for them at every beat, GPI_HDP.py:1972; only one cluster changes)
-            ent = self._stk["_lat_all"] = (key, self._lat_all(h_ini))
+        # members' scores are kept until the model changes (the online loop asks every cluster for them at every beat,
+        # GPI_HDP.py:1972; only one cluster changes)
+        lat = self._memo_get("lat_all", self._LAT_LISTS, (h_ini, len(self.indexes)))
+        if lat is None:
+            lat = self._memo_put("lat_all", self._LAT_LISTS, self._lat_all(h_ini), (h_ini, len(self.indexes)))
         # ... and so is the column itself (zeros with the members' scores scattered in), with room to grow: while the model does
         # not change, a longer history only needs a longer view of it
-        col = self._stk.get("_lat_col")
-        if col is None or col[0] is not ent[1] or col[1].shape[0] < n:
+        buf = self._memo_get("lat_col", (), (lat,))
+        if buf is None or buf.shape[0] < n:
             buf = torch.zeros(max(64, 2 * n), dtype=f64, device=self.device)
-            buf[ops.to_dev(self.indexes, torch.int64, self.device)] = ent[1]
-            col = self._stk["_lat_col"] = (ent[1], buf)
-        return col[1][:n]
+            buf[ops.to_dev(self.indexes, torch.int64, self.device)] = lat
+            self._memo_put("lat_col", (), buf, (lat,))
+        return buf[:n]
+
+    _LAT_LISTS = ("f_star_sm", "cov_f_sm", "A", "Gamma")           # what _lat_all reads
+    _LDS_LISTS = ("A", "Gamma", "C", "Sigma")                      # what return_LDS_param_likelihood reads
 
     def _is_dynamic(self):
         """bool(any(Gamma[-1] != 0)) (GPI_model.py:551), looked up once per state of the list (a device round trip otherwise)."""
-        G = self.Gamma[-1]
-        key = (len(self.Gamma), G.data_ptr())
-        ent = getattr(self, "_dyn", None)
-        if ent is None or ent[0] != key:
-            ent = self._dyn = (key, bool(torch.any(G != 0)))
-        return ent[1]
+        dyn = self._memo_get("dyn", ("Gamma",))
+        if dyn is None:
+            dyn = self._memo_put("dyn", ("Gamma",), bool(torch.any(self.Gamma[-1] != 0)))
+        return dyn
 
     def _dyn_prior(self):
         """bool(any(Gamma_def != 0)) (GPI_model.py:470), looked up once per prior object."""
-        ent = getattr(self, "_dyn_def", None)
-        if ent is None or ent[0] is not self.Gamma_def:
-            ent = self._dyn_def = (self.Gamma_def, bool(torch.any(self.Gamma_def != 0)))
-        return ent[1]
+        dyn = self._memo_get("dyn_def", (), (self.Gamma_def,))
+        if dyn is None:
+            dyn = self._memo_put("dyn_def", (), bool(torch.any(self.Gamma_def != 0)), (self.Gamma_def,))
+        return dyn
+
+    def _defs_diagonal(self):
+        """Are the default scales (the MNIW priors' Sigma_def, Gamma_def) diagonal?  They are the initial sigma I / gamma I unless
+        a caller replaced them: checked once per pair of objects."""
+        defs = (self.Sigma_def, self.Gamma_def)
+        diag = self._memo_get("def_diag", (), defs)
+        if diag is None:
+            diag = self._memo_put("def_diag", (), all(bool(torch.equal(s_, torch.diag(torch.diagonal(s_)))) for s_ in defs), defs)
+        return diag
+
+    def _share_prior_memos(self, other):
+        """Take over what `other` knows about the prior tensors this model shares with it (gpmodel_deepcopy)."""
+        for name, extra in (("dyn_def", (self.Gamma_def,)), ("def_diag", (self.Sigma_def, self.Gamma_def))):
+            value = other._memo_get(name, (), extra)
+            if value is not None:
+                self._memo_put(name, (), value, extra)
 
     # ------------------------------------------------------------------ a9
     def return_LDS_param_likelihood(self, first=False):
@@ -1083,23 +1056,32 @@ class GPI_model:
         Ms, Ss, means, scales = [C_], [Sig_], [self.C_def], [self.Sigma_def]
         if self._dyn_prior():
             Ms.append(A_), Ss.append(Gam_), means.append(self.A_def), scales.append(self.Gamma_def)
-        # the prior scales are the initial sigma I / gamma I unless a caller replaced them: checked once per pair of objects
-        key = (id(self.Sigma_def), id(self.Gamma_def))
-        if getattr(self, "_def_diag_key", None) != key:
-            self._def_diag = all(bool(torch.equal(s_, torch.diag(torch.diagonal(s_)))) for s_ in scales)
-            self._def_diag_key = key
         out, info = ops.mniw_loglik(torch.stack(Ms).contiguous(), torch.stack(Ss).contiguous(), torch.stack(means).contiguous(),
-                                    None, torch.stack(scales).contiguous(), scale_is_diagonal=self._def_diag)
+                                    None, torch.stack(scales).contiguous(), scale_is_diagonal=self._defs_diagonal())
         self._raise(info, "return_LDS_param_likelihood")
         return torch.sum(out) / T * 100.0
 
     def lds_param_likelihood_value(self):
         """return_LDS_param_likelihood() as a host float, evaluated once per state of the model: the variational loop asks for
-        it at every evaluation of the bound (GPI_HDP.py:1838-1864), mostly for models that have not changed.  Stored with the
-        stack cache, which every method that changes the per-step lists resets."""
-        ent = self._stk.get("_lds_lik")
-        key = (len(self.A), self.A[-1].data_ptr(), self.Sigma[-1].data_ptr(), self.Gamma[-1].data_ptr())
-        if ent is None or ent[0] != key:
-            ent = self._stk["_lds_lik"] = (key, float(self.return_LDS_param_likelihood()))
-        return ent[1]
+        it at every evaluation of the bound (GPI_HDP.py:1838-1864), mostly for models that have not changed.  Memoised under the
+        stamps of the four parameter lists and the identity of the four prior tensors (_memo_get)."""
+        defs = (self.A_def, self.Gamma_def, self.C_def, self.Sigma_def)
+        lik = self._memo_get("lds_lik", self._LDS_LISTS, defs)
+        if lik is None:
+            lik = self._memo_put("lds_lik", self._LDS_LISTS, float(self.return_LDS_param_likelihood()), defs)
+        return lik
 
+
+def _step_list(name):
+    """model.<name>: one of the per-step lists, always a StepList - a plain list or tuple assigned to it is wrapped (the list
+    taken as it is), a StepList is kept as given."""
+    key = "_" + name
+
+    def put(self, value):
+        self.__dict__[key] = value if isinstance(value, StepList) else StepList(value)
+
+    return property(attrgetter(key), put)     # (a C-level getter: these are read in the host loops' inner loops)
+
+
+for _name in GPI_model._TENSOR_LISTS:
+    setattr(GPI_model, _name, _step_list(_name))

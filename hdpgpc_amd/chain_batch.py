@@ -140,7 +140,6 @@ def _run_group(jobs):
             gp.x_train.append(j.x[idx])
             gp.y_train.append(j.y[idx].reshape(-1, 1))
         gp.N += len(j.rest)
-        gp._stk = {}
         if bad[1] != 0:      # torch.linalg.solve / inv of the reference would have raised at that member
             raise torch.linalg.LinAlgError(f"posterior / backwards_pair: the input is not positive-definite (LDS step {bad[1]})")
         if bad[0] != 0 and gp.verbose:
@@ -157,7 +156,6 @@ def _run_group(jobs):
     for j in jobs:
         gp = j.gp
         gp._check_pending()
-        gp._stk = {}
         j.out = (gp.compute_sq_err_all(j.x, j.y), gp.compute_q_lat_all(j.x))
 
 

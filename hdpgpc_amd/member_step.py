@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from . import _ffi, ops
-from .GPI_model import StackList, matrix_normal_inv_wishart
+from .GPI_model import matrix_normal_inv_wishart
+from .steplist import StepList
 
 f64 = torch.float64
 _p = ops._ptr
@@ -75,10 +76,9 @@ class Chain:
         dev = gp.device
         ch = cls(T=T)
         for key in _STACKS:
-            lst = getattr(gp, _LISTS[key])
             shape = (T, 1) if key in ("F", "Fsm") else (T, T)
             buf = torch.empty((rows,) + shape, dtype=f64, device=dev)
-            buf[:L] = (lst.stack() if isinstance(lst, StackList) else torch.stack(list(lst))).reshape((L,) + shape)
+            buf[:L] = getattr(gp, _LISTS[key]).stack().reshape((L,) + shape)
             buf[L:].zero_()
             setattr(ch, key, buf)
         ch.pos = torch.tensor([L - 1], dtype=torch.int64, device=dev)
@@ -103,9 +103,11 @@ class Chain:
             setattr(self, key, buf)
 
     def bind_model(self, gp, L, n0):
-        """The model's lists as views of the first L rows of the stacks, its MNIW distributions as views of W with count n0."""
+        """The model's lists as views of the first L rows of the stacks, its MNIW distributions as views of W with count n0.
+        The only binder: kernels write the stacks and W in place, and NEW lists (new stamps, steplist.py) are what tells the model
+        that they did - whoever lets a step write rows a model can see binds again."""
         for key in _STACKS:
-            setattr(gp, _LISTS[key], StackList(getattr(self, key)[:L]))
+            setattr(gp, _LISTS[key], StepList(getattr(self, key)[:L]))
         W = self.W
         gp.internal_params = matrix_normal_inv_wishart(W[0, 0], W[1, 0], n0, W[2, 0])
         gp.observation_params = matrix_normal_inv_wishart(W[0, 1], W[1, 1], n0, W[2, 1])

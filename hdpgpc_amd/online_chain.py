@@ -39,13 +39,6 @@ f64 = torch.float64
 Candidates = namedtuple("Candidates", "est cols lds extra_lat extra_lds")
 
 
-def _defs_diagonal(g):
-    """Are the model's default scales (the MNIW priors' Sigma_def, Gamma_def) diagonal?"""
-    if getattr(g, "_def_diag_key", None) == (id(g.Sigma_def), id(g.Gamma_def)):
-        return g._def_diag
-    return all(bool(torch.equal(s_, torch.diag(torch.diagonal(s_)))) for s_ in (g.Sigma_def, g.Gamma_def))
-
-
 def _copy_rows(rows, src, dbuf, item, n):
     """One more block of the copy-list table `rows`: n doubles from byte address src[i] to item item[i] (n doubles each) of dbuf."""
     src, item = np.atleast_1d(np.asarray(src, dtype=np.int64)), np.atleast_1d(np.asarray(item, dtype=np.int64))
@@ -201,25 +194,32 @@ class OnlinePool:
         sl = _Slot()
         sl.g, sl.N, sl.rows = g, L - 1, max(8, 2 * L)
         sl.ch = Chain.from_model(g, sl.rows)
-        sl.def_diag = _defs_diagonal(g)
+        sl.def_diag = g._defs_diagonal()
         sl.bad0 = 0
         self._bind(sl)
         self._rebind_lists(sl, float(g.internal_params.n0))
         return sl
 
-    def _rebind_lists(self, sl, n0):
-        """The model's lists and MNIW objects as views of the slot's stacks."""
+    def _rebind_lists(self, sl, n0, lat=None):
+        """The model's lists and MNIW objects as views of the slot's stacks.  The new lists hold what the old ones held, so the
+        members' latent-transition scores stay valid: the memo of them (lat, when given: the scores after a commit) goes with
+        the new lists."""
         g = sl.g
+        if lat is None:
+            lat = self._lat_memo(g)
         sl.ch.bind_model(g, sl.N + 1, n0)
-        g._stk = {k: v for k, v in g._stk.items() if k in ("_lat_all", "_lat_col")}
+        if lat is not None:
+            g._memo_put("lat_all", g._LAT_LISTS, lat, (1.0, len(g.indexes)))
+
+    @staticmethod
+    def _lat_memo(g):
+        """The model's memoised latent-transition scores (compute_q_lat_all, h_ini = 1) if they are current, else None."""
+        return g._memo_get("lat_all", g._LAT_LISTS, (1.0, len(g.indexes)))
 
     def _more_rows(self, sl):
         sl.rows *= 2
         sl.ch.more_rows(sl.rows)
-        lat = sl.g._stk.get("_lat_all")
         self._rebind_lists(sl, float(sl.g.internal_params.n0))
-        if lat is not None:           # the key holds data pointers of the old stacks
-            sl.g._stk["_lat_all"] = (self._lat_key(sl.g), lat[1])
         self._base[sl.g._slot] = sl.ch.stack_ptrs()
         self.descs_dirty = True
 
@@ -340,7 +340,7 @@ class OnlinePool:
                                   (defs[2], self.MN_mean, nm + 1, tt), (defs[3], self.MN_scale, nm + 1, tt)):
                 _copy_rows(rows, t_.data_ptr(), buf, j, n)
             nl, nm = nl + 1, nm + 2
-            diag = diag and _defs_diagonal(e)
+            diag = diag and e._defs_diagonal()
         return np.concatenate(rows), nl, nm, diag
 
     def _score_copies(self, table, nl, nm, diag, info):
@@ -381,10 +381,6 @@ class OnlinePool:
         return cols
 
     # ------------------------------------------------------------------ commit
-    @staticmethod
-    def _lat_key(g, h_ini=1.0):
-        return (h_ini, len(g.indexes), len(g.Gamma), g.f_star_sm[-1].data_ptr(), g.cov_f_sm[-1].data_ptr())
-
     def commit(self, g, index, x_train, y):
         """include_weighted_sample(h = 1) + bayesian_new_params(1) of the cluster that absorbs the beat (no smoother).  The launches
         are enqueued and the host-side bookkeeping is done here; the two status words the reference looks at (a failed filter
@@ -395,9 +391,8 @@ class OnlinePool:
         T = self.T
         if sl.N + 2 > sl.rows:
             self._more_rows(sl)
-        lat_old = g._stk.get("_lat_all")
-        if lat_old is not None and lat_old[0] != self._lat_key(g):
-            lat_old = None
+        lat_old = self._lat_memo(g)
+        col = None if lat_old is None else g._memo_get("lat_col", (), (lat_old,))
         yv = g.cond_to_torch(y).reshape(-1, 1)
         self.ybuf.copy_(yv.reshape(1, T))
         c = g._slot
@@ -407,8 +402,7 @@ class OnlinePool:
         g.indexes.append(int(index))
         g.x_train.append(x_train)
         g.y_train.append(yv)
-        self._rebind_lists(sl, float(g.internal_params.n0) + 1.0)
-        info = None
+        info = new = None
         if lat_old is not None:
             # latent-transition scores: member 0 now reads the new last parameters, the new member is added; the rest is unchanged
             n = sl.N                                          # members now; rows 0..n
@@ -420,12 +414,11 @@ class OnlinePool:
             C2 = torch.stack((ps[1], ps[n - 1]))
             out, info = ops.lat_error(cur, prv, A2, G2, C2)
             out = out - 0.5 * T * LOG2PI
-            new = torch.cat([out[0:1], lat_old[1][1:], out[1:2]])
-            g._stk["_lat_all"] = (self._lat_key(g), new)
-            col = g._stk.get("_lat_col")                       # the scattered column: two entries change
-            if col is not None and col[0] is lat_old[1] and col[1].shape[0] > int(index):
-                col[1][ops.to_dev([g.indexes[0], int(index)], torch.int64, self.device)] = out
-                g._stk["_lat_col"] = (new, col[1])
+            new = torch.cat([out[0:1], lat_old[1:], out[1:2]])
+            if col is not None and col.shape[0] > int(index):  # the scattered column: two entries change
+                col[ops.to_dev([g.indexes[0], int(index)], torch.int64, self.device)] = out
+                g._memo_put("lat_col", (), col, (new,))
+        self._rebind_lists(sl, float(g.internal_params.n0) + 1.0, lat=new)
         self._pending = (sl, info)
 
     def finish_commit(self):
