@@ -132,7 +132,8 @@ void hgp_internal_colnorm_diag(const double* Z, const double* S, long sS, int T,
 void hgp_internal_sub_batched(const double* A, const double* B, long sA, long sB, long n, double* C, int b, hipStream_t st);
 
 // hgp_pairs_acc.hip
-int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, hipStream_t st);
+// flags_done: the plan update has written the routing flags already (k_plan_ops, TP <= 128)
+int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, bool flags_done, hipStream_t st);
 int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts, const double* first_noise,
                            const int32_t* sel, double* out_quad, double* out_logdet, int32_t* out_info, hipStream_t st);
 size_t hgp_internal_acc_bytes(int TP, int K, size_t* sizes /*[6]*/);

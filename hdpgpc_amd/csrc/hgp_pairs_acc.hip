@@ -440,9 +440,9 @@ size_t hgp_internal_acc_bytes(int TP, int K, size_t* sizes) {
   return tot;
 }
 
-int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, hipStream_t st) {
+int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, bool flags_done, hipStream_t st) {
   const int K = p->K, TP = p->TP, NB = p->NB;
-  hipLaunchKernelGGL(k_acc_flags, dim3(1), dim3(64), 0, st, p->d_scal, K, p->acc_tol, p->d_acc_list);
+  if (!flags_done) hipLaunchKernelGGL(k_acc_flags, dim3(1), dim3(64), 0, st, p->d_scal, K, p->acc_tol, p->d_acc_list);
   if (p->acc_tol < 0.0) return launch_status();   // explicit operator everywhere: nothing else to prepare
   if (NB <= 8)   // T <= 128: the plan update computed L^{-1} only; T > 128: d_A already holds L
     dispatch_nb_wave(TP, [&](auto nb) {

@@ -1,5 +1,12 @@
 // The pairs plan: the per-cluster operators of the explicit-operator pair kernels (hgp_pairs.hip) and of the solve-based kernel
 // (hgp_pairs_acc.hip), the layout of the plan's device buffer, and the C-ABI of the plan and of hgp_loglik_pairs_f64.
+//
+// hgp_pairs_plan_update, TP <= 128:  k_prep_build (K~, S, scalars) -> inverse factor Z = L^-1 (hgp_factor.hip) -> k_plan_ops<NB>
+// (M', a', ||K~^-1||_inf and the routing flags in ONE launch: every workgroup recomputes from Z the strips of Kinv = Z^T Z,
+// P = S Kinv and the two tiles of Q = Kinv P its tile pair of M' needs; Kinv, P and Q never reach memory) -> the operands of the
+// solve-based kernel for the flagged clusters (hgp_internal_acc_prep).
+// TP = 192, 256:  k_prep_build -> cooperative factor + inverse -> 3 x k_gemm (Kinv, P, Q in memory) -> k_prep_final -> k_acc_flags
+// -> operands (d_A holds L there, and the strips do not fit LDS).
 #include <algorithm>
 #include <new>
 
@@ -94,6 +101,19 @@ __global__ __launch_bounds__(256) void k_prep_build(PrepArgs a) {
   }
 }
 
+// M'[i][j] = c^2 (sym(Q) - sym(Kinv))[i][j], Q = Kinv S Kinv.  Stated once: k_prep_final and k_plan_ops compile the same expression.
+__device__ __forceinline__ double plan_mp_value(double c, double qij, double qji, double kij, double kji) {
+  return (c * c) * (0.5 * (qij + qji) - 0.5 * (kij + kji));
+}
+// Column order of M' (logical j -> physical jp).  The pairs kernel reads row k of M' as the A operands of the NH
+// row tiles of one half h (tiles NH h .. NH h + NH - 1): inside a half, tiles are interleaved two by two so that ONE
+// 16-byte load per lane (lane cc) yields the operands of tiles 2q and 2q + 1; an odd last tile stays contiguous.
+__device__ __forceinline__ int plan_mp_col(int j, int NHh) {
+  const int hh = j / (16 * NHh), tl = (j / 16) % NHh, cc = j % 16;
+  const int loc = (tl < 2 * (NHh / 2)) ? 32 * (tl / 2) + 2 * cc + (tl & 1) : 16 * (NHh - 1) + cc;
+  return 16 * NHh * hh + loc;
+}
+
 struct PrepFinalArgs {
   const double* Q;      // Kinv * S * Kinv
   const double* Kinv;
@@ -118,10 +138,7 @@ __global__ __launch_bounds__(256) void k_prep_final(PrepFinalArgs a) {
   const double* Ki = a.Kinv + (size_t)k * TP * TP;
   double* Mp = a.Mp + (size_t)k * TP * TP;
   // M' = c^2 (sym(Q) - sym(Kinv)) by 32 x 32 tiles: tile (bi, bj) and its mirror (bj, bi) are both read row-wise
-  // (coalesced) and the mirror is transposed through LDS (pitch 33).
-  // Column order of M' (logical j -> physical jp).  The pairs kernel reads row k of M' as the A operands of the NH
-  // row tiles of one half h (tiles NH h .. NH h + NH - 1): inside a half, tiles are interleaved two by two so that ONE
-  // 16-byte load per lane (lane cc) yields the operands of tiles 2q and 2q + 1; an odd last tile stays contiguous.
+  // (coalesced) and the mirror is transposed through LDS (pitch 33).  Column order: plan_mp_col.
   __shared__ double tq[32][33], tk[32][33];
   const int NHh = (TP / 16) / 2, nt = TP / 32;
   const int tx = tid & 31, ty = tid >> 5;   // 32 x 8 threads, 4 rows each
@@ -140,14 +157,8 @@ __global__ __launch_bounds__(256) void k_prep_final(PrepFinalArgs a) {
       const int y = ty + 8 * r;
       const int i = 32 * bi + y, j = 32 * bj + tx;
       double v = 0.0;
-      if (i < T && j < T)
-        v = (c * c) * (0.5 * (Q[(size_t)i * TP + j] + tq[tx][y]) - 0.5 * (Ki[(size_t)i * TP + j] + tk[tx][y]));
-      int jp = j;
-      if (a.interleave) {
-        const int hh = j / (16 * NHh), tl = (j / 16) % NHh, cc = j % 16;
-        const int loc = (tl < 2 * (NHh / 2)) ? 32 * (tl / 2) + 2 * cc + (tl & 1) : 16 * (NHh - 1) + cc;
-        jp = 16 * NHh * hh + loc;
-      }
+      if (i < T && j < T) v = plan_mp_value(c, Q[(size_t)i * TP + j], tq[tx][y], Ki[(size_t)i * TP + j], tk[tx][y]);
+      const int jp = a.interleave ? plan_mp_col(j, NHh) : j;
       Mp[(size_t)i * TP + jp] = v;
     }
   }
@@ -179,6 +190,221 @@ __global__ __launch_bounds__(256) void k_prep_final(PrepFinalArgs a) {
   if (tid == 0) atomicMax(reinterpret_cast<unsigned long long*>(a.scal + 8 * k + 6), (unsigned long long)__double_as_longlong(red[0]));
 }
 
+// ------------------------------------------------------------------ one launch behind the inverse (TP <= 128)
+// M', a', ||K~^-1||_inf and the routing flags from Z = L^-1, without Kinv, P or Q in global memory.  One workgroup per
+// (cluster k, tile pair I < J) recomputes what its two output tiles M'[I][J], M'[J][I] depend on:
+//   Kinv[:, I], Kinv[:, J] (block columns) and Kinv[I, :], Kinv[J, :] (block rows) from Z   - the chains of Kinv = Z^T Z,
+//   P[:, I] = S Kinv[:, I], P[:, J]                                                         - the chains of P = S Kinv,
+//   Q_IJ = Kinv[I, :] P[:, J], Q_JI = Kinv[J, :] P[:, I]                                    - the chains of Q = Kinv P,
+// every tile by ONE accumulator over ascending k-steps of 4 (exactly k_gemm's order: the operators keep their bits).  The
+// redundant MFMAs cost nothing: the chip is otherwise idle.  A block row is never taken as the transpose of a block column
+// (nothing here relies on Z^T Z being symmetric bit for bit).  The diagonal tile (I, I) needs the strips of block I only, so
+// the workgroup of pair (I, I+1) makes it as well (one more Q tile), with a'[16 I ..] and the row sums of |Kinv|; the last
+// pair also serves block NB-1.  K NB (NB-1)/2 workgroups: 224 at K = 8, NB = 8 - one round on 256 CUs.  The last of those
+// workgroups to finish (an atomic counter behind a fence: nobody waits for anybody) computes the routing flags of all clusters
+// and re-arms the counter and the two counters of the fall-back list.
+struct PlanOpsArgs {
+  const double* Z;      // [K,TP,TP] L^-1, zeros above the diagonal
+  const double* S;      // [K,TP,TP] 0.5 (Sigma + Sigma^T)
+  const double* mean;   // [K,T]
+  double* scal;
+  int T, K;
+  double* Mp;           // [K,TP,TP], tile-pair interleaved columns
+  double* ap;           // [K,TP]
+  double tol;           // accuracy threshold of the routing flags (hgp_pairs_plan_set_accuracy)
+  int32_t* acc_list;
+  int32_t* fb;
+  unsigned* done;       // finished workgroups, of those that serve a diagonal block, of this launch; zero between launches
+};
+
+template <int NB>
+struct PlanOpsLds {
+  static constexpr int TILE = 256;        // acc layout [lane][4]: the B operand of k-step s is element s of the lane's d4
+  static constexpr int TILE_T = 16 * 17;  // row-major, pitch 17: read as the A operand X[c][4 s + g] (and transposed for M')
+  static constexpr int COL = 0, ROW = COL + 2 * NB * TILE, P = ROW + 2 * NB * TILE_T, END = P + 2 * NB * TILE;
+  static constexpr int QT = END, DOUBLES = END + 4 * TILE_T;   // Q_IJ, Q_JI, Q_II, Q_JJ; NB = 8: 109 056 bytes
+  static constexpr size_t BYTES = (size_t)DOUBLES * sizeof(double);
+};
+
+// routing flags of all clusters (scal[8k+7], acc_list = [count, ids...] ascending): one thread
+__device__ inline void plan_acc_flags(double* scal, int K, double tol, int32_t* acc_list) {
+  int n = 0;
+  for (int k = 0; k < K; ++k) {
+    // ||K~^-1||_inf was accumulated by atomics of other workgroups: read it past this CU's vector cache
+    const double ninf = __longlong_as_double((long long)__hip_atomic_load(
+        reinterpret_cast<unsigned long long*>(scal + 8 * k + 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const double ck = scal[8 * k] * ninf;
+    const double bound = F64_EPS * ck * ck;
+    const bool flag = (tol == 0.0) || (tol > 0.0 && !(bound <= tol));   // NaN bound -> solve-based
+    scal[8 * k + 7] = flag ? 1.0 : 0.0;
+    if (flag) acc_list[1 + n++] = k;
+  }
+  acc_list[0] = n;
+}
+
+template <int NB>
+__global__ __launch_bounds__(128 * NB) void k_plan_ops(PlanOpsArgs a) {
+  using L = PlanOpsLds<NB>;
+  constexpr int TP = 16 * NB, NK = 4 * NB, NOFF = NB * (NB - 1) / 2;
+  constexpr int TRIP = (NB == 6) ? 12 : (NB == 2 ? 8 : 16);   // k-steps whose operand loads are issued together (NK % TRIP == 0)
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  __shared__ int last;
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // one workgroup per pair t of the strictly upper tiles of cluster k, by columns: (0,1), (0,2), (1,2), ...
+  const int k = blockIdx.x / NOFF;
+  int I, J = 1;
+  {
+    int t = blockIdx.x % NOFF;
+    while (t >= J) t -= J++;
+    I = t;
+  }
+  // the diagonal tiles need nothing but the strips of their own block, which every workgroup of that block holds anyway:
+  // (I, I+1) also makes tile (I, I), and the last pair (NB-2, NB-1) also tile (NB-1, NB-1) - no second round of workgroups
+  const bool dI = J == I + 1, dJ = dI && J == NB - 1;
+  const int T = a.T;
+  const double* Z = a.Z + (size_t)k * TP * TP;
+  const double* S = a.S + (size_t)k * TP * TP;
+  double* colS = smem + L::COL;   // [2][NB] tiles (a, I), (a, J) of Kinv
+  double* rowS = smem + L::ROW;   // [2][NB] tiles (I, a), (J, a) of Kinv
+  double* pS = smem + L::P;       // [2][NB] tiles (t, I), (t, J) of P
+  double* qT = smem + L::QT;      // [4] Q_IJ, Q_JI, Q_II, Q_JJ
+  const int q = wave / NB, wa = wave % NB;   // this wave's strip (0: I, 1: J) and tile index along it
+  const int Bq = q ? J : I;
+
+  // ---- Kinv strips: tile (wa, Bq) of the block column and tile (Bq, wa) of the block row, from the same two operand streams
+  {
+    const double* Za = Z + 16 * wa + c;
+    const double* Zb = Z + 16 * Bq + c;
+    d4 ccol = (d4){0.0, 0.0, 0.0, 0.0}, crow = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k0 = 0; k0 < NK; k0 += TRIP) {
+      double za[TRIP], zb[TRIP];
+#pragma unroll
+      for (int u = 0; u < TRIP; ++u) {
+        const int kk = 4 * (k0 + u) + g;
+        za[u] = Za[(size_t)kk * TP];
+        zb[u] = Zb[(size_t)kk * TP];
+      }
+      // every load of the trip is in flight before its first MFMA: left alone, the scheduler trades them for occupancy this
+      // kernel cannot use and exposes one L2 latency per k-step
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < TRIP; ++u) {
+        ccol = mfma(za[u], zb[u], ccol);   // Kinv[16 wa + .][16 Bq + .]
+        crow = mfma(zb[u], za[u], crow);   // Kinv[16 Bq + .][16 wa + .]
+      }
+    }
+    *reinterpret_cast<d4*>(colS + (q * NB + wa) * L::TILE + lane * 4) = ccol;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rowS[(q * NB + wa) * L::TILE_T + (g + 4 * r) * 17 + c] = crow[r];
+  }
+  __syncthreads();
+
+  // ---- P strips: tile (wa, Bq) of P = S Kinv; A operand from S (L2), B operand from the block column in LDS
+  {
+    const double* Scol = S + (size_t)g * TP + 16 * wa + c;   // S[16 wa + c][4 u + g] = S[4 u + g][16 wa + c]: S is exactly symmetric,
+                                                            // and rows of 16 lanes read 128 contiguous bytes this way
+    const double* cs = colS + q * NB * L::TILE + lane * 4;
+    d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k0 = 0; k0 < NK; k0 += TRIP) {
+      double sv[TRIP];
+#pragma unroll
+      for (int u = 0; u < TRIP; ++u) sv[u] = Scol[(size_t)(4 * (k0 + u)) * TP];
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < TRIP; ++u) acc = mfma(sv[u], cs[((k0 + u) >> 2) * L::TILE + ((k0 + u) & 3)], acc);
+    }
+    *reinterpret_cast<d4*>(pS + (q * NB + wa) * L::TILE + lane * 4) = acc;
+  }
+  __syncthreads();
+
+  // ---- Q tiles (waves 0 .. 3) beside a' and the row sums of |Kinv| (two further waves; NB = 2 has none: waves 2, 3 do both)
+  if (wave < 2 || (wave == 2 && dI) || (wave == 3 && dJ)) {
+    // wave 0: Q_IJ = Kinv[I, :] P[:, J];  1: Q_JI = Kinv[J, :] P[:, I];  2: Q_II = Kinv[I, :] P[:, I];  3: Q_JJ = Kinv[J, :] P[:, J]
+    const int sr = wave & 1, sp = (wave < 2) ? 1 - sr : sr;
+    const double* rs_ = rowS + sr * NB * L::TILE_T + c * 17 + g;
+    const double* ps = pS + sp * NB * L::TILE + lane * 4;
+    d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u < NK; ++u) acc = mfma(rs_[(u >> 2) * L::TILE_T + 4 * (u & 3)], ps[(u >> 2) * L::TILE + (u & 3)], acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) qT[wave * L::TILE_T + (g + 4 * r) * 17 + c] = acc[r];
+  }
+  constexpr int WA = NB > 2 ? 4 : 2;   // waves WA, WA + 1: a' of block I, of block J
+  if ((wave == WA && dI) || (wave == WA + 1 && dJ)) {
+    // a'[i] = c sum_j Kinv[j][i] mean[j], row sums of |Kinv|: serially over j = 0 .. T-1, from the block column
+    const int sq = wave - WA;
+    const double* cs = colS + sq * NB * L::TILE;
+    const double cc = a.scal[8 * k];
+    const double* mu = a.mean + (size_t)k * T;
+    const int i = 16 * (sq ? J : I) + c;
+    double s = 0.0, rs = 0.0;
+    if (g == 0 && i < T) {
+#pragma unroll 8
+      for (int j = 0; j < T; ++j) {
+        const int jj = j & 15;
+        const double kij = cs[(j >> 4) * L::TILE + (16 * (jj & 3) + c) * 4 + (jj >> 2)];   // Kinv[j][i]
+        s = fma(kij, mu[j], s);
+        rs += fabs(kij);
+      }
+    }
+    if (g == 0) a.ap[(size_t)k * TP + i] = cc * s;
+    const double rmax = wave_allreduce<true>(fmax(0.0, rs));
+    // ||K~^{-1}||_inf >= ||K~^{-1}||_2: maximum over the blocks (non-negative doubles order like their bit patterns;
+    // k_prep_build zeroes the slot)
+    if (lane == 0) atomicMax(reinterpret_cast<unsigned long long*>(a.scal + 8 * k + 6), (unsigned long long)__double_as_longlong(rmax));
+  }
+  __syncthreads();
+
+  // ---- M' tiles (I, J), (J, I) and the diagonal tiles this workgroup makes: zero outside T, tile-pair interleaved columns
+  {
+    const double cc = a.scal[8 * k];
+    double* Mp = a.Mp + (size_t)k * TP * TP;
+    constexpr int NHh = NB / 2;
+    for (int e = tid; e < 1024; e += 128 * NB) {
+      const int m = e >> 8, rr = (e >> 4) & 15, c2 = e & 15;   // m: 0 (I, J), 1 (J, I), 2 (I, I), 3 (J, J)
+      if ((m == 2 && !dI) || (m == 3 && !dJ)) continue;
+      const int sm = m & 1, so = (m < 2) ? 1 - sm : sm;        // strips holding row bi and row bj of tile (bi, bj)
+      const int bi = sm ? J : I, bj = so ? J : I;
+      const int qa = m, qb = (m < 2) ? 1 - m : m;              // Q tile (bi, bj) and its mirror (bj, bi)
+      const int i = 16 * bi + rr, j = 16 * bj + c2;
+      double v = 0.0;
+      if (i < T && j < T)
+        v = plan_mp_value(cc, qT[qa * L::TILE_T + rr * 17 + c2], qT[qb * L::TILE_T + c2 * 17 + rr],
+                          rowS[(sm * NB + bj) * L::TILE_T + rr * 17 + c2], rowS[(so * NB + bi) * L::TILE_T + c2 * 17 + rr]);
+      Mp[(size_t)i * TP + plan_mp_col(j, NHh)] = v;
+    }
+  }
+
+  // ---- the last of the K (NB - 1) workgroups that accumulate ||K~^-1||_inf routes the clusters.  One fence per workgroup, by
+  // the thread that counts, behind the barrier that orders the workgroup's atomic maxima before it (a fence in every wave of
+  // every workgroup writes the L2 back thousands of times per launch: 108 us for this kernel at NB = 8).
+  if (!dI) return;
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    last = atomicAdd(a.done, 1u) == (unsigned)(a.K * (NB - 1)) - 1u ? 1 : 0;
+  }
+  __syncthreads();
+  if (last && tid == 0) {
+    __threadfence();
+    plan_acc_flags(a.scal, a.K, a.tol, a.acc_list);
+    a.fb[0] = 0;                    // fall-back list of k_pairs: its two counters start every plan state at zero
+    a.fb[1 + PAIRS_FB_CAP] = 0;     // (a killed launch cannot leave them set)
+    *a.done = 0u;
+  }
+}
+
+template <int NB>
+int launch_plan_ops(const PlanOpsArgs& a, hipStream_t st) {
+  const size_t lds = PlanOpsLds<NB>::BYTES;
+  if (int rc = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_plan_ops<NB>), lds)) return rc;
+  hipLaunchKernelGGL(k_plan_ops<NB>, dim3(a.K * (NB * (NB - 1) / 2)), dim3(128 * NB), lds, st, a);
+  return launch_status();
+}
+
 static int tp_for(int n) {   // padded size: wave kernels {32,64,96,128}, cooperative kernels {192,256}
   if (n <= HGP_MAX_T_WAVE) return 16 * nb_for(n);
   return n <= 192 ? 192 : 256;
@@ -202,8 +428,8 @@ size_t plan_layout(hgp_pairs_plan* p, int T, int Ts_max, int K, char* base) {
   take(p->d_A, mat);   // K~ then L
   take(p->d_S, mat);
   take(p->d_Z, mat);
-  take(p->d_Kinv, mat);
-  take(p->d_P, mat);
+  take(p->d_Kinv, mat);   // Kinv, P, Q: cooperative sizes only (TP <= 128: k_plan_ops keeps them in LDS; the areas keep their size)
+  take(p->d_P, mat);      // TP <= 128: first word = completion counter of k_plan_ops
   take(p->d_Q, mat);
   take(p->d_Mp, mat);
   take(p->d_ap, (size_t)K * TP * sizeof(double));
@@ -275,6 +501,11 @@ int hgp_pairs_plan_create(hgp_pairs_plan** plan, int T, int Ts_max, int K, const
     delete p;
     return 1000 + (int)hipGetLastError();
   }
+  // completion counter of k_plan_ops: first word of the P area, which the one-wave sizes do not use otherwise
+  if (!p->coop && hipMemset(p->d_P, 0, 256) != hipSuccess) {
+    delete p;
+    return 1000 + (int)hipGetLastError();
+  }
   if (p->coop && hipMemset(p->d_eflags, 0, (p->nscr + 1) * sizeof(int32_t)) != hipSuccess) {
     delete p;
     return 1000 + (int)hipGetLastError();
@@ -304,6 +535,15 @@ int hgp_pairs_plan_update(hgp_pairs_plan* p, const double* x_basis, const double
   fa.inv_info = 1;
   fa.symmetric = 1;   // k_prep_build writes K~ from (x_i - x_j)^2: exactly symmetric
   if (int rc = hgp_internal_chol_inverse(fa, p->NB, st)) return rc;
+  if (!p->coop) {
+    // TP <= 128: M', a', ||K~^-1||_inf and the routing flags in one launch behind the inverse; Kinv, P, Q never reach memory
+    PlanOpsArgs oa{p->d_Z, p->d_S, mean, p->d_scal, T, K, p->d_Mp, p->d_ap, p->acc_tol, p->d_acc_list, p->d_fb,
+                   reinterpret_cast<unsigned*>(p->d_P)};
+    if (int rc = dispatch_nb_wave(TP, [&](auto nb) { return launch_plan_ops<decltype(nb)::value>(oa, st); })) return rc;
+    // clusters whose explicit operator would lose digits take the solve-based kernel: packed operands of L, Sigma
+    int rc = hgp_internal_acc_prep(p, mean, /*flags_done=*/true, st);
+    return rc ? rc : launch_status();
+  }
   const long sm = (long)TP * TP;
   GemmArgs g1{p->d_Z, p->d_Z, p->d_Kinv, TP, TP, TP, TP, TP, TP, sm, sm, sm, 1.0, 0.0, 1, 0};     // Kinv = Z^T Z
   GemmArgs g2{p->d_S, p->d_Kinv, p->d_P, TP, TP, TP, TP, TP, TP, sm, sm, sm, 1.0, 0.0, 0, 0};    // P = S Kinv
@@ -316,7 +556,7 @@ int hgp_pairs_plan_update(hgp_pairs_plan* p, const double* x_basis, const double
   // overflow-area flags: a launch that was killed mid-flight must not leave areas marked busy for the next one
   if (p->d_eflags && p->nscr > 0 && hipMemsetAsync(p->d_eflags, 0, (p->nscr + 1) * sizeof(int32_t), st) != hipSuccess) return launch_status();
   // clusters whose explicit operator would lose digits take the solve-based kernel: flags + packed operands of L, Sigma
-  int rc = hgp_internal_acc_prep(p, mean, st);
+  int rc = hgp_internal_acc_prep(p, mean, /*flags_done=*/false, st);
   return rc ? rc : launch_status();
 }
 
