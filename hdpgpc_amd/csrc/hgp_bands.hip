@@ -93,13 +93,23 @@ __global__ __launch_bounds__(256) void k_bands_prep(const double* __restrict__ x
   }
 }
 
+// The dynamic LDS of k_bands<RT>, sized by the run-time tile count nb <= 4 RT
+template <int RT>
+struct BandsLds {
+  static constexpr int BN_CT = bands_ct(RT), BN_P = 16 * BN_CT;
+  __host__ __device__ static constexpr int red_off(int nb) { return nb * BN_CT * 256; }   // doubles
+  __host__ __device__ static constexpr size_t bytes(int nb) { return sizeof(double) * ((size_t)red_off(nb) + 3 * WAVES * BN_P); }
+  static_assert(bytes(4 * RT) <= LDS_MAX_BYTES, "k_bands: LDS");
+  __device__ static __forceinline__ double* Xs(double* smem) { return smem; }                          // [nb * BN_CT tiles][4][64]
+  __device__ static __forceinline__ double* red(double* smem, int nb) { return smem + red_off(nb); }   // [3][WAVES][BN_P]
+};
+
 template <int RT>
 __global__ __launch_bounds__(256) void k_bands(BandArgs a) {
   constexpr int BN_CT = bands_ct(RT), BN_P = 16 * BN_CT;   // queries per panel
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int T = a.T, nb = a.nb, Q = a.Q;
-  double* Xs = smem;                        // [nb * BN_CT tiles][4][64]
-  double* red = smem + nb * BN_CT * 256;    // [3][WAVES][BN_P]
+  double *Xs = BandsLds<RT>::Xs(smem), *red = BandsLds<RT>::red(smem, nb);
   const int s = blockIdx.x, tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int g = lane >> 4, c = lane & 15;
@@ -226,7 +236,7 @@ __global__ __launch_bounds__(256) void k_bands(BandArgs a) {
 template <int RT>
 int launch_bands(const BandArgs& a, hipStream_t st) {
   constexpr int BN_CT = bands_ct(RT), BN_P = 16 * BN_CT;
-  const size_t lds = sizeof(double) * ((size_t)a.nb * BN_CT * 256 + 3 * WAVES * BN_P);
+  const size_t lds = BandsLds<RT>::bytes(a.nb);
   if (int rc = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_bands<RT>), lds)) return rc;
   const int npanels = (a.Q + BN_P - 1) / BN_P;
   int ny = (768 + a.S - 1) / a.S;   // enough workgroups to fill the chip when the call holds few states

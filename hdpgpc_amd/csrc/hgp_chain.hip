@@ -224,16 +224,29 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_inv_rhs(InvRhsArgs a) {
 // no padding at T = 90): no workgroup barrier inside the factorisation - the wave that owns block K + 1 solves only that panel tile,
 // updates its diagonal tile from the accumulator, factors it and publishes W_{K+1} and Z_{K+1} while the others are still in the
 // trailing update of step K.  The barrier version above spends 4.5 us per block step for 1.2 us of diag16_acc.
+// Its dynamic LDS: the factorisation's buffers (three row buffers, W and Z of every block, per-wave scratch), red[8], then the
+// factorisation's flag block with the waves' status words behind it.
+template <int NB>
+struct CoophInvLds {
+  using C = CoopH<NB>;
+  using Df = typename C::template DfLds<1>;
+  static constexpr int DF = 0, RED = DF + Df::DOUBLES, FLAGS = RED + 8;   // doubles
+  static constexpr size_t BYTES = sizeof(double) * FLAGS + sizeof(int) * C::DF_INTS;
+  static_assert(RED % 2 == 0 && BYTES <= LDS_MAX_BYTES, "k_cooph_inv_rhs: LDS");
+  HGP_LDS_DOUBLES(df, DF)     // base of the Df members
+  HGP_LDS_DOUBLES(red, RED)   // [8]
+  HGP_LDS_INTS(flags, FLAGS, 0)
+  HGP_LDS_INTS(redi, FLAGS, C::DF_REDI)
+};
+
 template <int NB>
 __global__ __launch_bounds__(64 * CoopH<NB>::NW) void k_cooph_inv_rhs(InvRhsArgs a) {
   using C = CoopH<NB>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* row0 = smem;                       // three row buffers, W of every block, Z of every block: [NB] tiles each
-  double* Wall = row0 + 3 * NB * 256;
-  double* zbuf = Wall + NB * 256;
-  double* scr_all = zbuf + NB * 256;         // [NW][DIAG_SCR]
-  double* red = scr_all + C::NW * DIAG_SCR;  // [8]
-  int* flags = reinterpret_cast<int*>(red + 8);   // [16 + NB] + [8] status words
+  using L = CoophInvLds<NB>;
+  using Df = typename L::Df;
+  double *df = L::df(smem), *red = L::red(smem);
+  int *flags = L::flags(smem), *redi = L::redi(smem);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int g = lane >> 4, c = lane & 15;
   const int T = a.T, nblk = (T + 15) >> 4;
@@ -245,7 +258,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW) void k_cooph_inv_rhs(InvRhsArgs
     if (Jq == 0 && !a.Linv && threadIdx.x == 0 && a.info && (!a.rhs || (a.rhs_on && a.rhs_on[m] == 0))) a.info[m] = 0;
     return;
   }
-  double* scr = scr_all + wave * DIAG_SCR;
+  double* scr = Df::scr(df) + wave * DIAG_SCR;
   const double* A = a.A + (size_t)m * T * T;
   d4 U[C::NT];
 #pragma unroll
@@ -270,7 +283,8 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW) void k_cooph_inv_rhs(InvRhsArgs
   }
   PivotAcc pa;
   pa.init();
-  cooph_factor_df<NB, 1>(U, row0, row0 + NB * 256, row0 + 2 * NB * 256, Wall, scr, flags, wave, lane, pa, T, nullptr, &RA, &RB, zbuf);
+  cooph_factor_df<NB, 1>(U, Df::row0(df), Df::row1(df), Df::row2(df), Df::Wall(df), scr, flags, wave, lane, pa, T, nullptr, &RA, &RB,
+                         Df::zbuf(df));
   double* Z = (is_rhs ? a.rhs_out : a.Linv) + (size_t)m * T * T;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -283,7 +297,6 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW) void k_cooph_inv_rhs(InvRhsArgs
     }
   }
   if (Jq == (a.Linv ? 0 : nblk) && a.info) {   // the first panel sees every pivot: the earliest bad one over the waves
-    int* redi = flags + 16 + NB;
     if (lane == 0) redi[wave] = pa.info;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -297,7 +310,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW) void k_cooph_inv_rhs(InvRhsArgs
 
 template <int NB>
 int launch_cooph_inv_rhs(const InvRhsArgs& a, hipStream_t st) {
-  const size_t lds = sizeof(double) * ((size_t)5 * NB * 256 + CoopH<NB>::NW * DIAG_SCR + 8) + sizeof(int) * (16 + NB + 8);
+  const size_t lds = CoophInvLds<NB>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_cooph_inv_rhs<NB>), lds)) return rc_;
   hipLaunchKernelGGL(k_cooph_inv_rhs<NB>, dim3(a.b, 2 * ((a.T + 15) >> 4)), dim3(64 * CoopH<NB>::NW), lds, st, a);
   return launch_status();
@@ -482,13 +495,21 @@ struct RtsArgs {
 
 constexpr int RTS_WAVES = 12;   // three waves per SIMD: the LDS operand latency of one hides under the MFMAs of the others
 
+struct RtsLds {
+  static constexpr int PITCH = 100;     // row pitch (doubles) of the two staged matrices
+  static constexpr int JL = 0, DL = JL + 96 * PITCH, VL = DL + 96 * PITCH, ML = VL + 96, DOUBLES = ML + 96;
+  static constexpr size_t BYTES = sizeof(double) * DOUBLES;
+  static_assert(DL % 2 == 0 && BYTES <= LDS_MAX_BYTES, "k_rts_chain: LDS");
+  HGP_LDS_DOUBLES(Jl, JL)   // [96][PITCH]
+  HGP_LDS_DOUBLES(Dl, DL)   // [96][PITCH]  D, then X
+  HGP_LDS_DOUBLES(vl, VL)   // [96]  m_{t+1} - A_t m_t
+  HGP_LDS_DOUBLES(ml, ML)   // [96]  m_{t+1} (smoothed), then m_t
+};
+
 __global__ __launch_bounds__(64 * RTS_WAVES) void k_rts_chain(RtsArgs a) {
-  constexpr int NBR = 6, PITCH = 100;
+  constexpr int NBR = 6, PITCH = RtsLds::PITCH;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* Jl = smem;                    // [96][PITCH]
-  double* Dl = Jl + 96 * PITCH;         // [96][PITCH]  D, then X
-  double* vl = Dl + 96 * PITCH;         // [96]  m_{t+1} - A_t m_t
-  double* ml = vl + 96;                 // [96]  m_{t+1} (smoothed), then m_t
+  double *Jl = RtsLds::Jl(smem), *Dl = RtsLds::Dl(smem), *vl = RtsLds::vl(smem), *ml = RtsLds::ml(smem);
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int T = a.T;
@@ -711,7 +732,7 @@ int hgp_rts_chain_f64(const double* J, const double* P, const double* AM, double
   if (T > 96) return -2;
   if (n < 2) return 0;
   RtsArgs a{J, P, AM, M, Cv, n, T};
-  const size_t lds = sizeof(double) * (2 * 96 * 100 + 2 * 96);
+  const size_t lds = RtsLds::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_rts_chain), lds)) return rc_;
   hipLaunchKernelGGL(k_rts_chain, dim3(1), dim3(64 * RTS_WAVES), lds, (hipStream_t)stream, a);
   return launch_status();

@@ -117,11 +117,36 @@ __device__ __forceinline__ void solve_panels(const double* __restrict__ Lp, cons
 // pair kernels with a packed output (cooph_factor_df<NB, 2>) instead of the four-wave barrier version - the factor was 146 of the
 // 385 / 515 us of a call, and the panel solves behind it are spread over twice the waves.  a9 runs the eight-wave kernel only;
 // a8 keeps the four-wave one for large batches (launch_coop_lat).
-template <int NB, bool DF>
+//
+// The dynamic LDS of both kernels (LAT: k_coop_lat, which adds rvec).  First what the factorisation uses - DF: the buffers of
+// cooph_factor_df, fred[16], its flag block with the waves' status words;  else Coop<NB>'s layout - then red[8], the partial sums of
+// the kernel, and rvec[16 NB].  `stage` of k_coop_lat's Gram phase ([NWK][DIAG_SCR]) is the factorisation's diag16 scratch (DF) or
+// row buffer (else), free by then.
+template <int NB, bool DF, bool LAT = false>
 struct MatlikLds {
-  static constexpr int NWK = DF ? CoopH<NB>::NW : WAVES;
-  // DF: three row buffers + W of every block + per-wave diag16 scratch + red[16] + flags;  else Coop<NB>'s layout
-  static constexpr int DOUBLES = DF ? (4 * NB * 256 + NWK * DIAG_SCR + 16 + (16 + NB + 16) / 2 + 2) : Coop<NB>::LDS_DOUBLES;
+  using H = CoopH<NB>;
+  using Df = typename H::template DfLds<2>;
+  static constexpr int NWK = DF ? H::NW : WAVES;
+  static constexpr int FRED = Df::DOUBLES, FLAGS = FRED + 16;   // doubles
+  // 12 ints more than the flag block holds: they stay, the launch size is not this layout's to change
+  static constexpr int FLAGS_DOUBLES = (H::DF_INTS + 8) / 2 + 2;
+  static constexpr int RED = DF ? FLAGS + FLAGS_DOUBLES : Coop<NB>::LDS_DOUBLES, RVEC = RED + 8, DOUBLES = RVEC + (LAT ? 16 * NB : 0);
+  static constexpr int STAGE = DF ? Df::SCR : Coop<NB>::OFF_ROWBUF;
+  static constexpr size_t BYTES = sizeof(double) * DOUBLES;
+  static_assert(2 * FLAGS_DOUBLES >= H::DF_INTS, "flag block");
+  static_assert(NWK * DIAG_SCR <= (DF ? H::NW * DIAG_SCR : NB * 256), "stage: one tile per wave inside the member it reuses");
+  static_assert(FRED % 2 == 0 && RED % 2 == 0 && STAGE % 2 == 0 && BYTES <= LDS_MAX_BYTES, "k_coop_mniw / k_coop_lat: LDS");
+  HGP_LDS_DOUBLES(red, RED)       // [8]
+  __device__ static __forceinline__ double* rvec(double* smem) {   // [16 NB]
+    static_assert(LAT, "rvec is k_coop_lat's");
+    return smem + RVEC;
+  }
+  HGP_LDS_DOUBLES(stage, STAGE)
+  // DF only: the factorisation's members
+  HGP_LDS_DOUBLES(df, 0)          // base of the Df members
+  HGP_LDS_DOUBLES(fred, FRED)     // [16]
+  HGP_LDS_INTS(flags, FLAGS, 0)
+  HGP_LDS_INTS(redi, FLAGS, H::DF_REDI)
 };
 
 // factor 0.5 (S + S^T) + shift into the packed workspace; returns info (first bad pivot or 0) in every thread
@@ -131,11 +156,11 @@ __device__ __forceinline__ int matlik_factor(const double* __restrict__ S, int T
   int info = 0;
   if constexpr (DF) {
     using C = CoopH<NB>;
-    double* row0 = smem;
-    double* Wall = row0 + 3 * NB * 256;
-    double* scr = Wall + NB * 256 + wave * DIAG_SCR;
-    double* red = Wall + NB * 256 + C::NW * DIAG_SCR;
-    int* flags = reinterpret_cast<int*>(red + 16);
+    using L = MatlikLds<NB, true>;
+    using Df = typename L::Df;
+    double *df = L::df(smem), *red = L::fred(smem);
+    int *flags = L::flags(smem), *redi = L::redi(smem);
+    double* scr = Df::scr(df) + wave * DIAG_SCR;
     d4 U[C::NT];
 #pragma unroll
     for (int i_ = 0; i_ < C::NT; ++i_) U[i_] = (d4){0.0, 0.0, 0.0, 0.0};
@@ -145,9 +170,8 @@ __device__ __forceinline__ int matlik_factor(const double* __restrict__ S, int T
     if (sh != 0.0) cooph_add_diag<NB>(U, sh, T, wave, lane);
     PivotAcc pa;
     pa.init();
-    cooph_factor_df<NB, 2>(U, row0, row0 + NB * 256, row0 + 2 * NB * 256, Wall, scr, flags, wave, lane, pa, T, nullptr, nullptr, nullptr,
-                           nullptr, Lp, Wp);
-    int* redi = flags + 16 + NB;
+    cooph_factor_df<NB, 2>(U, Df::row0(df), Df::row1(df), Df::row2(df), Df::Wall(df), scr, flags, wave, lane, pa, T, nullptr, nullptr,
+                           nullptr, nullptr, Lp, Wp);
     if (lane == 0) redi[wave] = pa.info;
     __syncthreads();
     for (int w = 0; w < C::NW; ++w)
@@ -175,7 +199,7 @@ template <int NB, bool DF>
 __global__ __launch_bounds__((64 * MatlikLds<NB, DF>::NWK)) void k_coop_mniw(MniwCoopArgs a) {
   constexpr int NWK = MatlikLds<NB, DF>::NWK;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* red = smem + MatlikLds<NB, DF>::DOUBLES;   // [NWK] partial sums (behind whatever the factorisation uses)
+  double* red = MatlikLds<NB, DF>::red(smem);   // [NWK] partial sums (behind whatever the factorisation uses)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int m = blockIdx.x;
   const int T = a.T;
@@ -253,7 +277,7 @@ __global__ __launch_bounds__((64 * MatlikLds<NB, DF>::NWK)) void k_coop_mniw(Mni
 
 template <int NB>
 int launch_coop_mniw(const MniwCoopArgs& a, hipStream_t st) {
-  const size_t lds = sizeof(double) * (MatlikLds<NB, true>::DOUBLES + 8);
+  const size_t lds = MatlikLds<NB, true>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_mniw<NB, true>), lds)) return rc_;
   hipLaunchKernelGGL((k_coop_mniw<NB, true>), dim3(a.b), dim3(64 * MatlikLds<NB, true>::NWK), lds, st, a);
   return launch_status();
@@ -279,9 +303,10 @@ template <int NB, bool DF>
 __global__ __launch_bounds__((64 * MatlikLds<NB, DF>::NWK)) void k_coop_lat(LatCoopArgs a) {
   constexpr int NWK = MatlikLds<NB, DF>::NWK;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* red = smem + MatlikLds<NB, DF>::DOUBLES;   // [NWK] partial sums
-  double* rvec = red + 8;                            // [16 NB]: r = f_cur - A f_prev (zero padded)
-  double* stage = smem + (DF ? 4 * NB * 256 : 0);    // [NWK][DIAG_SCR]: per-wave 16 x 18 staging tiles of the Gram phase (the factorisation's diag16 scratch / row buffer, free by then)
+  // red: [NWK] partial sums; rvec: [16 NB] r = f_cur - A f_prev (zero padded); stage: [NWK][DIAG_SCR] per-wave 16 x 18 staging tiles
+  // of the Gram phase
+  using L = MatlikLds<NB, DF, true>;
+  double *red = L::red(smem), *rvec = L::rvec(smem), *stage = L::stage(smem);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int m = blockIdx.x;
   const int T = a.T;
@@ -458,7 +483,7 @@ __global__ __launch_bounds__((64 * MatlikLds<NB, DF>::NWK)) void k_coop_lat(LatC
 
 template <int NB, bool DF>
 int launch_coop_lat_v(const LatCoopArgs& a, hipStream_t st) {
-  const size_t lds = sizeof(double) * (MatlikLds<NB, DF>::DOUBLES + 8 + 16 * NB);
+  const size_t lds = MatlikLds<NB, DF, true>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_lat<NB, DF>), lds)) return rc_;
   hipLaunchKernelGGL((k_coop_lat<NB, DF>), dim3(a.b), dim3(64 * MatlikLds<NB, DF>::NWK), lds, st, a);
   return launch_status();

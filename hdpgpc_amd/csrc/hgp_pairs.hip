@@ -28,11 +28,27 @@ constexpr int PAIRS_DCOLS = 16;   // clusters whose d = y - E^T a' one pass of t
 constexpr int PAIRS_W8_NB = 6;   // the NB whose band kernel runs eight waves per workgroup
 template <int NB, bool BAND>
 constexpr int pairs_waves() { return (BAND && NB == PAIRS_W8_NB) ? 8 : WAVES; }
-template <int NB, int PW = WAVES>
-constexpr size_t pairs_lds_bytes() {
-  return sizeof(double) * ((size_t)(16 * NB) * (16 * NB) + 3 * 16 * NB + PW * DIAG_SCR + PAIRS_DCOLS * 16 * NB) +
-         sizeof(int) * 32;
-}
+
+// The dynamic LDS of k_pairs<NB, BAND> at PW = pairs_waves<NB, BAND>() waves
+template <int NB, int PW>
+struct PairsLds {
+  static constexpr int TP = 16 * NB;
+  static constexpr int EMAT = 0, XS = EMAT + TP * TP, YS = XS + TP, XBS = YS + TP, SCR = XBS + TP, DALL = SCR + PW * DIAG_SCR,
+                       MASKS = DALL + PAIRS_DCOLS * TP;                            // doubles
+  static constexpr int AMASK = 0, KMASK = AMASK + 8, AMASK4 = KMASK + 8, MASK_INTS = 32;   // ints behind MASKS, 24 of them in use
+  static constexpr size_t BYTES = sizeof(double) * MASKS + sizeof(int) * MASK_INTS;
+  static_assert(AMASK4 + 8 <= MASK_INTS, "mask words");
+  static_assert(XS % 2 == 0 && SCR % 2 == 0 && DALL % 2 == 0 && BYTES <= LDS_MAX_BYTES, "k_pairs: LDS");
+  HGP_LDS_DOUBLES(E, EMAT)               // [TP][TP]: row k = basis point, column j = segment point
+  HGP_LDS_DOUBLES(xs, XS)                // segment grid / ell
+  HGP_LDS_DOUBLES(ys, YS)
+  HGP_LDS_DOUBLES(xbs, XBS)              // basis grid / ell
+  HGP_LDS_DOUBLES(scr, SCR)              // [PW][DIAG_SCR]
+  HGP_LDS_DOUBLES(dall, DALL)            // [PAIRS_DCOLS][TP]: d = y - E^T a' of the clusters of the current chunk, then z = L^{-1} d
+  HGP_LDS_INTS(amask, MASKS, AMASK)      // bit Kt of amask[J]: block (Kt, J) of E active
+  HGP_LDS_INTS(kmask, MASKS, KMASK)      // bit I of kmask[J]: tile (I, J) of K** has an entry above the cut-off (I <= J)
+  HGP_LDS_INTS(amask4, MASKS, AMASK4)    // bit 4 Kt + s of amask4[J]: k-step s of block (Kt, J) of E has an entry above the cut-off
+};
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The two sweeps of k_pairs for the BLOCK-TRIDIAGONAL E of the reference's setting (length-scale 1.2 on a unit-spaced grid, any
@@ -246,14 +262,12 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
   constexpr int TP = 16 * NB;
   constexpr int NH = NB / 2;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* E = smem;               // [TP][TP]: row k = basis point, column j = segment point
-  double* xs = E + TP * TP;       // segment grid / ell
-  double* ys = xs + TP;
-  double* xbs = ys + TP;          // basis grid / ell
+  using L = PairsLds<NB, PW>;
+  double *E = L::E(smem), *xs = L::xs(smem), *ys = L::ys(smem), *xbs = L::xbs(smem);
   const int tid = threadIdx.x, wave = tid >> 6;
-  double* scr = xbs + TP + wave * DIAG_SCR;
-  double* dall = xbs + TP + PW * DIAG_SCR;   // [PAIRS_DCOLS][TP]: d = y - E^T a' of the clusters of the current chunk, then z = L^{-1} d
-  int* amask = reinterpret_cast<int*>(dall + PAIRS_DCOLS * TP);   // bit Kt of amask[J]: block (Kt, J) of E active
+  double* scr = L::scr(smem) + wave * DIAG_SCR;
+  double* dall = L::dall(smem);
+  int *amask = L::amask(smem), *kmask = L::kmask(smem), *amask4 = L::amask4(smem);
   const int T = a.T, Ts = a.Ts;
   HGP_STAMP_DECL
   HGP_T0();
@@ -273,9 +287,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
     ys[i] = (i < Ts) ? a.y[(size_t)n * Ts + i] : 0.0;
     xbs[i] = (i < T) ? a.xb[i] / a.ell : -1e150 * (double)(1 + i);
   }
-  int* kmask = amask + 8;   // bit I of kmask[J]: tile (I, J) of K** has an entry above the cut-off (I <= J)
-  int* amask4 = amask + 16;  // bit 4 Kt + s of amask4[J]: k-step s of block (Kt, J) of E has an entry above the cut-off
-  if (tid < 24) amask[tid] = 0;
+  if (tid < 24) amask[tid] = 0;   // amask, kmask, amask4
   __syncthreads();
 #ifdef HGP_STAMPS
   { unsigned long long n_ = __builtin_readcyclecounter(); hgp_acc_[8] += n_ - hgp_t_; }
@@ -671,10 +683,38 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
 template <int NB>
 struct PairsCoop {
   static constexpr int TP = 16 * NB;
-  static constexpr int CAP = (NB >= 12) ? 48 : (NB >= 8 ? 24 : 16);   // >= 2 NB: the factorisation reuses the E slots (row buffer, W)
-  static constexpr size_t LDS_BYTES =
-      sizeof(double) * ((size_t)CAP * 256 + NB * 256 /*rowbuf*/ + 256 /*Wbuf*/ + TP /*dvec*/ + 3 * TP + DIAG_SCR + 16) +
-      sizeof(int) * (8 + 16 + 16 + 16 + 20 + NB * NB) + sizeof(double) * 4 * NB;
+  static constexpr int CAP = (NB >= 12) ? 48 : (NB >= 8 ? 24 : 16);   // E slots; the factorisation reuses them (Df below)
+  // The dynamic LDS of k_pairs_cooph<NB>: a double area, an int area, and the double area rng behind it.
+  using H = CoopH<NB>;
+  using Df = typename H::template DfLds<0>;
+  static constexpr int EC = 0, ROWBUF = EC + CAP * 256, WBUF = ROWBUF + NB * 256, DVEC = WBUF + 256, XS = DVEC + TP, YS = XS + TP,
+                       XBS = YS + TP, SCR = XBS + TP, RED = SCR + DIAG_SCR, INTS = RED + 16;   // doubles; WBUF: 256 reserved, no reader left
+  static constexpr int REDI = 0, AMASK = REDI + 8, KMASK = AMASK + 16, PNEED = KMASK + 16, BASE = PNEED + 16, SLOTBLK = BASE + 20,
+                       N_INTS = SLOTBLK + NB * NB;                                                       // ints behind INTS
+  static_assert(N_INTS % 2 == 0, "rng: doubles behind the int area");
+  static constexpr int RNG = INTS + N_INTS / 2;                                                          // doubles again
+  static constexpr size_t BYTES = sizeof(double) * (RNG + 4 * NB);
+  static_assert(ROWBUF % 2 == 0 && DVEC % 2 == 0 && SCR % 2 == 0, "tile areas are read as 16-byte vectors");
+  static_assert(BYTES <= LDS_MAX_BYTES, "k_pairs_cooph: LDS");
+  // the factorisation (cooph_factor_df<NB>): row0 is rowbuf; Df's ROW1 .. SCR (row1, row2, Wall) lie on the E slots, dead by then, with
+  // ROW1 at Ec; one scr serves (the pivot chain is serial); its flag block lies on slotblk
+  static_assert(CAP * 256 >= Df::OVERLAY, "E slots too small for the factorisation's buffers");
+  static_assert(NB * NB >= H::DF_FLAGS, "slotblk too small for the factorisation's flags");
+  HGP_LDS_DOUBLES(Ec, EC)                 // [CAP][4][64]
+  HGP_LDS_DOUBLES(rowbuf, ROWBUF)         // [NB][4][64]; row0 of the factorisation
+  HGP_LDS_DOUBLES(dvec, DVEC)             // d, then z = L^{-1} d
+  HGP_LDS_DOUBLES(xs, XS)
+  HGP_LDS_DOUBLES(ys, YS)
+  HGP_LDS_DOUBLES(xbs, XBS)
+  HGP_LDS_DOUBLES(scr, SCR)
+  HGP_LDS_DOUBLES(red, RED)               // [16]
+  HGP_LDS_INTS(redi, INTS, REDI)          // [8]
+  HGP_LDS_INTS(amask, INTS, AMASK)        // bit Kt of amask[J]: block (Kt, J) of E active
+  HGP_LDS_INTS(kmask, INTS, KMASK)        // bit I of kmask[J]: tile (I, J) of K** above the cut-off (I <= J)
+  HGP_LDS_INTS(pneed, INTS, PNEED)        // OR of amask[0..J]: row tiles of B[:, J] that sweep 2 reads
+  HGP_LDS_INTS(base, INTS, BASE)          // first slot of column J (prefix sum of popcounts), base[NB] = total
+  HGP_LDS_INTS(slotblk, INTS, SLOTBLK)    // slot -> (Kt << 8) | J; the factorisation's flag block
+  HGP_LDS_DOUBLES(rng, RNG)               // [2 NB][lo, hi] of the real points of each 16-block
 };
 
 // The same pipeline with NB/2 waves per pair (CoopH<NB>, tile_f64.hpp: 8 waves and 17 tiles per wave at NB = 16 instead
@@ -688,22 +728,10 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
   constexpr int TP = 16 * NB, CAP = PC::CAP;
   constexpr int CH = (NB <= 8 && NB % 4 == 0) ? 4 : 2;   // row tiles of B[:, J] per pass (must divide NB; register budget)
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* Ec = smem;                    // [CAP][4][64]
-  double* rowbuf = Ec + CAP * 256;      // [NB][4][64]
-  double* Wbuf = rowbuf + NB * 256;
-  double* dvec = Wbuf + 256;            // d, then z = L^{-1} d
-  double* xs = dvec + TP;
-  double* ys = xs + TP;
-  double* xbs = ys + TP;
-  double* scr = xbs + TP;
-  double* red = scr + DIAG_SCR;         // 16 doubles
-  int* redi = reinterpret_cast<int*>(red + 16);   // 8
-  int* amask = redi + 8;                // bit Kt of amask[J]: block (Kt, J) of E active
-  int* kmask = amask + 16;              // bit I of kmask[J]: tile (I, J) of K** above the cut-off (I <= J)
-  int* pneed = kmask + 16;              // OR of amask[0..J]: row tiles of B[:, J] that sweep 2 reads
-  int* base = pneed + 16;               // first slot of column J (prefix sum of popcounts), base[NB] = total
-  int* slotblk = base + 20;             // slot -> (Kt << 8) | J
-  double* rng = reinterpret_cast<double*>(slotblk + NB * NB);   // [2 NB][lo, hi] of the real points of each 16-block
+  double *Ec = PC::Ec(smem), *rowbuf = PC::rowbuf(smem), *dvec = PC::dvec(smem), *xs = PC::xs(smem), *ys = PC::ys(smem);
+  double *xbs = PC::xbs(smem), *scr = PC::scr(smem), *red = PC::red(smem), *rng = PC::rng(smem);
+  int *redi = PC::redi(smem), *amask = PC::amask(smem), *kmask = PC::kmask(smem), *pneed = PC::pneed(smem), *base = PC::base(smem);
+  int* slotblk = PC::slotblk(smem);
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int T = a.T, Ts = a.Ts;
@@ -1032,9 +1060,11 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
   PivotAcc pa;
   pa.init();
   HGP_ACC(5);
-  // dataflow-synchronised (tile_f64.hpp, cooph_factor_df): the E slots are dead now - second row buffer and the W of every step
-  static_assert(CAP >= 3 * NB, "E slots too small for the factorisation's buffers");
-  double zq = cooph_factor_df<NB>(U, rowbuf, Ec, Ec + NB * 256, Ec + 2 * NB * 256, scr, slotblk, wave, lane, pa, Ts, dvec);
+  // dataflow-synchronised (tile_f64.hpp, cooph_factor_df): the E slots are dead now - two row buffers and the W of every step lie over
+  // them, as PairsCoop states.  (Offsets from Ec here and not accessors of PairsCoop: with those the NB = 16 kernel compiles differently.)
+  using Df = typename PC::Df;
+  double zq = cooph_factor_df<NB>(U, rowbuf, Ec, Ec + (Df::ROW2 - Df::ROW1), Ec + (Df::WALL - Df::ROW1), scr, slotblk, wave, lane, pa, Ts,
+                                  dvec);
   int info;
   const double ld = cooph_logdet_info<NB>(pa, wave, lane, red, redi, info);
   zq = wave_sum(zq);
@@ -1059,7 +1089,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
 
 template <int NB>
 int launch_pairs_cooph(const PairsArgs& a, hipStream_t st) {
-  const size_t lds = PairsCoop<NB>::LDS_BYTES;
+  const size_t lds = PairsCoop<NB>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs_cooph<NB>), lds)) return rc_;
   const int blocks = a.sel ? a.N : a.N * (a.kend - a.kbeg);
   hipLaunchKernelGGL(k_pairs_cooph<NB>, dim3(blocks), dim3(64 * CoopH<NB>::NW), lds, st, a);
@@ -1068,7 +1098,7 @@ int launch_pairs_cooph(const PairsArgs& a, hipStream_t st) {
 
 template <int NB>
 int launch_pairs(const PairsArgs& a0, hipStream_t st) {
-  size_t lds = pairs_lds_bytes<NB>();
+  const size_t lds = PairsLds<NB, pairs_waves<NB, false>()>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, false>), lds)) return rc_;
   if (NB < 6 || (a0.flags & 1) || !a0.fb) {   // mask-driven sweeps for every segment
     PairsArgs a = a0;
@@ -1077,7 +1107,7 @@ int launch_pairs(const PairsArgs& a0, hipStream_t st) {
     return launch_status();
   }
   constexpr int PWB = pairs_waves<NB, true>();
-  const size_t ldsb = pairs_lds_bytes<NB, PWB>();
+  const size_t ldsb = PairsLds<NB, PWB>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, true>), ldsb)) return rc_;
   for (int off = 0; off < a0.N; off += PAIRS_FB_CAP) {   // the fall-back list holds PAIRS_FB_CAP segments
     PairsArgs a = a0;

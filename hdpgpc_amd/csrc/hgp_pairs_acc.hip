@@ -189,11 +189,24 @@ struct AccArgs {
   int score_on;
 };
 
+// The dynamic LDS of k_pairs_acc<NB>
 template <int NB>
-struct AccLds {
+struct PairsAccLds {
   static constexpr int TP = 16 * NB;
-  static constexpr size_t DOUBLES = (size_t)NB * 256 /*rowbuf*/ + 256 /*Wbuf*/ + 5 * TP /*dvec xs ys xbs mus*/ + DIAG_SCR + 32;
-  static constexpr size_t BYTES = DOUBLES * sizeof(double) + 16 * sizeof(int);
+  static constexpr int ROWBUF = 0, WBUF = ROWBUF + NB * 256, DVEC = WBUF + 256, XS = DVEC + TP, YS = XS + TP, XBS = YS + TP,
+                       MUS = XBS + TP, SCR = MUS + TP, RED = SCR + DIAG_SCR, REDI = RED + 32;   // doubles
+  static constexpr size_t BYTES = sizeof(double) * REDI + sizeof(int) * 16;
+  static_assert(WBUF % 2 == 0 && SCR % 2 == 0 && BYTES <= LDS_MAX_BYTES, "k_pairs_acc: LDS");
+  HGP_LDS_DOUBLES(rowbuf, ROWBUF)   // [NB][4][64]
+  HGP_LDS_DOUBLES(Wbuf, WBUF)
+  HGP_LDS_DOUBLES(dvec, DVEC)       // d, then z = L^{-1} d
+  HGP_LDS_DOUBLES(xs, XS)           // segment grid / ell (sentinel padded)
+  HGP_LDS_DOUBLES(ys, YS)
+  HGP_LDS_DOUBLES(xbs, XBS)         // basis grid / ell (sentinel padded)
+  HGP_LDS_DOUBLES(mus, MUS)         // prior mean on the basis grid (zero padded)
+  HGP_LDS_DOUBLES(scr, SCR)
+  HGP_LDS_DOUBLES(red, RED)         // [32]
+  HGP_LDS_INTS(redi, REDI, 0)       // [16]
 };
 
 __device__ __forceinline__ d4 ld4(const double* base, unsigned off) { return *reinterpret_cast<const d4*>(base + off); }
@@ -203,16 +216,10 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
   using H = CoopH<NB>;
   constexpr int NW = H::NW, TP = 16 * NB;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double* rowbuf = smem;                // [NB][4][64]
-  double* Wbuf = rowbuf + NB * 256;
-  double* dvec = Wbuf + 256;            // d, then z = L^{-1} d
-  double* xs = dvec + TP;               // segment grid / ell (sentinel padded)
-  double* ys = xs + TP;
-  double* xbs = ys + TP;                // basis grid / ell (sentinel padded)
-  double* mus = xbs + TP;               // prior mean on the basis grid (zero padded)
-  double* scr = mus + TP;
-  double* red = scr + DIAG_SCR;         // 32 doubles
-  int* redi = reinterpret_cast<int*>(red + 32);
+  using L = PairsAccLds<NB>;
+  double *rowbuf = L::rowbuf(smem), *Wbuf = L::Wbuf(smem), *dvec = L::dvec(smem), *xs = L::xs(smem), *ys = L::ys(smem);
+  double *xbs = L::xbs(smem), *mus = L::mus(smem), *scr = L::scr(smem), *red = L::red(smem);
+  int* redi = L::redi(smem);
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int T = a.T, Ts = a.Ts;
@@ -415,7 +422,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
 
 template <int NB>
 int launch_pairs_acc(const AccArgs& a, hipStream_t st) {
-  const size_t lds = AccLds<NB>::BYTES;
+  const size_t lds = PairsAccLds<NB>::BYTES;
   hipLaunchKernelGGL(k_pairs_acc<NB>, dim3(acc_grid_for(NB)), dim3(64 * CoopH<NB>::NW), lds, st, a);
   return launch_status();
 }

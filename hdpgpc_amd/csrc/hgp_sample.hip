@@ -44,6 +44,17 @@ struct SampleArgs {
   const int32_t* finfo;     // [S] info of the factorisation
 };
 
+// The dynamic LDS of k_sample<RT>, sized by the run-time tile count nb <= 4 RT
+template <int RT>
+struct SampleLds {
+  static constexpr int BN_CT = bands_ct(RT);
+  __host__ __device__ static constexpr int stg_off(int nb) { return nb * BN_CT * 256; }   // doubles
+  __host__ __device__ static constexpr size_t bytes(int nb) { return sizeof(double) * ((size_t)stg_off(nb) + WAVES * STG); }
+  static_assert(bytes(4 * RT) <= LDS_MAX_BYTES, "k_sample: LDS");
+  __device__ static __forceinline__ double* Xs(double* smem) { return smem; }                          // [nb * BN_CT tiles][4][64]
+  __device__ static __forceinline__ double* stg(double* smem, int nb) { return smem + stg_off(nb); }   // [WAVES][STG]: one staging tile per wave
+};
+
 template <int RT>
 __global__ __launch_bounds__(256) void k_sample(SampleArgs a) {
   constexpr int BN_CT = bands_ct(RT), BN_P = 16 * BN_CT;   // draws per panel
@@ -52,8 +63,8 @@ __global__ __launch_bounds__(256) void k_sample(SampleArgs a) {
   const int s = blockIdx.x, tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int g = lane >> 4, c = lane & 15;
-  double* Xs = smem;                                   // [nb * BN_CT tiles][4][64]
-  double* stg = smem + nb * BN_CT * 256 + wave * STG;  // this wave's staging tile
+  double* Xs = SampleLds<RT>::Xs(smem);
+  double* stg = SampleLds<RT>::stg(smem, nb) + wave * STG;   // this wave's staging tile
   const long m = a.cov_idx ? (long)a.cov_idx[s] : (long)s;
   const double d = tid < T ? a.cov[(m * T + tid) * T + tid] : 0.0;   // T <= 256: one diagonal entry per thread
   const int bad = __syncthreads_or(!(fabs(d) <= 1.79769313486231570815e308));   // NaN or infinite diagonal
@@ -129,7 +140,7 @@ __global__ __launch_bounds__(256) void k_sample(SampleArgs a) {
 template <int RT>
 int launch_sample(const SampleArgs& a, hipStream_t st) {
   constexpr int BN_CT = bands_ct(RT), BN_P = 16 * BN_CT;
-  const size_t lds = sizeof(double) * ((size_t)a.nb * BN_CT * 256 + WAVES * STG);
+  const size_t lds = SampleLds<RT>::bytes(a.nb);
   if (int rc = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_sample<RT>), lds)) return rc;
   const int npanels = (a.n + BN_P - 1) / BN_P;
   int ny = (768 + a.S - 1) / a.S;   // enough workgroups to fill the chip when the call holds few states

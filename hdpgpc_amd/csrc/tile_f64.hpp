@@ -36,6 +36,16 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 constexpr int DIAG_LD = 18;              // row stride (doubles) of the per-wave 16x16 LDS staging tile
 constexpr int DIAG_SCR = 16 * DIAG_LD;   // doubles of LDS scratch each wave needs
+constexpr size_t LDS_MAX_BYTES = 160 * 1024;   // LDS of one workgroup (gfx950): every kernel's LDS layout asserts its BYTES against it
+
+// A kernel's dynamic LDS is stated once, in a layout type beside the kernel: constexpr offsets, BYTES (or bytes(nb)) = the end of the
+// last member, compile-time checks, and one accessor per member - `double* xs = L::xs(smem)` in the kernel, L::BYTES in the launcher,
+// which never computes a size.  (Accessors, not one carve() that returns a struct of pointers: such pointers travel through memory
+// until the optimiser promotes them, late enough that k_pairs_acc, k_pairs, k_bands and others allocate their registers differently.)
+#define HGP_LDS_DOUBLES(name, OFF) \
+  __device__ static __forceinline__ double* name(double* base) { return (OFF) == 0 ? base : base + (OFF); }
+#define HGP_LDS_INTS(name, OFF, INT_OFF) \
+  __device__ static __forceinline__ int* name(double* base) { return reinterpret_cast<int*>(base + (OFF)) + (INT_OFF); }
 constexpr double F64_EPS = 2.220446049250313e-16;
 
 __host__ __device__ constexpr int tix(int I, int J, int NB) { return I * NB - (I * (I - 1)) / 2 + (J - I); }
@@ -754,10 +764,10 @@ struct Coop {
     double *rowbuf, *Rbuf, *Wbuf, *scr, *red;
     int* redi;
   };
-  static constexpr int OFF_RBUF = NB * 256, OFF_WBUF = OFF_RBUF + NB * 256, OFF_SCR = OFF_WBUF + 256, OFF_RED = OFF_SCR + DIAG_SCR,
-                       OFF_REDI = OFF_RED + 8, LDS_DOUBLES = OFF_REDI + 8;
+  static constexpr int OFF_ROWBUF = 0, OFF_RBUF = OFF_ROWBUF + NB * 256, OFF_WBUF = OFF_RBUF + NB * 256, OFF_SCR = OFF_WBUF + 256,
+                       OFF_RED = OFF_SCR + DIAG_SCR, OFF_REDI = OFF_RED + 8, LDS_DOUBLES = OFF_REDI + 8;
   __device__ static __forceinline__ Lds lds(double* smem) {
-    return {smem, smem + OFF_RBUF, smem + OFF_WBUF, smem + OFF_SCR, smem + OFF_RED, reinterpret_cast<int*>(smem + OFF_REDI)};
+    return {smem + OFF_ROWBUF, smem + OFF_RBUF, smem + OFF_WBUF, smem + OFF_SCR, smem + OFF_RED, reinterpret_cast<int*>(smem + OFF_REDI)};
   }
 };
 
@@ -1067,6 +1077,33 @@ struct CoopH {
   __host__ __device__ static constexpr int slotB(int I) { return I; }
   __host__ __device__ static constexpr int owner(int J) { return J < NW ? J : NB - 1 - J; }
   __host__ __device__ static constexpr int diag_slot(int K) { return K < NW ? slotA(K) : slotB(K); }
+
+  // The LDS of cooph_factor_df (below), stated in ONE place: offsets in doubles from the base of the sub-layout, and one accessor
+  // per member.  Tile areas of [NB][4][64] doubles: three row buffers, Wall and - only with a block of right-hand sides (RHS == 1) -
+  // zbuf; scr: the diag16 scratch, [NW][DIAG_SCR] where every wave also stages through a slice of its own.  A kernel whose own
+  // buffers are dead during the factorisation lays ROW1 .. SCR (OVERLAY doubles) over them and supplies row0 and scr itself.
+  template <int RHS>
+  struct DfLds {
+    static constexpr int AREA = NB * 256;
+    static constexpr int ROW0 = 0, ROW1 = ROW0 + AREA, ROW2 = ROW1 + AREA, WALL = ROW2 + AREA, ZBUF = WALL + AREA,
+                         SCR = ZBUF + (RHS == 1 ? AREA : 0), DOUBLES = SCR + NW * DIAG_SCR;
+    static constexpr int OVERLAY = SCR - ROW1;
+    static_assert(AREA % 2 == 0 && DIAG_SCR % 2 == 0, "tile areas are read as 16-byte vectors");
+    HGP_LDS_DOUBLES(row0, ROW0)
+    HGP_LDS_DOUBLES(row1, ROW1)
+    HGP_LDS_DOUBLES(row2, ROW2)
+    HGP_LDS_DOUBLES(Wall, WALL)
+    __device__ static __forceinline__ double* zbuf(double* base) {
+      static_assert(RHS == 1, "zbuf exists with a block of right-hand sides only");
+      return base + ZBUF;
+    }
+    HGP_LDS_DOUBLES(scr, SCR)
+  };
+  // ... and its flag block, ints: the counters of the dataflow (zeroed by cooph_factor_df), then the NW status words that the
+  // callers without a reduction area of their own hang behind it (DF_INTS in all)
+  static constexpr int DF_WDONE = 0, DF_TDONE = 1 /*[8]*/, DF_ERR = 9, DF_ROWPUB = 16 /*[NB]*/, DF_FLAGS = DF_ROWPUB + NB;
+  static constexpr int DF_REDI = DF_FLAGS /*[8]*/, DF_INTS = DF_REDI + 8;
+  static_assert(DF_WDONE < DF_TDONE && DF_TDONE + NW <= DF_ERR && DF_ERR < DF_ROWPUB && NW <= 8, "flag block of cooph_factor_df");
 };
 
 // mean over i < n of |A_ii + shift| (LDS reduction in red[8])
@@ -1314,7 +1351,9 @@ __device__ __forceinline__ void df_wait_all_ge(int* tdone, int v, int lane, int*
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// row0 / row1 / row2: three row buffers [NB][4][64]; Wall: [NB][4][64]; flags: 16 + NB ints (zeroed here).
+// row0 / row1 / row2, Wall, zbuf: the members of CoopH<NB>::DfLds<RHS>; scr: the calling wave's diag16 scratch; flags: the DF_FLAGS
+// counters of CoopH<NB> (zeroed here).  (The members travel as pointers: with the struct as the parameter k_cooph_inv_rhs allocates
+// its registers differently.)
 // Two refinements on the critical path (the chain diag16(K) -> W_K -> tile (K, K+1) -> tile (K+1, K+1) -> diag16(K+1)):
 //  * the owner of block K + 1 solves ONLY that panel tile first, updates its diagonal tile straight from the accumulator (no LDS
 //    round trip), factors it and publishes W_{K+1} - its other panel tile and the rest of its trailing update come afterwards;
@@ -1338,11 +1377,11 @@ __device__ __forceinline__ double cooph_factor_df(d4 (&U)[CoopH<NB>::NT], double
                                                   double* Lpack = nullptr, double* Wpack = nullptr) {
   constexpr bool RP = (RHS == 1), NORHS = (RHS == 2);
   using C = CoopH<NB>;
-  int* wdone = flags;
-  int* tdone = flags + 1;        // [8]
-  int* err = flags + 9;
-  int* rowpub = flags + 16;      // [NB]
-  if (threadIdx.x < 16 + NB) flags[threadIdx.x] = 0;
+  int* wdone = flags + C::DF_WDONE;
+  int* tdone = flags + C::DF_TDONE;
+  int* err = flags + C::DF_ERR;
+  int* rowpub = flags + C::DF_ROWPUB;
+  if (threadIdx.x < C::DF_FLAGS) flags[threadIdx.x] = 0;
   __syncthreads();
   double zq = 0.0;
   const int JA = wave, JB = NB - 1 - wave;   // my block columns

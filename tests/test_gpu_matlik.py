@@ -37,6 +37,22 @@ def test_lat_error_a8(T, b):
     assert rel_err(out.cpu().numpy() - 0.5 * T * orc.LOG2PI, ref) < 1e-9
 
 
+@pytest.mark.parametrize("T", [129, 192, 193, 256])
+def test_lat_error_a8_large_batch_takes_the_four_wave_kernel(T):
+    """From 200 items on a8 runs the four-wave kernel above T = 128 (k_coop_lat<NB, false>; the smaller batches above run the
+    eight-wave one): both padded sizes, at both ends of their range of T."""
+    b = 200
+    rng = np.random.default_rng(T)
+    A = np.eye(T)[None] + 0.05 * rng.normal(size=(b, T, T))
+    Gam, P = spd(rng, b, T, 0.3), spd(rng, b, T, 2.0)
+    Gam = Gam + 1e-3 * rng.normal(size=Gam.shape)
+    fc, fp = rng.normal(size=(b, T)) * 5, rng.normal(size=(b, T)) * 5
+    out, info = ops.lat_error(dev(fc), dev(fp), dev(A), dev(Gam), dev(P))
+    assert int(info.abs().max()) == 0
+    ref = np.array([orc.lat_error_terms(fc[i], fp[i], A[i], Gam[i], P[i]) for i in range(b)])
+    assert rel_err(out.cpu().numpy() - 0.5 * T * orc.LOG2PI, ref) < 1e-9
+
+
 # (160, 82) with a dense per-item prior: the composition's products L^-1 D and L^-1 S (lower-triangular A) are 25 blocks of 32 x 32
 # per item, 2050 in all - the one-wave-per-block kernel k_gemm22 with triA, which no smaller batch reaches.  The diagonal per-item
 # prior takes the fused cooperative kernel at every 128 < T <= 256 and never the composition, so it gains no case.
