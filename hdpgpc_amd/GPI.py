@@ -115,6 +115,19 @@ class IterativeGaussianProcess:
             cov_f = 0.5 * (cov_f + cov_f.T) + 1e-6 * torch.eye(m, dtype=torch_f64, device=self.device)
         return f_star, cov_f
 
+    def projection_matrix(self, x_basis, x_train):
+        """GPI.py:153-192: K(xb, x) (K(x, x) + 1e-4 I)^{-1}, [T, T*] - what carries values on the grid x back onto the basis
+        (two-argument kernel calls: no white noise); the identity when x is the basis."""
+        x_b = self.cond_to_torch(x_basis).reshape(-1, 1)
+        x_t = self.cond_to_torch(x_train).reshape(-1, 1)
+        if x_b.shape == x_t.shape and torch.equal(x_b, x_t):
+            return torch.eye(x_b.shape[0], dtype=torch_f64, device=self.device)
+        c, ell, _ = self.kernel.params()
+        _, info, Z = ops.potrf_batched(ops.gram_rbf(x_t, x_t, c, ell), 0.0, 1e-4, want_inv=True)
+        ops.raise_on_info(info, "projection_matrix")
+        sol = self._spd_solve(Z[0], ops.gram_rbf(x_t, None, c, ell, 1e-4), ops.gram_rbf(x_t, x_b, c, ell))   # K~^{-1} K(x, xb)
+        return sol.T.contiguous()
+
     def pred_latent_dist(self, x_post, x_fixed, mean_prior, cov_prior):
         """GPI.py:505-560."""
         x_p = self.cond_to_torch(x_post).reshape(-1, 1)

@@ -199,7 +199,12 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
             for gp in self.gpmodels[ld]:
                 gp.reinit_LDS(save_last=True)
                 gp.reinit_GP(save_last=True, save_index=True)
-        self.__dict__.pop("_pools", None)       # the persistent chains of the online step held the dropped history
+        self._drop_online_pools()               # the persistent chains of the online step held the dropped history
+
+    def _drop_online_pools(self):
+        """Forget the online step's persistent chains (online_chain.OnlinePool, one per lead): whoever replaces the cluster
+        models or cuts their lists calls this; OnlineLoop._online_pool builds new chains from the models when it next needs them."""
+        self.__dict__.pop("_pools", None)
 
     def save_swgp(self, st):
         """GPI_HDP.py:3946-3950: keep_last_all, everything to host memory, pickle.  ``load_swgp`` (or pickle.load) brings it back
@@ -364,6 +369,7 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         assert y.shape[2] == self.n_outputs
         N = y.shape[0]
         labels = np.asarray(_np(labels), dtype=np.int64).reshape(-1)
+        self._drop_online_pools()
         self.M, self.T = int(M), N
         self.x_basis = [self.x_basis_ini] * self.M
         self.model_type = [self.model_type_def] * self.M

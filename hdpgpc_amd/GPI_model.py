@@ -50,10 +50,11 @@ class matrix_normal_inv_wishart:
         self.scale = scale
 
     def posterior(self, n_k, y1, y2, cov=None, cov_=None, cov_cross=None, sse_matrix=None, annealing=False, defer=None):
-        """GPI_model.py:1300-1344 for n_k = 1, zero covariance corrections and no projection (the only call the
-        one-step estimation makes on a shared grid, GPI_model.py:995-998,1034-1036)."""
-        if n_k != 1 or sse_matrix is not None:
-            raise NotImplementedError("MNIW posterior: only the one-step, shared-grid update is built")
+        """GPI_model.py:1300-1344 for n_k = 1 and zero covariance corrections (the only calls the one-step estimation makes,
+        GPI_model.py:995-998,1034-1041).  sse_matrix [T, T*]: both samples sit on a grid of their own and are projected onto
+        the basis first (GPI_model.py:1318-1319); None on the shared grid."""
+        if n_k != 1:
+            raise NotImplementedError("MNIW posterior: only the one-step update is built")
         T = self.scale.shape[0]
         dev = self.scale.device
         eye = torch.eye(T, dtype=f64, device=dev)
@@ -63,7 +64,9 @@ class matrix_normal_inv_wishart:
         Z, info = ops.chol_inverse((0.5 * (m_r_cov + m_r_cov.T) + jitter * eye).contiguous())   # :1313-1316
         (defer.append(info) if defer is not None else ops.raise_on_info(info, "MNIW.posterior"))
         scale_inv = ops.gemm_batched(Z[0], Z[0], transA=True)
-        y1, y2 = y1.reshape(T, 1), y2.reshape(T, 1)
+        y1, y2 = y1.reshape(-1, 1), y2.reshape(-1, 1)
+        if sse_matrix is not None:
+            y1, y2 = ops.gemm_batched(sse_matrix, y1.contiguous()), ops.gemm_batched(sse_matrix, y2.contiguous())
         S__ = ops.gemm_batched(y2, y2, transB=True) + scale_inv                                 # :1321,1325
         S_ = ops.gemm_batched(y1, y2, transB=True) + ops.gemm_batched(self.m_mean.contiguous(), scale_inv)
         Zs, info = ops.chol_inverse(S__.contiguous(), 0.0, 1e-8)                                # :1329
@@ -670,7 +673,9 @@ class GPI_model:
             self.f_star_sm[-1], self.cov_f_sm[-1] = m1, c1
 
     def bayesian_new_params(self, h, model_type="dynamic", full_data=False, q=None, force=False, snr=1.0):
-        """GPI_model.py:966-1115, one-step estimation (full_data=False), dynamic model, shared grid."""
+        """GPI_model.py:966-1115, one-step estimation (full_data=False), dynamic model.  A newest member on a grid of its own
+        (GPI_model.py:1037-1041,1065): the observation update compares it with the latent mean resampled on that grid, both
+        projected back onto the basis."""
         if h != 1.0:          # the reference's whole body sits under `if h == 1.0:` (GPI_model.py:972): a soft member is skipped
             return
         if full_data:
@@ -678,7 +683,11 @@ class GPI_model:
         if 1 < self.N < self.estimation_limit or force:
             infos = []
             new_int = self.internal_params.posterior(1, self.f_star_sm[-1], self.f_star_sm[-2], defer=infos)
-            new_obs = self.observation_params.posterior(1, self.y_train[-1], self.f_star_sm[-1], defer=infos)
+            x_last, f_obs, proj = self.x_train[-1], self.f_star_sm[-1], None
+            if x_last is not self.x_basis and not (x_last.shape == self.x_basis.shape and bool(torch.equal(x_last, self.x_basis))):
+                f_obs, _ = self.gp.pred_latent_dist(x_last, self.x_basis, f_obs, self.cov_f_sm[-1])
+                proj = self.gp.projection_matrix(self.x_basis, x_last)
+            new_obs = self.observation_params.posterior(1, self.y_train[-1], f_obs, sse_matrix=proj, defer=infos)
             if bool(torch.cat(infos).any()):             # GPI_model.py:1068-1071: keep the previous distributions
                 new_int, new_obs = self.internal_params, self.observation_params
             elif self._rank1_on():

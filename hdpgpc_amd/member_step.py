@@ -61,7 +61,8 @@ class Chain:
     """A model's per-step lists as stacks with head-room, and everything one member step of it reads and writes."""
     __slots__ = _STACKS + ("T", "pos", "Nf", "n0", "W",          # from_model
                            "ws", "bad", "sync", "Y", "y_row0",   # the caller's: gathered previous state, status words, observations
-                           "lv", "bufs")                         # build_lists
+                           "lv", "bufs",                         # build_lists
+                           "bound")                              # bind_model
 
     def __init__(self, **fields):
         for k, v in fields.items():
@@ -106,11 +107,25 @@ class Chain:
         """The model's lists as views of the first L rows of the stacks, its MNIW distributions as views of W with count n0.
         The only binder: kernels write the stacks and W in place, and NEW lists (new stamps, steplist.py) are what tells the model
         that they did - whoever lets a step write rows a model can see binds again."""
-        for key in _STACKS:
-            setattr(gp, _LISTS[key], StepList(getattr(self, key)[:L]))
+        views = tuple(StepList(getattr(self, key)[:L]) for key in _STACKS)
+        for key, lst in zip(_STACKS, views):
+            setattr(gp, _LISTS[key], lst)
         W = self.W
         gp.internal_params = matrix_normal_inv_wishart(W[0, 0], W[1, 0], n0, W[2, 0])
         gp.observation_params = matrix_normal_inv_wishart(W[0, 1], W[1, 1], n0, W[2, 1])
+        self.bound = (views, gp.internal_params, gp.observation_params)
+
+    def bound_to(self, gp):
+        """Is the model still what the last bind_model(gp, ...) left: every list the very view handed out then and still a view
+        (a mutation turns a list into a real one, an assignment replaces it), both MNIW distributions the objects over W?
+        Identity checks only: this runs for every cluster at every beat of the online loop."""
+        views, ip, op = self.bound
+        if gp.internal_params is not ip or gp.observation_params is not op:
+            return False
+        for key, lst in zip(_STACKS, views):
+            if getattr(gp, _LISTS[key]) is not lst or lst.stacked() is None:
+                return False
+        return True
 
     def build_lists(self, shared, c, alloc=None):
         """The member step as ONE launch per dependency level (hgp_chain.hip): every product of the step is an item of a

@@ -796,6 +796,7 @@ class OfflineLoop:
         if self.reduce_outputs:
             raise NotImplementedError("reduce_outputs is not part of this build")
         self.warp = bool(warp)
+        self._drop_online_pools()                 # the loop replaces the cluster models
         self._log(f"------ HDP Hyperparameters ------\ngamma: {self.gamma}\ntransAlpha: {self.transAlpha}\n"
                   f"startAlpha: {self.startAlpha}\nkappa: {self.kappa}\n---------------------------------")
         y = self.cond_to_torch(y_trains)
@@ -874,6 +875,7 @@ class OfflineLoop:
         (Where the reference's loop meets its stop condition it evaluates an undefined name, ``warp_computed``,
         GPI_HDP.py:3139 - a NameError; with ``warp=False`` the branch it guards is the plain ``break`` taken here.)"""
         D, dev = self.n_outputs, self.device
+        self._drop_online_pools()                 # every cluster is rebuilt below
         q_new = self.frozen_scores(x_new, y_new)
         snr_new = torch.stack([torch.stack([self.compute_snr(y_new[:, :, ld], self.gpmodels[ld][m]) for ld in range(D)], dim=-1)
                                for m in range(self.M)], dim=1)

@@ -128,16 +128,22 @@ class OnlinePool:
         self.MN_M, self.MN_S, self.MN_mean, self.MN_scale = (new(cap * 2, T, T) for _ in range(4))
 
     def _grow(self):
-        """Twice the cluster capacity: the per-cluster slices of the shared buffers move, so every slot's lists are rebuilt."""
-        old = self.slots
+        """Twice the cluster capacity: the per-cluster slices of the shared buffers move, so every slot's lists are rebuilt.
+        A commit in flight is finished first (its status words live in the buffers that go), and the committed steps' status
+        words move with their slots: bad_all[c, 0] counts the skipped MNIW updates of slot c for the life of its chain, and
+        sl.bad0 is the host's copy of that count."""
+        self.finish_commit()
+        old, bad = self.slots, self.bad_all
         self.slots = []
         self._alloc(self.cap * 2)
+        self.bad_all[:bad.shape[0]].copy_(bad)
         for sl in old:
             self._bind(sl)
 
-    def _bind(self, sl):
-        """Give the slot its index, its slices of the shared buffers and its level lists."""
-        c = len(self.slots)
+    def _bind(self, sl, c=None):
+        """Give the slot its index (c: the index of the slot it replaces; default: the next free one), its slices of the shared
+        buffers and its level lists."""
+        c = len(self.slots) if c is None else c
         sl.g._slot = c
         ch = sl.ch
         ch.ws = self.ws_all[c]
@@ -167,7 +173,10 @@ class OnlinePool:
         self.ini_noise_all[c] = 1e-2 * torch.mean(torch.diagonal(dd.Sigma[0]))
         self.MN_mean[2 * c].copy_(dd.C_def), self.MN_mean[2 * c + 1].copy_(dd.A_def)
         self.MN_scale[2 * c].copy_(dd.Sigma_def), self.MN_scale[2 * c + 1].copy_(dd.Gamma_def)
-        self.slots.append(sl)
+        if c == len(self.slots):
+            self.slots.append(sl)
+        else:
+            self.slots[c] = sl
 
     @staticmethod
     def supports(g):
@@ -181,14 +190,28 @@ class OnlinePool:
         same = lambda a, b: a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape) or bool(torch.equal(a, b))   # noqa: E731
         return same(g.f_star[-1], g.f_star_sm[-1]) and same(g.cov_f[-1], g.cov_f_sm[-1])
 
-    def holds(self, g):
-        """Does a slot of this pool carry the model g?"""
+    def _slot_of(self, g):
+        """The slot that was made for the model g, or None."""
         c = getattr(g, "_slot", None)
-        return c is not None and c < len(self.slots) and self.slots[c].g is g
+        return self.slots[c] if c is not None and c < len(self.slots) and self.slots[c].g is g else None
+
+    def holds(self, g):
+        """Does a slot of this pool carry the model g - as it is now?  The chain is the cluster only as long as nobody else
+        changes the model: a member step taken with the one-by-one methods (a beat off the basis grid, OnlineLoop._member_update)
+        turns the lists into real ones and moves N, and the slot's stacks, position and device-side distributions stay behind.
+        Such a model is not held any more; adopt(g) gives it its slot back, rebuilt."""
+        sl = self._slot_of(g)
+        return sl is not None and sl.N == g.N and len(g.f_star) == sl.N + 1 and sl.ch.bound_to(g)
 
     def adopt(self, g):
-        """Move the model's per-step lists into a slot's stacks (the model keeps reading them through views)."""
-        if len(self.slots) == self.cap:
+        """Move the model's per-step lists into a slot's stacks (the model keeps reading them through views).  A model that has
+        a slot already keeps it: the slot gets a new chain built from the model as it is now (see holds())."""
+        c = None
+        if self._slot_of(g) is not None:
+            self.finish_commit()
+            c = g._slot
+            self.bad_all[c].zero_()
+        elif len(self.slots) == self.cap:
             self._grow()
         L = len(g.f_star)
         sl = _Slot()
@@ -196,7 +219,7 @@ class OnlinePool:
         sl.ch = Chain.from_model(g, sl.rows)
         sl.def_diag = g._defs_diagonal()
         sl.bad0 = 0
-        self._bind(sl)
+        self._bind(sl, c)
         self._rebind_lists(sl, float(g.internal_params.n0))
         return sl
 

@@ -67,10 +67,18 @@ class OnlineLoop:
         if xb is None or x.shape != xb.shape or not bool(torch.equal(x, xb)) or ops.env_flag("HGP_ONLINE_EAGER"):
             return None
         pools = self.__dict__.setdefault("_pools", {})
-        if ld not in pools:
-            pools[ld] = online_chain.OnlinePool(xb.shape[0], self.device, self.annealing_def)
-        pool = pools[ld]
-        for g in self.gpmodels[ld]:
+        models = self.gpmodels[ld]
+        pool = pools.get(ld)
+        if pool is not None and len(pool.slots) > 0:
+            listed = {id(g) for g in models}
+            if any(id(sl.g) not in listed for sl in pool.slots):
+                # a slot's model has left the list (the list was replaced by copies, a cluster was dropped): the chains start over
+                pool.finish_commit()
+                pool = None
+        if pool is None:
+            pool = pools[ld] = online_chain.OnlinePool(xb.shape[0], self.device, self.annealing_def)
+        for g in models:
+            # (a model that was changed behind its chain's back - the one-by-one commit of a beat off the grid - is not held)
             if not pool.holds(g):
                 if not pool.supports(g):
                     return None
@@ -369,7 +377,7 @@ class OnlineLoop:
         for m in range(self.M):
             h = float(resp_mod[m])
             gp = self.gpmodels[ld][m]
-            chained = pool is not None and h == 1.0 and gp.N >= 1 and getattr(gp, "_slot", None) is not None
+            chained = pool is not None and h == 1.0 and gp.N >= 1 and pool.holds(gp)
             if chained:               # the cluster's persistent chain takes the member step (Kalman + both MNIW updates)
                 pool.commit(gp, b.t, b.x, b.y[:, [ld]])
                 committed = pool

@@ -42,6 +42,10 @@ class StepList(MutableSequence):
         self.touch()
         return self._ls
 
+    def stacked(self):
+        """The tensor [L, ...] the list was built over while it still is that tensor's view (no mutation since), else None."""
+        return self._st
+
     def stack(self):
         """The entries as one contiguous tensor [L, ...]: the underlying tensor itself while stacked, else stacked once per
         stamp.  Read-only for the caller."""

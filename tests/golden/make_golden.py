@@ -731,10 +731,13 @@ def gen_include_batch(tag, rec, n=None, lead=0, n_explore=5, leads=None, warp=Fa
 
 
 # ------------------------------------- SURVEY 8b Face 1 / configs[4]: the online step, GPI_HDP.include_sample
-def gen_include_sample(tag, rec, n, T_res=None, lead=0, with_warp=False):
+def gen_include_sample(tag, rec, n, T_res=None, lead=0, with_warp=False, off_grid=None):
     """Run the reference's online loop as hdpgpc/tests/test_online.py:41-83 drives it (n_f = 30, free_deg_MNIV = 20, warp
     off, theta injected) on the first n beats of a record - optionally resampled to T_res points by linear interpolation
-    (BASELINE configs[4] names T = 256) - and record after every beat what the step decided and scored."""
+    (BASELINE configs[4] names T = 256) - and record after every beat what the step decided and scored.
+    off_grid = (beat indices, shift): those beats are handed over on the grid x_basis + shift (key x_shift[n]: the per-beat
+    shift), so they leave the shared-grid short cut of pred_dist (GPI.py:467-468); such a trace also records the reference's
+    own sensitivity (ref_sens, ref_sens_row[n]: the same run on inputs perturbed by 1e-15 relative)."""
     import time
     if isinstance(rec, (list, tuple)):     # BASELINE configs[4] "concatenated MIT-BIH records": n beats of each record, one after the other
         raw = np.concatenate([np.load(os.path.join(REF, "data", "mitbih", f"{r}.npy"))[:n, :, [lead]] for r in rec])
@@ -755,10 +758,14 @@ def gen_include_sample(tag, rec, n, T_res=None, lead=0, with_warp=False):
                      mode_warp="rough", bayesian_params=True, inducing_points=False, estimation_limit=None, free_deg_MNIV=20)
     out = {"y": data[..., 0], "x_basis": xb[:, 0], "estimators": np.array([std, std_dif, *bound_sigma, *bound_gamma]),
            "theta_inject": np.array(THETA_INJECT), "with_warp": np.array(bool(with_warp))}
+    x_shift = np.zeros(n)
+    if off_grid is not None:
+        x_shift[sorted(off_grid[0])] = float(off_grid[1])
+        out["x_shift"] = x_shift
     states, Ms, secs = [], [], []
     for i in range(n):
         t0 = time.time()
-        sw.include_sample(xb, data[i], with_warp=bool(with_warp))   # hdpgpc/tests/test_online_warp.py:82 passes True
+        sw.include_sample(xb + x_shift[i], data[i], with_warp=bool(with_warp))   # hdpgpc/tests/test_online_warp.py:82 passes True
         secs.append(time.time() - t0)
         if with_warp:   # what compute_warp_y returned for this beat: liks [M + 1], the warps and the warped beat per cluster
             out[f"b{i}_liks"] = np.asarray(npy(sw.liks[-1]) if torch.is_tensor(sw.liks[-1]) else sw.liks[-1], dtype=np.float64)
@@ -771,6 +778,29 @@ def gen_include_sample(tag, rec, n, T_res=None, lead=0, with_warp=False):
         out[f"b{i}_counts"] = np.array([len(g.indexes) for g in sw.gpmodels[0]], dtype=np.int64)
     out["state"], out["M"], out["secs"] = np.array(states), np.array(Ms), np.array(secs)
     out["transTheta"], out["startTheta"], out["rho"], out["omega"] = npy(sw.transTheta), npy(sw.startTheta), npy(sw.rho), npy(sw.omega)
+    if off_grid is not None:
+        # how sharply are the REFERENCE's scores defined?  Its own run on inputs perturbed by 1e-15 relative (below one ulp)
+        data_p = data * (1.0 + 1e-15 * np.random.default_rng(0).standard_normal(data.shape))
+        sw2 = HDP.GPI_HDP(xb, x_basis_warp=xb[::2], n_outputs=1, kernels=None, model_type="dynamic", ini_lengthscale=3.0,
+                          bound_lengthscale=(1.0, 20.0), ini_gamma=std_dif, ini_sigma=std, ini_outputscale=300.0, noise_warp=std * 0.1,
+                          bound_sigma=bound_sigma, bound_gamma=bound_gamma, bound_noise_warp=(std * 0.01, std * 0.02),
+                          warp_updating=False, method_compute_warp="greedy", verbose=False, hmm_switch=True, max_models=100,
+                          mode_warp="rough", bayesian_params=True, inducing_points=False, estimation_limit=None, free_deg_MNIV=20)
+        same, row = True, np.zeros(n)
+        for i in range(n):
+            sw2.include_sample(xb + x_shift[i], data_p[i], with_warp=False)
+            q0, q1 = out[f"b{i}_q"], npy(sw2.q[-1])
+            same = same and sw2.actual_state == states[i] and sw2.M == Ms[i] and q1.shape == q0.shape and \
+                np.array_equal(npy(sw2.resp_assigned[-1]).astype(np.int16), out[f"b{i}_labels"])
+            if not same:
+                break
+            fin = np.isfinite(q0)
+            d = np.where(fin, np.abs(q1 - np.where(fin, q0, 0.0)) / np.maximum(np.abs(np.where(fin, q0, 1.0)), 1e-300), 0.0)
+            row[:i + 1] = np.maximum(row[:i + 1], d.reshape(i + 1, -1).max(axis=1))
+        out["ref_pert_same_decisions"] = np.array(same)
+        if same:
+            out["ref_sens"], out["ref_sens_row"] = np.array(row.max()), row
+            print("reference sensitivity of the score matrices to a 1e-15 input perturbation:", row.max(), "per row:", row)
     np.savez_compressed(os.path.join(OUT, f"include_sample_{tag}.npz"), **out)
     print(f"include_sample_{tag}: n={n} T={T} states={states} M={Ms[-1]} total {sum(secs):.1f}s last beat {secs[-1]:.2f}s")
 
@@ -914,6 +944,8 @@ if __name__ == "__main__":
         gen_include_sample("r102_t256_n24", "102", 24, T_res=256)
     if "online256x2" in which:         # configs[4]: two records concatenated (16 beats of record 100, then 16 of record 102), T = 256
         gen_include_sample("r100_r102_t256_n32", ["100", "102"], 16, T_res=256)
+    if "onlinemix" in which:           # beats on and off the basis grid in one run: the per-pair scores and the one-by-one commit
+        gen_include_sample("r102_n37_mixedgrid", "102", 37, off_grid=({5, 19, 20, 21, 29, 30, 31, 34}, 0.3))
     if "fitnb" in which:
         gen_kernel_fit_notebook()
     if "reload" in which:

@@ -25,10 +25,13 @@ def _beat(sw):
 
 
 def run_online(g, n=None):
+    """The first n beats of the trace g (all of them by default).  A trace with the key x_shift hands beat i over on the grid
+    x_basis + x_shift[i]: a non-zero shift takes the beat off the basis grid (make_golden.py gen_include_sample, off_grid)."""
     sw, xb, data = _mirror(g)
+    shift = g["x_shift"] if "x_shift" in getattr(g, "files", g) else np.zeros(data.shape[0])
     tr = []
     for i in range(data.shape[0] if n is None else n):
-        sw.include_sample(xb, data[i], with_warp=False)
+        sw.include_sample(xb + float(shift[i]), data[i], with_warp=False)
         tr.append(_beat(sw))
     return sw, tr
 

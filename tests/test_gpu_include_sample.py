@@ -104,3 +104,48 @@ def test_online_rank1_factor_tracking_t256():
             L = fac[0].cpu().numpy()
             S = m.observation_params.scale.cpu().numpy()
             assert np.max(np.abs(L @ L.T - S)) <= 1e-10 * np.max(np.abs(S))
+
+
+def test_include_sample_mixed_grids_t90():
+    """Beats on and off the basis grid in one run (make_golden.py onlinemix: 37 beats of record 102, beats 5, 19, 20, 21, 29,
+    30, 31 and 34 handed over on the grid x_basis + 0.3).  An off-grid beat is scored by the per-pair kernel, its candidates are
+    built one by one (_eager_candidates) and it is committed with the one-by-one GPI_model methods - on a model whose lists are
+    views of a pool slot's stacks (the observation update of such a commit projects the beat onto the basis,
+    GPI_model.py:1037-1041,1065); the on-grid beats after it must find the chains in the state the off-grid beat left.  Same
+    gate as the other traces: decisions, assignments and sizes identical after every beat, score matrices within 1e-8.  (The
+    reference's own sensitivity to a 1e-15 input perturbation, recorded in the fixture as ref_sens, is 1.0e-13: the scores are
+    sharply defined and 1e-8 stands for the off-grid rows too.)"""
+    import numpy as np
+    g = golden("include_sample_r102_n37_mixedgrid.npz")
+    # the fixture does what the test is about: off-grid beats join existing clusters, and on-grid beats join those clusters later
+    n, M, shift, final = len(g["M"]), g["M"], g["x_shift"], g[f"b{len(g['M']) - 1}_labels"]
+    joins = [i for i in range(1, n) if int(M[i]) == int(M[i - 1])]
+    off_joins = [i for i in joins if shift[i] != 0.0]
+    assert len(off_joins) >= 3, off_joins
+    assert any(shift[j] == 0.0 and j > i and final[j] == final[i] for i in off_joins for j in joins)
+    assert bool(g["ref_pert_same_decisions"]) and float(g["ref_sens"]) * 50 < 1e-8
+    torch.cuda.synchronize()
+    t0 = time.time()
+    _, tr = run_online(g)
+    torch.cuda.synchronize()
+    wall = time.time() - t0
+    worst = compare_online(g, tr, 1e-8)
+    print(f"include_sample, 37 beats T=90, 8 of them off the grid: {wall:.2f} s (reference {float(g['secs'].sum()):.1f} s), worst {worst:.2e}")
+
+
+def test_include_sample_one_by_one_path_t90(monkeypatch):
+    """HGP_ONLINE_EAGER=1: no persistent chains - every beat is scored by _last_scores, proposed by _eager_candidates and
+    committed with include_weighted_sample + bayesian_new_params.  The first 24 beats of the record-102 trace, which hold the
+    joins at beats 13, 19, 20, 21 and 23 (candidates are built and a member is committed to a cluster that has members)."""
+    monkeypatch.setenv("HGP_ONLINE_EAGER", "1")
+    g = golden("include_sample_r102_n40.npz")
+    assert all(int(g["M"][i]) == int(g["M"][i - 1]) for i in (13, 19, 20, 21, 23))
+    torch.cuda.synchronize()
+    t0 = time.time()
+    sw, tr = run_online(g, 24)
+    torch.cuda.synchronize()
+    wall = time.time() - t0
+    assert not sw.__dict__.get("_pools")                      # no pool was created
+    assert all(getattr(m, "_slot", None) is None for m in sw.gpmodels[0])
+    worst = compare_online(g, tr, 1e-8)
+    print(f"include_sample one by one, 24 beats T=90: {wall:.2f} s, worst {worst:.2e}")
