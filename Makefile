@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC   = hdpgpc_amd/csrc
 SRCS   = $(wildcard $(CSRC)/*.hip)
-HDR    = $(CSRC)/tile_f64.hpp $(CSRC)/hgp_internal.hpp $(CSRC)/panel_prod.hpp include/hdpgpc_hip.h include/hdpgpc_hip_fit.h include/hdpgpc_hip_mds.h
+HDR    = $(CSRC)/tile_f64.hpp $(CSRC)/hgp_internal.hpp $(CSRC)/panel_prod.hpp include/hdpgpc_hip.h include/hdpgpc_hip_fit.h include/hdpgpc_hip_mds.h include/hdpgpc_hip_ragged.h
 OBJDIR = build/obj
 OBJS   = $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 LIB    = hdpgpc_amd/lib/libhdpgpc_hip.so
@@ -14,6 +14,10 @@ all: $(LIB)
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDR)
 	mkdir -p $(OBJDIR)
 	$(HIPCC) $(FLAGS) -c -o $@ $<
+
+# the ragged pair kernels are the templates of the rectangular units, instantiated in units of their own
+$(OBJDIR)/hgp_pairs_ragged.o: $(CSRC)/hgp_pairs.hip
+$(OBJDIR)/hgp_pairs_acc_ragged.o: $(CSRC)/hgp_pairs_acc.hip
 
 $(LIB): $(OBJS)
 	mkdir -p hdpgpc_amd/lib

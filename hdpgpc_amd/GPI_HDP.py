@@ -413,16 +413,40 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
             if ind.numel():
                 self.f_ind_old[m] = int(ind[torch.argmax(wq[ind, m])])
 
-    def frozen_scores(self, x, y):
+    def _ragged_input(self, x, y, lengths):
+        """(x, y, lengths) of frozen_scores / cluster_new_batch as device tensors: lists of per-segment arrays (x_n [len], y_n
+        [len, D] or [len] with one lead) are padded (ops.pad_ragged); host lengths are range-checked here."""
+        if isinstance(x, (list, tuple)) and lengths is None:
+            X, Y, lengths = ops.pad_ragged(x, y, self.device)
+            return X, Y.reshape(Y.shape[0], Y.shape[1], -1), lengths
+        x, y = self.cond_to_torch(x), self.cond_to_torch(y)
+        if lengths is not None:
+            if not torch.is_tensor(lengths) or not lengths.is_cuda:
+                len_h = np.asarray(_np(lengths)).reshape(-1)
+                if len_h.shape[0] != x.shape[0] or (len_h.size and (len_h.min() < 1 or len_h.max() > x.shape[1])):
+                    raise ValueError(f"lengths must be [{x.shape[0]}] with entries in [1, {x.shape[1]}]")
+            lengths = ops.to_dev(lengths, torch.int32, self.device).reshape(-1)
+        return x, y, lengths
+
+    def frozen_scores(self, x, y, lengths=None):
         """q[N, M, D]: GPI_model.log_sq_error(x_n, y_n[:, ld], i=-1) of every (segment, cluster, lead) against the LAST state
         of each frozen model (GPI_HDP.py:2981-2985).  Segments on the basis grid share the covariance Sigma_m (pred_dist
         short-circuits, GPI.py:467-468): one factorisation per cluster; all others go through the per-pair kernels in ONE
-        launch per lead."""
+        launch per lead.
+
+        lengths [N] (optional): segments of different lengths, segment n in the first lengths[n] entries of row n of x [N, ld]
+        and y [N, ld, D]; or x, y as lists of per-segment arrays.  A row is on the basis when its length is T and its grid is
+        the basis; the others are one ragged call per lead (PairsPlan.loglik)."""
+        x, y, lengths = self._ragged_input(x, y, lengths)
         N, Ts = x.shape[0], x.shape[1]
         T = self.x_basis_ini.shape[0]
         X = (x[..., 0] if x.dim() == 3 else x).contiguous()
         xb = self.cond_to_torch(self.x_basis_ini).reshape(-1)
-        on_basis = torch.zeros(N, dtype=torch.bool, device=self.device) if Ts != T else (X == xb.unsqueeze(0)).all(dim=1)
+        if lengths is None:
+            on_basis = torch.zeros(N, dtype=torch.bool, device=self.device) if Ts != T else (X == xb.unsqueeze(0)).all(dim=1)
+        else:
+            on_basis = (torch.zeros(N, dtype=torch.bool, device=self.device) if Ts < T
+                        else (lengths == T) & (X[:, :T] == xb.unsqueeze(0)).all(dim=1))
         rows_b = torch.nonzero(on_basis).reshape(-1)
         rows_p = torch.nonzero(~on_basis).reshape(-1)
         q = torch.zeros((N, self.M, self.n_outputs), dtype=f64, device=self.device)
@@ -432,7 +456,7 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
             means = torch.stack([g._mean_of(ci, fi).reshape(-1) for g, (ci, fi) in zip(self.gpmodels[ld], sel)]).contiguous()
             Sig = torch.stack([g.Sigma[ci] for g, (ci, _) in zip(self.gpmodels[ld], sel)]).contiguous()
             if rows_b.numel():
-                Yb = Y[rows_b].contiguous()
+                Yb = Y[rows_b][:, :T].contiguous()
                 nb = Yb.shape[0]
                 for m in range(self.M):
                     items = ops.build_items([m], [0.0], [nb])
@@ -443,21 +467,27 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
                 theta = np.array([g.gp.kernel.params() for g in self.gpmodels[ld]])
                 plan = ops.PairsPlan(T, Ts, theta, device=self.device).update(xb, means, Sig)
                 ops.raise_on_info(plan.info, "pred_dist")
-                score, info = plan.score(X[rows_p].contiguous(), Y[rows_p].contiguous())
+                score, info = plan.score(X[rows_p].contiguous(), Y[rows_p].contiguous(),
+                                         lengths=None if lengths is None else lengths[rows_p])
                 ops.raise_on_info(info, "cluster_new_batch")
                 q[rows_p, :, ld] = score
         return q
 
-    def cluster_new_batch(self, x_trains, y_trains, learning=False, it_limit=None, warp=False):
-        """GPI_HDP.py:2975-3003 (learning=False): classify a batch with the frozen models; returns the label tensor."""
-        x = self.cond_to_torch(x_trains)
-        y = self.cond_to_torch(y_trains)
+    def cluster_new_batch(self, x_trains, y_trains, learning=False, it_limit=None, warp=False, lengths=None):
+        """GPI_HDP.py:2975-3003 (learning=False): classify a batch with the frozen models; returns the label tensor.
+        lengths / list inputs: segments of different lengths, as frozen_scores takes them (learning=False only)."""
+        x, y, lengths = self._ragged_input(x_trains, y_trains, lengths)
+        if lengths is not None:
+            if learning:
+                raise NotImplementedError("training on segments of different lengths is not part of this build")
+            if self.use_snr and self.n_outputs > 1:    # compute_snr compares y with a state on the basis grid (GPI_HDP.py:732-748)
+                raise NotImplementedError("use_snr with more than one lead needs segments on one grid length")
         if learning:
             if warp:
                 raise NotImplementedError("warping is not part of this build")
             return self.cluster_new_batch_learning(x, y, it_limit=it_limit)
         M = self.M
-        q = self.frozen_scores(x, y)
+        q = self.frozen_scores(x, y, lengths)
         snr = torch.stack([torch.stack([self.compute_snr(y[:, :, ld], self.gpmodels[ld][m]) for ld in range(self.n_outputs)], dim=-1)
                            for m in range(M)], dim=1)
         tt, st = _np(self.transTheta), _np(self.startTheta)

@@ -904,13 +904,23 @@ class GPI_model:
         first = exact & (i_vals == 1) & (not no_first)
         return i_vals, first
 
-    def compute_sq_err_all(self, x_trains, y_trains, no_first=False):
-        """GPI_model.py:488-547: score of every segment of the batch under this cluster -> (N,) on the device."""
+    def compute_sq_err_all(self, x_trains, y_trains, no_first=False, lengths=None):
+        """GPI_model.py:488-547: score of every segment of the batch under this cluster -> (N,) on the device.
+
+        Segments of different lengths: lengths [N] with x_trains, y_trains [N, ld] (segment n in the first lengths[n] entries of
+        its row, anything behind it), or lists of per-segment arrays, padded here (ops.pad_ragged).  Such a batch takes the
+        general path - the reference's loop calls log_sq_error segment by segment, GPI_model.py:535-545 - in one ragged call;
+        only a batch whose rows all have full length and lie on the basis grid is the on-basis case it is without lengths."""
+        if lengths is None and isinstance(x_trains, (list, tuple)) and len({np.shape(a)[0] for a in x_trains}) > 1:
+            x_trains, y_trains, lengths = ops.pad_ragged(x_trains, [np.asarray(_host(a)).reshape(-1) for a in y_trains], self.device)
         x_trains = self.cond_to_torch(x_trains)
         y_trains = self.cond_to_torch(y_trains)
         X = (x_trains[..., 0] if x_trains.ndim == 3 else x_trains).contiguous()
         Y = (y_trains[..., 0] if y_trains.ndim == 3 else y_trains).contiguous()
         n, Ts = X.shape
+        if lengths is not None:   # the routing below is decided on the host, as it is from the grids
+            lengths = np.asarray(_host(lengths)).reshape(-1).astype(np.int32)
+        full = lengths is None or bool(lengths.shape == (n,) and np.all(lengths == Ts))
         T = self.x_basis.shape[0]
         out = torch.zeros(n, dtype=f64, device=self.device)
         if len(self.indexes) == 0:
@@ -921,7 +931,7 @@ class GPI_model:
         step_pos = np.searchsorted(np.unique(i_vals), i_vals)
         ci_seg, fi_seg = sel[step_pos, 0], sel[step_pos, 1]
         ini_noise = 1e-2 * float(torch.mean(torch.diagonal(self.Sigma[0])))
-        shared = bool(torch.equal(X, X[0:1].expand_as(X)))
+        shared = full and bool(torch.equal(X, X[0:1].expand_as(X)))
         on_basis = shared and Ts == T and bool(torch.equal(X[0], self.x_basis.reshape(-1)))
         if on_basis:
             # one Cholesky per (step, first) group, every member of the group solved against it (GPI_model.py:519-533)
@@ -966,7 +976,7 @@ class GPI_model:
         plan.update(self.x_basis.reshape(-1).contiguous(), means.contiguous(), Sig)
         ops.raise_on_info(plan.info, "pred_dist")
         fn = torch.as_tensor(np.where(first, ini_noise, 0.0), dtype=f64, device=self.device)
-        score, info = plan.score(X, Y, first_noise=fn, sel=col.astype(np.int32))
+        score, info = plan.score(X, Y, first_noise=fn, sel=col.astype(np.int32), lengths=lengths)
         ops.raise_on_info(info, "compute_sq_err_all")
         return score
 
@@ -1079,6 +1089,11 @@ class GPI_model:
         if lik is None:
             lik = self._memo_put("lds_lik", self._LDS_LISTS, float(self.return_LDS_param_likelihood()), defs)
         return lik
+
+
+def _host(a):
+    """A host array of a list, array or tensor (device tensors are copied)."""
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
 def _step_list(name):

@@ -103,8 +103,9 @@ def sharded_scores(score_fn, x, y, group=None, events=None):
     return gather_rows(local, n, group)
 
 
-def emission_scores(plan, x, y, first_noise=None, group=None, events=None, want_info=False):
+def emission_scores(plan, x, y, first_noise=None, group=None, events=None, want_info=False, lengths=None):
     """Reference scores (no log-determinant) of every (segment, cluster) pair; x, y [N, Ts] replicated on all ranks.
+    lengths [N] (optional): a ragged batch (PairsPlan.loglik); each rank passes its slice on.
     Returns q [N, K] on every rank (and, with want_info, this rank's LAPACK info block [n_loc, K])."""
     infos = []
     if _dist_on(group):
@@ -116,7 +117,8 @@ def emission_scores(plan, x, y, first_noise=None, group=None, events=None, want_
         fnl = None if first_noise is None else first_noise[lo:hi].contiguous()
         if events is not None:
             events[0].record()
-        q, _, info = plan.loglik(xs.contiguous(), ys.contiguous(), first_noise=fnl, want_logdet=False, score=True)
+        lens = None if lengths is None else lengths[lo:hi]
+        q, _, info = plan.loglik(xs.contiguous(), ys.contiguous(), first_noise=fnl, want_logdet=False, score=True, lengths=lens)
         if events is not None:                   # the bracket holds the pair kernels only
             events[1].record()
         infos.append(info)

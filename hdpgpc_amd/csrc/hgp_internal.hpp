@@ -136,6 +136,10 @@ void hgp_internal_sub_batched(const double* A, const double* B, long sA, long sB
 int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, bool flags_done, hipStream_t st);
 int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts, const double* first_noise,
                            const int32_t* sel, double* out_quad, double* out_logdet, int32_t* out_info, hipStream_t st);
+// ragged form (hgp_pairs_acc_ragged.hip): rows ld apart, seg_len[n] real points in row n
+int hgp_internal_pairs_acc_ragged(const hgp_pairs_plan* p, const double* x, const double* y, int N, int ld, const int32_t* seg_len,
+                                  const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet,
+                                  int32_t* out_info, hipStream_t st);
 size_t hgp_internal_acc_bytes(int TP, int K, size_t* sizes /*[6]*/);
 
 // hgp_matlik_coop.hip: the same two terms for 128 < T <= HGP_MAX_T_COOP, one workgroup per item (factor once, packed factor in ws)
@@ -177,7 +181,16 @@ struct PairsArgs {
   int32_t* fb;           // k_pairs: fall-back list [0] = count, [1 .. PAIRS_FB_CAP] = segments, [1 + PAIRS_FB_CAP] = finished workgroups
 };
 
+// The same for a ragged batch (hgp_loglik_pairs_ragged_f64, hgp_pairs_ragged.hip): segment n has seg_len[n] real points, the first
+// of its row; Ts above is then the row stride ld of x and y and nothing else, and score_add is not read (the kernels form the
+// offset from the segment's own length).  A struct of its own: the rectangular kernels keep their kernarg layout.
+struct PairsRagArgs : PairsArgs {
+  const int32_t* seg_len;   // [N], 1 <= seg_len[n] <= Ts; anything else: NaN / info = -1 for the row's pairs
+};
+template <class Args> constexpr bool pairs_ragged = std::is_base_of<PairsRagArgs, Args>::value;
+
 #ifdef HGP_STAMPS
 extern unsigned long long* hgp_internal_stamp_dev;
 #endif
 int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t st);
+int hgp_internal_pairs_fast_ragged(const PairsRagArgs& a, int NB, bool coop, hipStream_t st);

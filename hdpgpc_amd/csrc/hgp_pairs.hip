@@ -2,6 +2,10 @@
 // wavefront per pair) and k_pairs_cooph<NB> (NB/2 waves per pair) for 128 < T <= 256.  (The 4-wave cooperative kernel of round 1,
 // k_pairs_coop, 1.28x slower, was removed in round 3.)
 // The plan (per-cluster operators) and the C-ABI live in hgp_plan.hip; the solve-based kernel in hgp_pairs_acc.hip.
+// This text is compiled twice.  As hgp_pairs.hip it gives the rectangular kernels (KArgs = PairsArgs: every row of x / y has Ts
+// points).  hgp_pairs_ragged.hip includes it with HGP_PAIRS_RAGGED_TU defined and the kernels renamed k_pairs_rag /
+// k_pairs_cooph_rag: KArgs = PairsRagArgs, a length per segment (hgp_loglik_pairs_ragged_f64).  The few places where the two
+// differ go through the PAIRS_* macros above k_pairs; for PairsArgs they expand to what stood there before.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -256,8 +260,33 @@ __device__ __forceinline__ void band_sweeps(d4 (&cov)[NB * (NB + 1) / 2], const 
 // kernel the allocator spilled 126 VGPRs at NB = 8 (284 B of scratch per lane, 189 MB of scratch writes per launch, WRITE_SIZE);
 // apart they need none.  Without a list (a.fb == nullptr: NB < 6, HGP_PAIRS_GENERIC=1) the generic kernel takes every segment.
 constexpr int PAIRS_OCC2_NB = 4;   // largest NB built for two workgroups per CU (<= 256 VGPRs)
+
+// Ragged batches (PairsRagArgs): segment n has seg_len[n] real points and a.Ts is the row stride ld of x / y only.  Everything a
+// kernel derives from the segment's length - sentinels, the unit diagonal of the padding, the regularisation, the factor's order,
+// the iso log-determinant, the score offset - takes it from PAIRS_SEG_LEN, so a ragged row has the bits of a rectangular call of
+// its length.  (Macros and not helper templates over the argument struct: handing `a` to a function by reference, though inlined,
+// left the rectangular generic kernels with other code than before - DESIGN 4.4e.  pairs_bad_len below is such a helper, but only
+// the ragged unit instantiates it.)
+#ifdef HGP_PAIRS_RAGGED_TU
+using KArgs = PairsRagArgs;
+#define PAIRS_SEG_LEN(a, n, ld) __builtin_amdgcn_readfirstlane((a).seg_len[n])
+#define PAIRS_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * 1.8378770664093453)   // -0.5 Ts log(2 pi), the host's expression
+#define PAIRS_SKIP_SEGMENTS(a, off) (a).seg_len += (off)                      // launch_pairs: the lengths move with the other per-segment pointers
+#else
+using KArgs = PairsArgs;
+#define PAIRS_SEG_LEN(a, n, ld) (ld)
+#define PAIRS_SCORE_ADD(a, Ts) (a).score_add
+#define PAIRS_SKIP_SEGMENTS(a, off) (void)0
+#endif
+// a length outside [1, ld]: nothing of the row is read, its pair reports NaN / info = -1
+template <class Args>
+__device__ __forceinline__ void pairs_bad_len(const Args& a, size_t oidx) {
+  a.out_quad[oidx] = __builtin_nan("");
+  if (a.out_logdet) a.out_logdet[oidx] = __builtin_nan("");
+  if (a.out_info) a.out_info[oidx] = -1;
+}
 template <int NB, bool BAND>
-__global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_NB) ? 2 : 1)) void k_pairs(PairsArgs a) {   // T <= 64: two workgroups per CU (the kernel sat 3 registers above that limit)
+__global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_NB) ? 2 : 1)) void k_pairs(KArgs a) {   // T <= 64: two workgroups per CU (the kernel sat 3 registers above that limit)
   constexpr int PW = pairs_waves<NB, BAND>();
   constexpr int TP = 16 * NB;
   constexpr int NH = NB / 2;
@@ -268,7 +297,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
   double* scr = L::scr(smem) + wave * DIAG_SCR;
   double* dall = L::dall(smem);
   int *amask = L::amask(smem), *kmask = L::kmask(smem), *amask4 = L::amask4(smem);
-  const int T = a.T, Ts = a.Ts;
+  const int T = a.T, row_ld = a.Ts;   // row stride of x and y; without lengths also every row's length
   HGP_STAMP_DECL
   HGP_T0();
   int n = blockIdx.x, total = 0;
@@ -279,12 +308,23 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
       n = a.fb[1 + n];
     }
   }
+  const int Ts = PAIRS_SEG_LEN(a, n, row_ld);
+  if constexpr (pairs_ragged<KArgs>) {
+    if (Ts < 1 || Ts > row_ld) {   // (the band kernel lists no such segment: none of the generic kernel's LISTED workgroups leaves here)
+      for (int kk = a.kbeg + tid; kk < a.kend; kk += 64 * PW) {
+        const int kc = a.perm[kk];
+        if ((a.sel && a.sel[n] != kc) || a.scal[8 * kc + 7] != 0.0) continue;   // (flagged clusters: the solve-based kernel reports them)
+        pairs_bad_len(a, a.sel ? (size_t)n : (size_t)n * a.K + kc);
+      }
+      return;
+    }
+  }
 
   // Padding (i >= Ts, k >= T) uses far-apart sentinels instead of bounds predicates: every kernel entry that
   // involves a padded point is then exp(-huge) = 0 by itself (all differences stay finite: < 3e152).
   for (int i = tid; i < TP; i += 64 * PW) {
-    xs[i] = (i < Ts) ? a.x[(size_t)n * Ts + i] / a.ell : 1e150 * (double)(1 + i);
-    ys[i] = (i < Ts) ? a.y[(size_t)n * Ts + i] : 0.0;
+    xs[i] = (i < Ts) ? a.x[(size_t)n * row_ld + i] / a.ell : 1e150 * (double)(1 + i);
+    ys[i] = (i < Ts) ? a.y[(size_t)n * row_ld + i] : 0.0;
     xbs[i] = (i < T) ? a.xb[i] / a.ell : -1e150 * (double)(1 + i);
   }
   if (tid < 24) amask[tid] = 0;   // amask, kmask, amask4
@@ -466,7 +506,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
       double v2 = v + 1e-8 * fmax(fabs(v), F64_EPS);
       double q = wave_sum(dsq) / v2;
       if (lane == 0) {
-        a.out_quad[oidx] = a.score_on ? fma(-0.5, q, a.score_add) : (q);
+        a.out_quad[oidx] = a.score_on ? fma(-0.5, q, PAIRS_SCORE_ADD(a, Ts)) : (q);
         if (a.out_logdet) a.out_logdet[oidx] = (double)Ts * log(v2);
         if (a.out_info) a.out_info[oidx] = (v2 > 0.0) ? 0 : 1;
       }
@@ -647,7 +687,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
     HGP_ACC(4);
     const double q = wave_factor<NB, 2, BAND || (NB < 8)>(cov, Rnone, scr, nullptr, dv, lane, pa, nullptr, 0, Ts);
     if (lane == 0) {
-      a.out_quad[oidx] = a.score_on ? fma(-0.5, q, a.score_add) : (q);
+      a.out_quad[oidx] = a.score_on ? fma(-0.5, q, PAIRS_SCORE_ADD(a, Ts)) : (q);
       if (a.out_logdet) a.out_logdet[oidx] = pa.logdet();
       if (a.out_info) a.out_info[oidx] = pa.info;
     }
@@ -721,7 +761,7 @@ struct PairsCoop {
 // of 4 waves and 34-40 tiles): more than one wave per SIMD, so the latencies and barrier waits of one wave sit under the
 // MFMAs of another.
 template <int NB>
-__global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs_cooph(PairsArgs a) {
+__global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs_cooph(KArgs a) {
   using PC = PairsCoop<NB>;
   using H = CoopH<NB>;
   constexpr int NW = H::NW;
@@ -734,7 +774,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
   int* slotblk = PC::slotblk(smem);
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int T = a.T, Ts = a.Ts;
+  const int T = a.T, row_ld = a.Ts;   // row stride of x and y; without lengths also every row's length
   const int Kg = a.kend - a.kbeg;
 
   // block -> (segment, cluster).  Without `sel` the Kg clusters of the group are spread over the 8 XCDs (block b runs
@@ -760,12 +800,19 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
     kc = a.perm[a.kbeg + kk];
   }
   if (a.scal[8 * kc + 7] != 0.0) return;   // ill-conditioned K~: scored by the solve-based kernel (hgp_pairs_acc.hip)
+  const int Ts = PAIRS_SEG_LEN(a, n, row_ld);
+  if constexpr (pairs_ragged<KArgs>) {
+    if (Ts < 1 || Ts > row_ld) {
+      if (tid == 0) pairs_bad_len(a, a.sel ? (size_t)n : (size_t)n * a.K + kc);
+      return;
+    }
+  }
 
   HGP_STAMP_DECL
   HGP_T0();
   for (int i = tid; i < TP; i += 64 * NW) {   // sentinel padding as in k_pairs
-    xs[i] = (i < Ts) ? a.x[(size_t)n * Ts + i] / a.ell : 1e150 * (double)(1 + i);
-    ys[i] = (i < Ts) ? a.y[(size_t)n * Ts + i] : 0.0;
+    xs[i] = (i < Ts) ? a.x[(size_t)n * row_ld + i] / a.ell : 1e150 * (double)(1 + i);
+    ys[i] = (i < Ts) ? a.y[(size_t)n * row_ld + i] : 0.0;
     xbs[i] = (i < T) ? a.xb[i] / a.ell : -1e150 * (double)(1 + i);
   }
   if (tid < 16) {
@@ -917,7 +964,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
       const double v2 = v + 1e-8 * fmax(fabs(v), F64_EPS);
       double tot_ = 0.0;
       for (int w_ = 0; w_ < NW; ++w_) tot_ += red[w_];
-      a.out_quad[oidx] = a.score_on ? fma(-0.5, tot_ / v2, a.score_add) : (tot_ / v2);
+      a.out_quad[oidx] = a.score_on ? fma(-0.5, tot_ / v2, PAIRS_SCORE_ADD(a, Ts)) : (tot_ / v2);
       if (a.out_logdet) a.out_logdet[oidx] = (double)Ts * log(v2);
       if (a.out_info) a.out_info[oidx] = (v2 > 0.0) ? 0 : 1;
     }
@@ -1073,7 +1120,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
   if (tid == 0) {
     double tot_ = 0.0;
     for (int w_ = 0; w_ < NW; ++w_) tot_ += red[8 + w_];
-    a.out_quad[oidx] = a.score_on ? fma(-0.5, tot_, a.score_add) : (tot_);
+    a.out_quad[oidx] = a.score_on ? fma(-0.5, tot_, PAIRS_SCORE_ADD(a, Ts)) : (tot_);
     if (a.out_logdet) a.out_logdet[oidx] = ld;
     if (a.out_info) a.out_info[oidx] = info;
   }
@@ -1088,7 +1135,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
 }
 
 template <int NB>
-int launch_pairs_cooph(const PairsArgs& a, hipStream_t st) {
+int launch_pairs_cooph(const KArgs& a, hipStream_t st) {
   const size_t lds = PairsCoop<NB>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs_cooph<NB>), lds)) return rc_;
   const int blocks = a.sel ? a.N : a.N * (a.kend - a.kbeg);
@@ -1097,11 +1144,11 @@ int launch_pairs_cooph(const PairsArgs& a, hipStream_t st) {
 }
 
 template <int NB>
-int launch_pairs(const PairsArgs& a0, hipStream_t st) {
+int launch_pairs(const KArgs& a0, hipStream_t st) {
   const size_t lds = PairsLds<NB, pairs_waves<NB, false>()>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, false>), lds)) return rc_;
   if (NB < 6 || (a0.flags & 1) || !a0.fb) {   // mask-driven sweeps for every segment
-    PairsArgs a = a0;
+    KArgs a = a0;
     a.fb = nullptr;
     hipLaunchKernelGGL((k_pairs<NB, false>), dim3(a.N), dim3(64 * WAVES), lds, st, a);
     return launch_status();
@@ -1110,11 +1157,12 @@ int launch_pairs(const PairsArgs& a0, hipStream_t st) {
   const size_t ldsb = PairsLds<NB, PWB>::BYTES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, true>), ldsb)) return rc_;
   for (int off = 0; off < a0.N; off += PAIRS_FB_CAP) {   // the fall-back list holds PAIRS_FB_CAP segments
-    PairsArgs a = a0;
+    KArgs a = a0;
     a.N = std::min(PAIRS_FB_CAP, a0.N - off);
     const size_t oo = a.sel ? (size_t)off : (size_t)off * a.K;
     a.x += (size_t)off * a.Ts;
     a.y += (size_t)off * a.Ts;
+    PAIRS_SKIP_SEGMENTS(a, off);
     if (a.first_noise) a.first_noise += oo;
     if (a.sel) a.sel += off;
     a.out_quad += oo;
@@ -1136,7 +1184,11 @@ int launch_pairs(const PairsArgs& a0, hipStream_t st) {
 }  // namespace
 
 // dispatch by padded size / kernel family (see hgp_loglik_pairs_f64)
+#ifdef HGP_PAIRS_RAGGED_TU
+int hgp_internal_pairs_fast_ragged(const PairsRagArgs& a, int NB, bool coop, hipStream_t st) {
+#else
 int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t st) {
+#endif
   if (coop) return dispatch_nb_coop(16 * NB, [&](auto nb) { return launch_pairs_cooph<decltype(nb)::value>(a, st); });   // NB/2 waves per pair (CoopH)
   return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs<decltype(nb)::value>(a, st); });
 }

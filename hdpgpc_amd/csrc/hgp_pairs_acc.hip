@@ -19,6 +19,8 @@
 // covariance tiles of its own block columns: cov[I][J] = K**[I][J] + sum_K S[K,I]^T Q[K,J], Q[K,J] = (Sigma S - K*)[K,J].
 // Then the cooperative factorisation of tile_f64.hpp (cooph_factor) with the single right-hand side d = y - f*.
 // Workgroups are persistent (grid = acc_grid_for(NB)) and walk the flagged (segment, cluster) pairs.
+// The pair kernel's text is compiled twice, as hgp_pairs.hip is: here for AccArgs, and in hgp_pairs_acc_ragged.hip (which includes
+// this file with HGP_PAIRS_RAGGED_TU defined and the kernel renamed k_pairs_acc_rag) for AccRagArgs, a length per segment.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -33,6 +35,7 @@ namespace {
 __host__ __device__ constexpr int ntl(int NB) { return NB * (NB - 1) / 2; }          // strictly lower tiles
 __host__ __device__ constexpr int tl(int K, int Kp) { return K * (K - 1) / 2 + Kp; }   // K > Kp
 
+#ifndef HGP_PAIRS_RAGGED_TU   // the plan's preparation belongs to the rectangular unit alone
 // ------------------------------------------------------------------------------------------------ flags
 // scal[8k+7] = 1 when cluster k takes the solve-based kernel; acc_list = [count, ids...] (ascending).
 __global__ void k_acc_flags(double* scal, int K, double tol, int32_t* acc_list) {
@@ -164,6 +167,8 @@ __global__ __launch_bounds__(256) void k_acc_prep(AccPrepArgs a) {
   }
 }
 
+#endif  // !HGP_PAIRS_RAGGED_TU
+
 // ------------------------------------------------------------------------------------------------ the pair kernel
 struct AccArgs {
   const double* x;
@@ -188,6 +193,21 @@ struct AccArgs {
   double score_add;   // out_quad = score_on ? -0.5 quad + score_add : quad (hgp_pairs_plan_set_score_output)
   int score_on;
 };
+// ragged batches (hgp_loglik_pairs_ragged_f64): seg_len[n] real points in row n; Ts above is the row stride of x and y only and
+// score_add is not read
+struct AccRagArgs : AccArgs {
+  const int32_t* seg_len;
+};
+template <class Args> constexpr bool acc_ragged = std::is_base_of<AccRagArgs, Args>::value;
+#ifdef HGP_PAIRS_RAGGED_TU   // (macros, as in hgp_pairs.hip)
+using KArgs = AccRagArgs;
+#define ACC_SEG_LEN(a, n, ld) __builtin_amdgcn_readfirstlane((a).seg_len[n])
+#define ACC_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * 1.8378770664093453)   // -0.5 Ts log(2 pi), the host's expression
+#else
+using KArgs = AccArgs;
+#define ACC_SEG_LEN(a, n, ld) (ld)
+#define ACC_SCORE_ADD(a, Ts) (a).score_add
+#endif
 
 // The dynamic LDS of k_pairs_acc<NB>
 template <int NB>
@@ -212,7 +232,7 @@ struct PairsAccLds {
 __device__ __forceinline__ d4 ld4(const double* base, unsigned off) { return *reinterpret_cast<const d4*>(base + off); }
 
 template <int NB>
-__global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs_acc(AccArgs a) {
+__global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs_acc(KArgs a) {
   using H = CoopH<NB>;
   constexpr int NW = H::NW, TP = 16 * NB;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -222,7 +242,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
   int* redi = L::redi(smem);
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int T = a.T, Ts = a.Ts;
+  const int T = a.T, row_ld = a.Ts;   // row stride of x and y; without lengths also every row's length
   const int nflag = a.acc_list[0];
   if (nflag == 0) return;
   const long npairs = a.sel ? (long)a.N : (long)a.N * nflag;
@@ -244,10 +264,21 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
     const bool iso = sc[3] != 0.0;
     const size_t oidx = a.sel ? (size_t)n : (size_t)n * a.K + kc;
     const double fn = a.first_noise ? a.first_noise[oidx] : 0.0;
+    const int Ts = ACC_SEG_LEN(a, n, row_ld);   // everything below takes the segment's own length
+    if constexpr (acc_ragged<KArgs>) {
+      if (Ts < 1 || Ts > row_ld) {   // uniform over the workgroup: nothing of the row is read
+        if (tid == 0) {
+          a.out_quad[oidx] = __builtin_nan("");
+          if (a.out_logdet) a.out_logdet[oidx] = __builtin_nan("");
+          if (a.out_info) a.out_info[oidx] = -1;
+        }
+        continue;
+      }
+    }
     __syncthreads();   // the previous pair is done with the LDS vectors
     for (int i = tid; i < TP; i += 64 * NW) {   // sentinel padding: every kernel entry that touches a padded point is exp(-huge) = 0
-      xs[i] = (i < Ts) ? a.x[(size_t)n * Ts + i] / ell : 1e150 * (double)(1 + i);
-      ys[i] = (i < Ts) ? a.y[(size_t)n * Ts + i] : 0.0;
+      xs[i] = (i < Ts) ? a.x[(size_t)n * row_ld + i] / ell : 1e150 * (double)(1 + i);
+      ys[i] = (i < Ts) ? a.y[(size_t)n * row_ld + i] : 0.0;
       xbs[i] = (i < T) ? a.xb[i] / ell : -1e150 * (double)(1 + i);
       mus[i] = a.mu[(size_t)kc * TP + i];
     }
@@ -341,7 +372,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
         const double v2 = v + 1e-8 * fmax(fabs(v), F64_EPS);
         double tot_ = 0.0;
         for (int w_ = 0; w_ < NW; ++w_) tot_ += red[w_];
-        a.out_quad[oidx] = a.score_on ? fma(-0.5, tot_ / v2, a.score_add) : (tot_ / v2);
+        a.out_quad[oidx] = a.score_on ? fma(-0.5, tot_ / v2, ACC_SCORE_ADD(a, Ts)) : (tot_ / v2);
         if (a.out_logdet) a.out_logdet[oidx] = (double)Ts * log(v2);
         if (a.out_info) a.out_info[oidx] = (v2 > 0.0) ? 0 : 1;
       }
@@ -413,7 +444,7 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
     if (tid == 0) {
       double tot_ = 0.0;
       for (int w_ = 0; w_ < NW; ++w_) tot_ += red[8 + w_];
-      a.out_quad[oidx] = a.score_on ? fma(-0.5, tot_, a.score_add) : (tot_);
+      a.out_quad[oidx] = a.score_on ? fma(-0.5, tot_, ACC_SCORE_ADD(a, Ts)) : (tot_);
       if (a.out_logdet) a.out_logdet[oidx] = ld;
       if (a.out_info) a.out_info[oidx] = info;
     }
@@ -421,14 +452,29 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
 }
 
 template <int NB>
-int launch_pairs_acc(const AccArgs& a, hipStream_t st) {
+int launch_pairs_acc(const KArgs& a, hipStream_t st) {
   const size_t lds = PairsAccLds<NB>::BYTES;
   hipLaunchKernelGGL(k_pairs_acc<NB>, dim3(acc_grid_for(NB)), dim3(64 * CoopH<NB>::NW), lds, st, a);
   return launch_status();
 }
 
+AccArgs acc_args(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts, const double* first_noise, const int32_t* sel,
+                 double* out_quad, double* out_logdet, int32_t* out_info) {
+  return AccArgs{x, y, N, Ts, p->d_xb, p->T, p->d_scal, p->d_mu, p->d_Lop, p->d_LTop, p->d_Dop, p->d_Sop, p->d_acc_list,
+                 first_noise, sel, p->K, out_quad, out_logdet, out_info, p->d_sscr, -0.5 * (double)Ts * 1.8378770664093453, p->score_out};
+}
+
 }  // namespace
 
+#ifdef HGP_PAIRS_RAGGED_TU
+int hgp_internal_pairs_acc_ragged(const hgp_pairs_plan* p, const double* x, const double* y, int N, int ld, const int32_t* seg_len,
+                                  const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet,
+                                  int32_t* out_info, hipStream_t st) {
+  if (p->acc_tol < 0.0) return 0;
+  const AccRagArgs a{acc_args(p, x, y, N, ld, first_noise, sel, out_quad, out_logdet, out_info), seg_len};
+  return dispatch_nb(p->NB, [&](auto nb) { return launch_pairs_acc<decltype(nb)::value>(a, st); });
+}
+#else
 // sizes[0..5]: Lop, LTop, Dop, Sop, mu, sscr (bytes)
 size_t hgp_internal_acc_bytes(int TP, int K, size_t* sizes) {
   const int NB = TP / 16;
@@ -463,7 +509,7 @@ int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, bool flags_done
 int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts, const double* first_noise,
                            const int32_t* sel, double* out_quad, double* out_logdet, int32_t* out_info, hipStream_t st) {
   if (p->acc_tol < 0.0) return 0;
-  AccArgs a{x, y, N, Ts, p->d_xb, p->T, p->d_scal, p->d_mu, p->d_Lop, p->d_LTop, p->d_Dop, p->d_Sop, p->d_acc_list,
-            first_noise, sel, p->K, out_quad, out_logdet, out_info, p->d_sscr, -0.5 * (double)Ts * 1.8378770664093453, p->score_out};
+  const AccArgs a = acc_args(p, x, y, N, Ts, first_noise, sel, out_quad, out_logdet, out_info);
   return dispatch_nb(p->NB, [&](auto nb) { return launch_pairs_acc<decltype(nb)::value>(a, st); });
 }
+#endif  // HGP_PAIRS_RAGGED_TU

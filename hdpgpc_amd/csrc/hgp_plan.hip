@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <new>
 
+#include "../../include/hdpgpc_hip_ragged.h"
 #include "hgp_internal.hpp"
 #include "tile_f64.hpp"
 
@@ -572,11 +573,11 @@ int hgp_pairs_plan_set_score_output(hgp_pairs_plan* p, int on) {
   return 0;
 }
 
-int hgp_loglik_pairs_f64(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts,
-                         const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet,
-                         int32_t* out_info, void* stream) {
-  if (N == 0) return 0;   // an empty batch is a no-op (its pointers may legitimately be null)
-  if (!p || !x || !y || !out_quad || N < 0 || Ts <= 0) return -1;
+// hgp_loglik_pairs_f64 (seg_len == nullptr: every row has ld points) and hgp_loglik_pairs_ragged_f64 (seg_len[n] points in row n)
+static int loglik_pairs(const hgp_pairs_plan* p, const double* x, const double* y, int N, int ld, const int32_t* seg_len,
+                        const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet, int32_t* out_info,
+                        void* stream) {
+  const int Ts = ld;
   if (Ts > HGP_MAX_T_COOP) return -2;
   if (Ts > p->TP) return -2;   // plan was created with a smaller Ts_max
   hipStream_t st = (hipStream_t)stream;
@@ -594,10 +595,29 @@ int hgp_loglik_pairs_f64(const hgp_pairs_plan* p, const double* x, const double*
 #endif
                 p->K, out_quad, out_logdet, out_info, p->d_escr, p->d_eflags, p->nscr, p->escr_stride,
                 env_on("HGP_PAIRS_GENERIC") ? 1 : 0, -0.5 * (double)Ts * 1.8378770664093453, p->score_out, p->d_fb};
-    rc = hgp_internal_pairs_fast(a, p->NB, p->coop, st);
+    rc = seg_len ? hgp_internal_pairs_fast_ragged(PairsRagArgs{a, seg_len}, p->NB, p->coop, st)
+                 : hgp_internal_pairs_fast(a, p->NB, p->coop, st);
   }
-  if (rc == 0) rc = hgp_internal_pairs_acc(p, x, y, N, Ts, first_noise, sel, out_quad, out_logdet, out_info, st);
+  if (rc == 0)
+    rc = seg_len ? hgp_internal_pairs_acc_ragged(p, x, y, N, ld, seg_len, first_noise, sel, out_quad, out_logdet, out_info, st)
+                 : hgp_internal_pairs_acc(p, x, y, N, Ts, first_noise, sel, out_quad, out_logdet, out_info, st);
   return rc;
+}
+
+int hgp_loglik_pairs_f64(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts,
+                         const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet,
+                         int32_t* out_info, void* stream) {
+  if (N == 0) return 0;   // an empty batch is a no-op (its pointers may legitimately be null)
+  if (!p || !x || !y || !out_quad || N < 0 || Ts <= 0) return -1;
+  return loglik_pairs(p, x, y, N, Ts, nullptr, first_noise, sel, out_quad, out_logdet, out_info, stream);
+}
+
+int hgp_loglik_pairs_ragged_f64(const hgp_pairs_plan* p, const double* x, const double* y, int N, int ld, const int32_t* seg_len,
+                                const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet,
+                                int32_t* out_info, void* stream) {
+  if (N == 0) return 0;
+  if (!p || !x || !y || !seg_len || !out_quad || N < 0 || ld <= 0) return -1;
+  return loglik_pairs(p, x, y, N, ld, seg_len, first_noise, sel, out_quad, out_logdet, out_info, stream);
 }
 
 #ifdef HGP_STAMPS

@@ -286,8 +286,14 @@ class PairsPlan:
         """Boolean [K] (host sync): clusters the last update() routed to the solve-based kernel."""
         return self.scalars()[:, 7].cpu().numpy() != 0.0
 
-    def loglik(self, x, y, first_noise=None, want_logdet=True, want_info=True, sel=None, score=False):
+    def loglik(self, x, y, first_noise=None, want_logdet=True, want_info=True, sel=None, score=False, lengths=None):
         """x, y [N,Ts] -> (quad [N,K], logdet [N,K] or None, info [N,K] or None).
+
+        lengths [N] int32 (optional; host array or device tensor): a ragged batch (hgp_loglik_pairs_ragged_f64).  x, y are then
+        [N, ld] with segment n in the first lengths[n] entries of row n, 1 <= lengths[n] <= ld; the rest of a row is never read
+        (ops.pad_ragged fills it with NaN).  Row n's outputs have the bits of loglik(x[n:n+1, :lengths[n]], y[n:n+1, :lengths[n]]).
+        Host lengths outside [1, ld] raise ValueError; device lengths are not looked at on the host: such a row comes back as
+        NaN / info = -1 and the others are unaffected.
 
         sel [N] int32 (optional): segment n is scored against cluster sel[n] only; outputs (and first_noise) are [N].
         score=True: the first output is the reference's score -0.5 quad - 0.5 Ts log(2 pi) (GPI_model.py:285), written by the
@@ -320,16 +326,30 @@ class PairsPlan:
             quad = torch.empty(shape, dtype=torch.float64, device=dev)
             info = torch.empty(shape, dtype=torch.int32, device=dev) if want_info else None
         logdet = torch.empty(shape, dtype=torch.float64, device=dev) if want_logdet else None
+        if lengths is not None:
+            if not torch.is_tensor(lengths) or not lengths.is_cuda:
+                len_h = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
+                if len_h.shape != (N,) or (N and (len_h.min() < 1 or len_h.max() > Ts)):
+                    raise ValueError(f"PairsPlan.loglik: lengths must be [{N}] with entries in [1, {Ts}]")
+            elif tuple(lengths.shape) != (N,):
+                raise ValueError(f"PairsPlan.loglik: lengths must be [{N}]")
+            lengths = to_dev(lengths, torch.int32, dev)
         if bool(score) != self._score_out:
             _ffi.check(_ffi.lib.hgp_pairs_plan_set_score_output(self._h, int(bool(score))), "pairs_plan_set_score_output")
             self._score_out = bool(score)
+        if lengths is not None:
+            _ffi.check(_ffi.lib.hgp_loglik_pairs_ragged_f64(self._h, _ptr(x), _ptr(y), N, Ts, _ptr(lengths), _ptr(first_noise),
+                                                            _ptr(sel), _ptr(quad), _ptr(logdet), _ptr(info), _stream()),
+                       "loglik_pairs_ragged")
+            return quad, logdet, info
         _ffi.check(_ffi.lib.hgp_loglik_pairs_f64(self._h, _ptr(x), _ptr(y), N, Ts, _ptr(first_noise), _ptr(sel), _ptr(quad),
                                                  _ptr(logdet), _ptr(info), _stream()), "loglik_pairs")
         return quad, logdet, info
 
-    def score(self, x, y, first_noise=None, sel=None):
-        """The reference's score: -0.5 quad - 0.5 Ts log(2 pi)  (GPI_model.py:285, no log-determinant)."""
-        q, _, info = self.loglik(x, y, first_noise, want_logdet=False, sel=sel, score=True)
+    def score(self, x, y, first_noise=None, sel=None, lengths=None):
+        """The reference's score: -0.5 quad - 0.5 Ts log(2 pi)  (GPI_model.py:285, no log-determinant); with `lengths` (see
+        loglik) Ts is each segment's own length."""
+        q, _, info = self.loglik(x, y, first_noise, want_logdet=False, sel=sel, score=True, lengths=lengths)
         return q, info
 
     def close(self):
@@ -342,6 +362,29 @@ class PairsPlan:
             self.close()
         except Exception:
             pass
+
+
+def pad_ragged(xs, ys, device="cuda"):
+    """Segments of different lengths as one ragged batch: xs, ys are lists of per-segment 1-D arrays (ys[n] may also be
+    [len, D] for D leads) -> (X [N, ld], Y [N, ld] or [N, ld, D], lengths [N] int32) on the device, ld the longest segment, NaN
+    in the padding (the kernels never read it: PairsPlan.loglik(..., lengths=))."""
+    host = lambda a: np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float64)  # noqa: E731
+    xs = [host(a).reshape(-1) for a in xs]
+    ys = [host(a) for a in ys]
+    if len(xs) != len(ys) or not xs:
+        raise ValueError("pad_ragged: xs and ys must be non-empty lists of the same length")
+    ys = [a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1) for a in ys]
+    lens = np.array([a.shape[0] for a in xs], dtype=np.int32)
+    tail = ys[0].shape[1:]
+    if any(b.shape[0] != n or b.shape[1:] != tail for n, b in zip(lens, ys)) or lens.min() < 1:
+        raise ValueError("pad_ragged: every segment needs a grid and values of one length >= 1 (and one number of leads)")
+    ld = int(lens.max())
+    X = np.full((len(xs), ld), np.nan)
+    Y = np.full((len(xs), ld) + tail, np.nan)
+    for n, (a, b) in enumerate(zip(xs, ys)):
+        X[n, :lens[n]] = a
+        Y[n, :lens[n]] = b
+    return (torch.as_tensor(X, device=device), torch.as_tensor(Y, device=device), torch.as_tensor(lens, device=device))
 
 
 _PLANS = {}                        # (device, T, Ts, K, theta) -> PairsPlan, in least-recently-used order
