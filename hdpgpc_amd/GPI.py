@@ -2,7 +2,7 @@
 error behaviour); all arithmetic runs in HIP kernels through hdpgpc_amd.ops.
 
 Built: the kernel object (scikit-learn's ConstantKernel*RBF + WhiteKernel, GPI_HDP.py:164-166),
-IterativeGaussianProcess.pred_dist (GPI.py:457-503), pred_latent_dist (GPI.py:505-560),
+IterativeGaussianProcess.pred_dist (GPI.py:457-503), pred_latent_dist (GPI.py:505-560), project_y (GPI.py:194-238),
 log_marginal_likelihood (GPI.py:976-1056, value and gradient), KL_divergence (GPI.py:1058-1094), sample_y (GPI.py:564-608, same
 distribution from torch's normals, see its docstring).  Not built here: posterior / backward (the LDS recursion)
 and fit_torch (gpytorch, 8f-2).
@@ -127,6 +127,28 @@ class IterativeGaussianProcess:
         ops.raise_on_info(info, "projection_matrix")
         sol = self._spd_solve(Z[0], ops.gram_rbf(x_t, None, c, ell, 1e-4), ops.gram_rbf(x_t, x_b, c, ell))   # K~^{-1} K(x, xb)
         return sol.T.contiguous()
+
+    def project_y(self, x_train, y, cov, C, Sigma, x_basis=None):
+        """GPI.py:194-238: observations y [T*, D] on the grid x_train carried onto the basis, y_p = C K(xb, x) (K(x, x) +
+        1e-4 I)^{-1} y; returns (y_p [T, D], Sigma).  y itself when x_train is the basis (the reference's torch.equal).  One
+        device call (ops.project_ragged with a batch of one) and one product with C when C is not the identity; `cov` is not
+        used, as in the reference.  A matrix that is not positive definite raises LinAlgError."""
+        x_b = self.x_basis if x_basis is None else self.cond_to_torch(x_basis).reshape(-1, 1)
+        x_t = self.cond_to_torch(x_train).reshape(-1, 1)
+        y = self.cond_to_torch(y)
+        if x_b.shape == x_t.shape and torch.equal(x_b, x_t):
+            return y, Sigma
+        c, ell, _ = self.kernel.params()
+        Y = y.reshape(1, x_t.shape[0], -1).contiguous()
+        yp, info = ops.project_ragged(x_t.reshape(1, -1).contiguous(), Y, None, x_b.reshape(-1).contiguous(), c, ell, 1e-4)
+        ops.raise_on_info(info, "project_y")
+        y_p = yp[0]
+        if C is not None:
+            C = self.cond_to_torch(C)
+            T = x_b.shape[0]
+            if not torch.equal(C, torch.eye(T, dtype=torch_f64, device=self.device)):
+                y_p = ops.gemm_batched(C.contiguous(), y_p.contiguous())
+        return (y_p.reshape(-1) if y.dim() == 1 else y_p), Sigma
 
     def pred_latent_dist(self, x_post, x_fixed, mean_prior, cov_prior):
         """GPI.py:505-560."""

@@ -473,6 +473,24 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
                 q[rows_p, :, ld] = score
         return q
 
+    def project_batch(self, x_trains, y_trains, lengths=None, kernel=None):
+        """Segments of different lengths carried onto the basis grid, all leads in ONE device call (ops.project_ragged):
+        IterativeGaussianProcess.project_y (GPI.py:194-238) per segment, with the kernel a new cluster starts with
+        (ini_outputscale_def, ini_lengthscale, as create_gp_default; no white noise) or `kernel` (anything with params()).
+        Input as frozen_scores takes it: x [N, ld], y [N, ld, D] with lengths [N], or lists of per-segment arrays.  A segment
+        that already is on the basis comes back bit for bit.  Returns (x_b [N, T, 1], y_b [N, T, D]): what include_batch,
+        cluster_new_batch(learning=True), reload_model_from_labels and include_sample take - the front end for training on
+        segments of different lengths.  A segment whose Gram matrix is not positive definite raises LinAlgError."""
+        x, y, lengths = self._ragged_input(x_trains, y_trains, lengths)
+        X = (x[..., 0] if x.dim() == 3 else x).contiguous()
+        Y = y.reshape(X.shape[0], X.shape[1], -1).contiguous()
+        xb = self.cond_to_torch(self.x_basis_ini).reshape(-1).contiguous()
+        c, ell = (self.ini_outputscale_def, float(self.ini_lengthscale)) if kernel is None else kernel.params()[:2]
+        y_b, info = ops.project_ragged(X, Y, lengths, xb, c, ell, 1e-4)
+        ops.raise_on_info(info, "project_batch")
+        x_b = xb.reshape(1, -1, 1).expand(X.shape[0], -1, -1).contiguous()
+        return x_b, y_b
+
     def cluster_new_batch(self, x_trains, y_trains, learning=False, it_limit=None, warp=False, lengths=None):
         """GPI_HDP.py:2975-3003 (learning=False): classify a batch with the frozen models; returns the label tensor.
         lengths / list inputs: segments of different lengths, as frozen_scores takes them (learning=False only)."""

@@ -700,6 +700,56 @@ def smacof_steps(delta, X, state, status, stress, n_iter, n_steps, eps=1e-6, max
                                              _ptr(status), _ptr(stress), _ptr(n_iter), _ptr(ws), stream), "smacof_steps")
 
 
+_project_ws = _StreamWorkspace()   # hgp_project_ragged_f64 (ld > 128 only)
+
+
+def project_release():
+    """Drop the cached workspaces of project_ragged."""
+    _project_ws.release()
+
+
+def project_ragged(x, y, lengths, xb, c, ell, jitter=1e-4):
+    """IterativeGaussianProcess.project_y (GPI.py:194-238, C = I) for a ragged batch in one call (hgp_project_ragged_f64):
+    yp[n] = K(xb, x_n) (K(x_n, x_n) + jitter I)^-1 y_n with the two-argument kernel c * RBF(ell) (no white noise).
+
+    x [N, ld], y [N, ld, D] (or [N, ld]: one lead) with segment n in the first lengths[n] entries of row n; lengths [N] int32
+    (host array or device tensor; None: every row has ld points); xb [T], T and ld <= 256.  The rest of a row is never read
+    (ops.pad_ragged fills it with NaN).  Returns (yp [N, T, D] or [N, T], info [N] int32).  A row of T points whose grid is xb bit
+    for bit is copied (info 0); a row whose matrix is not positive definite has info > 0 and NaN values (raise_on_info raises
+    on it); no row affects another.  Host lengths outside [1, ld] raise ValueError; device lengths are not looked at on the host:
+    such a row comes back as NaN / info = -1."""
+    x = _dev64(x, "x")
+    y = _dev64(y, "y")
+    xb = _dev64(xb.reshape(-1), "xb")
+    if x.dim() != 2 or y.dim() not in (2, 3) or tuple(y.shape[:2]) != tuple(x.shape):
+        raise ValueError("project_ragged: x must be [N, ld] and y [N, ld] or [N, ld, D]")
+    N, ld = x.shape
+    D = 1 if y.dim() == 2 else y.shape[2]
+    T, dev = xb.numel(), x.device
+    if lengths is not None:
+        if not torch.is_tensor(lengths) or not lengths.is_cuda:
+            len_h = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
+            if len_h.shape != (N,) or (N and (len_h.min() < 1 or len_h.max() > ld)):
+                raise ValueError(f"project_ragged: lengths must be [{N}] with entries in [1, {ld}]")
+        elif tuple(lengths.shape) != (N,):
+            raise ValueError(f"project_ragged: lengths must be [{N}]")
+        lengths = to_dev(lengths, torch.int32, dev)
+    yp = torch.empty((N, T) if y.dim() == 2 else (N, T, D), dtype=torch.float64, device=dev)
+    info = torch.empty(N, dtype=torch.int32, device=dev)
+    if N == 0:
+        return yp, info
+    need = int(_ffi.lib.hgp_project_ragged_ws_bytes(N, ld, T, D))
+    ws = None
+    if need:
+        ws, stream = _project_ws.get(dev, need // 8)
+    else:
+        with torch.cuda.device(dev):
+            stream = _stream()
+    _ffi.check(_ffi.lib.hgp_project_ragged_f64(_ptr(x), _ptr(y), _ptr(lengths), N, ld, D, _ptr(xb), T, float(c), float(ell),
+                                               float(jitter), _ptr(yp), _ptr(info), _ptr(ws), need, stream), "project_ragged")
+    return yp, info
+
+
 def rts_chain(J, P, AM, M, Cv):
     """Sequential part of the RTS smoother for all steps in one launch (in place on M [n,T] and Cv [n,T,T]); T <= 96."""
     n, T = M.shape[0], Cv.shape[1]
