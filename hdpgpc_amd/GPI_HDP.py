@@ -16,7 +16,11 @@ driver entry points -
 plus the small public helpers they and the drivers use (``LogLik``, ``_safe_exp``, ``weight_mean``, ``forward``,
 ``backward``, ``coupled_state_coef``, ``compute_trans_A/pi``, ``selected_gpmodels``).  NOT built (each raises
 NotImplementedError): ``include_sample(with_warp=True)`` (the reference's own path raises at its second beat), ``classify=True``,
-several leads online, static models, ``estimation_limit``, inducing points, ``bayesian_params=False``.  ``kernels=`` IS built: scikit-learn
+several leads online, static models, inducing points, ``bayesian_params=False``.  ``estimation_limit`` IS built (a scalar or one
+value per initial cluster: a cluster stops re-estimating its LDS parameters at that many members).
+As in the reference, a cluster that the OFFLINE loop rebuilds from a copy loses its limit (the reference's gpmodel_deepcopy
+builds the copy with default options): after include_batch only clusters that create_gp_default made are still limited.
+``kernels=`` IS built: scikit-learn
 ``ConstantKernel * RBF + WhiteKernel`` objects or ``RBFWhiteKernel`` are read for their parameters, one kernel for all initial clusters (what
 every driver passes); only a list whose kernels differ from cluster to cluster raises.
 
@@ -69,6 +73,9 @@ def _first(v):
     return v[0] if isinstance(v, (list, np.ndarray)) and np.ndim(v) > 0 else v
 
 
+_DEFAULT = object()
+
+
 class GPI_HDP(OfflineLoop, OnlineLoop):
     _default_device = "cuda"     # every tensor of this build lives on the GPU
 
@@ -90,8 +97,8 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
             if any(p_ != pars[0] for p_ in pars[1:]):
                 raise NotImplementedError("kernels=: different initial kernels per cluster are not part of this build")
             kern0 = pars[0]
-        if inducing_points or estimation_limit is not None:
-            raise NotImplementedError("inducing points / estimation_limit are not part of this build")
+        if np.any(inducing_points):
+            raise NotImplementedError("inducing points are not part of this build")
         _limit_host_threads()
         self.M = 1 if M is None else int(M)
         self.n_outputs = int(n_outputs)
@@ -116,6 +123,11 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         self.bound_sigma_def = tuple(bound_sigma[0]) if isinstance(bound_sigma, list) else tuple(bound_sigma)
         self.bound_gamma_def = tuple(bound_gamma[0]) if isinstance(bound_gamma, list) else tuple(bound_gamma)
         self.annealing_def = bool(_first(annealing))
+        # GPI_HDP.py:143-144,174,303-307: initial cluster m gets its own limit, every cluster created later the first one
+        limits = list(estimation_limit) if isinstance(estimation_limit, (list, np.ndarray)) else [estimation_limit] * self.M
+        if len(limits) != self.M:
+            raise ValueError("estimation_limit: one value, or one per initial cluster")
+        self.estimation_limit, self.estimation_limit_def = limits, limits[0]
         self.hmm_switch, self.max_models, self.batch = hmm_switch, max_models, batch
         self.use_snr, self.bayesian_params, self.free_deg_MNIV = use_snr, bayesian_params, free_deg_MNIV
         self.n_explore_steps, self.reestimate_initial_params = n_explore_steps, reestimate_initial_params
@@ -140,15 +152,18 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         self.fmsg = self.margPrObs = None
         self.elbo_last = None
         self.snr_norm = None
-        self.gpmodels = [[self.create_gp_default() for _ in range(self.M)] for _ in range(self.n_outputs)]
+        self.gpmodels = [[self.create_gp_default(m, limits[m]) for m in range(self.M)] for _ in range(self.n_outputs)]
         self.init_global_params(self.M)
 
     # ------------------------------------------------------------------ per-cluster models
-    def create_gp_default(self, i=None):
-        """A fresh cluster model with the default priors (GPI_HDP.py:496-572, without the warping systems)."""
+    def create_gp_default(self, i=None, estimation_limit=_DEFAULT):
+        """A fresh cluster model with the default priors (GPI_HDP.py:496-572, without the warping systems); its estimation limit
+        is the default one (the constructor alone hands the initial clusters their own)."""
+        if estimation_limit is _DEFAULT:
+            estimation_limit = self.estimation_limit_def
         kern = RBFWhiteKernel(self.ini_outputscale_def, float(self.ini_lengthscale), self.bound_sigma_def[0], device=self.device)
         gp = GPI_model(kern, self.x_basis_ini, annealing=self.annealing_def, bayesian=self.bayesian_params,
-                       free_deg_MNIV=self.free_deg_MNIV, verbose=self.verbose)
+                       estimation_limit=estimation_limit, free_deg_MNIV=self.free_deg_MNIV, verbose=self.verbose)
         gp.noise_bounds = self.bound_sigma_def
         cond = gp.GPR_dynamic(self.ini_gamma_def, self.ini_sigma_def)
         gp.initial_conditions(ini_A=cond[0], ini_Gamma=cond[1], ini_C=cond[2], ini_Sigma=cond[3])
@@ -272,6 +287,12 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
             print('***** Optim failed. Remain at cur val. ' + str(err))
             rho, omega = self.rho, self.omega
         return rho, omega
+
+    def compute_Pi(self):
+        """GPI_HDP.py:424-429: the expected transition matrix of the Dirichlet pseudo-counts, exp(digamma(transTheta)) with
+        each row divided by its sum (on the host)."""
+        dg = _digamma(_np(self.transTheta))
+        return torch.as_tensor(np.exp(dg - np.log(np.sum(np.exp(dg), axis=1))[:, None]), dtype=f64)
 
     def compute_trans_A(self, M):
         """log transition matrix from the Dirichlet pseudo-counts (GPI_HDP.py:3527-3535): the leading M x M block, each row

@@ -19,7 +19,9 @@ Every other chain runs the same step as a group of one (n_chains = 1): a chain w
 with 128 < T <= 256, whose inversions are the cooperative inverse-only kernels with Z rhs one more list level behind each (the
 batch size picks the inversion kernel, so these chains are not batched).  GPI_model.full_pass_weighted is ``run`` over one job.
 Results are bit-identical to running the chains one after the other.  Chains the graphed step does not cover (static models,
-soft members, irregular grids, T > 256, fewer than 4 members, an estimation limit) take GPI_model._full_pass_eager.
+soft members, irregular grids, T > 256, fewer than 4 members) take GPI_model._full_pass_eager.  A chain with an estimation
+limit runs the full step up to the limit and the frozen step (finish flag 8: no MNIW update, the parameters copied forward)
+behind it, as two consecutive runs (_run_group).
 
 The step itself - a chain's device state, its level lists, the descriptors, the launch order - is member_step.py, which the
 online pool (online_chain.py) runs too; here is the offline orchestration around it.
@@ -44,11 +46,11 @@ class Job:
 
 
 def _graphable(job):
-    """The graphed member step covers: dynamic model, h = 1 for every active member, at least 4 members, no estimation limit,
-    the members on the basis grid, T <= 256."""
+    """The graphed member step covers: dynamic model, h = 1 for every active member, at least 4 members, the members on the
+    basis grid, T <= 256."""
     gp = job.gp
     a = job.active
-    if len(a) < 4 or gp.x_basis.shape[0] > _ffi.MAX_T_COOP or gp.estimation_limit != np.inf:
+    if len(a) < 4 or gp.x_basis.shape[0] > _ffi.MAX_T_COOP:
         return False
     if not bool(torch.any(gp.Gamma[-1] != 0)) or not bool(torch.all(job.resp[a] == 1.0)):
         return False
@@ -87,7 +89,11 @@ def run(jobs):
 
 
 def _run_group(jobs):
-    """The graphed member step over the members of every job (all of one basis length), then commit, RTS pass and scores."""
+    """The graphed member step over the members of every job (all of one basis length), then commit, RTS pass and scores.
+    A chain with an estimation limit E re-estimates its parameters while N' < E (N' = members after the inclusion) and keeps
+    them from then on (GPI_model.py:974,1092): two consecutive runs over the same Chain, the full step for the first members and
+    the frozen step (member_step.py: shorter lists, finish flag 8) for the rest, each in lock-step with the other chains' runs
+    of its kind.  Without a limit the second run is empty."""
     dev = jobs[0].gp.device
     T = int(jobs[0].gp.x_basis.shape[0])
     assert all(j.gp.x_basis.shape[0] == T for j in jobs)
@@ -100,41 +106,30 @@ def _run_group(jobs):
             gp.backwards_pair(1.0)
             gp.bayesian_new_params(1.0)
         j.rest = j.active[head:]
+        j.bad = [0, 0]                                     # status words of the chain's runs (_advance); none without a step
         gp._check_pending()
-    jobs = sorted(jobs, key=lambda j: -len(j.rest))    # longest first: the live set is always a prefix
-    nc = len(jobs)
-    sh = shared_buffers(nc, T, dev)
-    chs = []
-    for c, j in enumerate(jobs):
-        ch = Chain.from_model(j.gp, len(j.gp.f_star) + len(j.rest))
+        # member i of rest makes N' = N + i + 1: estimated while N' < E
+        j.n_full = len(j.rest) if gp.estimation_limit == np.inf else int(min(max(gp.estimation_limit - gp.N - 1, 0), len(j.rest)))
+        ch = j.ch = Chain.from_model(gp, len(gp.f_star) + len(j.rest))
         ch.ws = torch.empty(ws_size(T), dtype=f64, device=dev)            # gathered previous state
         ch.bad = torch.zeros(2, dtype=torch.int32, device=dev)            # [MNIW updates skipped, first step whose filter failed]
         ch.sync = torch.zeros(1, dtype=torch.int32, device=dev)           # inter-block counter of the finish kernel
         # observations of the run; the step reads row (pos - y_row0) inside its gather kernel
         ch.Y = (j.y[j.rest][..., 0] if j.y.ndim == 3 else j.y[j.rest]).reshape(len(j.rest), -1).contiguous()
         ch.y_row0 = int(ch.pos[0])
-        ch.build_lists(sh, c)
-        chs.append(ch)
-    gdev = upload_descs([gather_desc(ch) for ch in chs], dev)
-    fdev = upload_descs([finish_desc(ch, int(bool(j.gp.annealing)), ch.bad) for j, ch in zip(jobs, chs)], dev)
-    levels = _MergedLevels(chs)
-    step = lambda k: member_step(levels, sh, gdev, fdev, 0, k, T)      # noqa: E731  (one member of the first k chains)
-
-    lengths = [len(j.rest) for j in jobs]
-    graphs = []
-    done = 0
-    for k in range(nc, 0, -1):                             # phase: the first k chains are alive for lengths[k-1] - done steps
-        n_it = lengths[k - 1] - done
-        if n_it > 0:
-            graphs.append(_replay([j.gp for j in jobs[:k]], lambda: step(k), n_it, 1 if nc == 1 else 2 * UNROLL))
-            done += n_it
-    bads = [ch.bad.tolist() for ch in chs]             # the first read-back waits for every replay: the graphs may go
-    del graphs
+    for frozen in (False, True):
+        part = [(j, len(j.rest) - j.n_full if frozen else j.n_full) for j in jobs]
+        part = sorted([p for p in part if p[1] > 0], key=lambda p: -p[1])      # longest first: the live set is always a prefix
+        if part:
+            _advance([j for j, _ in part], [n for _, n in part], T, frozen)
+    bads = [j.bad for j in jobs]
+    nc = len(jobs)
     main = torch.cuda.current_stream()
     side = [None] if nc == 1 else [torch.cuda.Stream() for _ in jobs]
-    for j, ch, s, bad in zip(jobs, chs, side, bads):       # commit + backward recursion (lock-step: one stream per chain)
-        gp = j.gp
-        ch.bind_model(gp, int(ch.pos[0]) + 1, float(ch.n0))
+    for j, s, bad in zip(jobs, side, bads):                # commit + backward recursion (lock-step: one stream per chain)
+        gp, ch = j.gp, j.ch
+        L = int(ch.pos[0]) + 1
+        ch.bind_model(gp, L, float(ch.n0), Lp=int(min(L, gp.estimation_limit)))
         for idx in j.rest:
             gp.indexes.append(int(idx))
             gp.x_train.append(j.x[idx])
@@ -157,6 +152,33 @@ def _run_group(jobs):
         gp = j.gp
         gp._check_pending()
         j.out = (gp.compute_sq_err_all(j.x, j.y), gp.compute_q_lat_all(j.x))
+        del j.ch
+
+
+def _advance(jobs, lengths, T, frozen):
+    """lengths[c] member steps of the chain of jobs[c] (lengths descending), side by side; frozen: the step of a chain at its
+    estimation limit.  Waits for the steps and leaves every chain's status words in its job (job.bad)."""
+    dev = jobs[0].gp.device
+    nc = len(jobs)
+    sh = shared_buffers(nc, T, dev)
+    chs = [j.ch for j in jobs]
+    for c, ch in enumerate(chs):
+        ch.build_lists(sh, c, frozen=frozen)
+    gdev = upload_descs([gather_desc(ch) for ch in chs], dev)
+    fdev = upload_descs([finish_desc(ch, int(bool(j.gp.annealing)) | (8 if frozen else 0), ch.bad) for j, ch in zip(jobs, chs)], dev)
+    levels = _MergedLevels(chs)
+    step = lambda k: member_step(levels, sh, gdev, fdev, 0, k, T, frozen=frozen)      # noqa: E731  (one member of the first k chains)
+
+    graphs = []
+    done = 0
+    for k in range(nc, 0, -1):                             # phase: the first k chains are alive for lengths[k-1] - done steps
+        n_it = lengths[k - 1] - done
+        if n_it > 0:
+            graphs.append(_replay([j.gp for j in jobs[:k]], lambda: step(k), n_it, 1 if nc == 1 else 2 * UNROLL))
+            done += n_it
+    for j, ch in zip(jobs, chs):                       # the first read-back waits for every replay: the graphs may go
+        j.bad = ch.bad.tolist()                        # (the words accumulate over a chain's runs: its last run's are final)
+    del graphs
 
 
 def _replay(gps, fn, n_iter, min_left):

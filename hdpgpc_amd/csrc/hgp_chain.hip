@@ -388,7 +388,13 @@ using Finish2Args = hgp_chain_finish_desc;   // include/hdpgpc_hip.h
 __device__ __forceinline__ void chain_finish2_body(const Finish2Args& a, int& last) {
   const int T = a.T;
   const long tt = (long)T * T;
-  const bool bad = (a.info1[2] | a.info1[3] | a.info2[0] | a.info2[1]) != 0;
+  // bit 3 = parameters frozen (the cluster reached its estimation limit, GPI_model.py:974,1092): the state rows as always, no
+  // MNIW update - part, Snew, info1[2..3] and info2 may be stale: part and Snew are not read, and the four status words, which
+  // come in with the other scalars of this preamble in ONE round of loads (a second, dependent round costs every step of every
+  // chain about a microsecond), are ignored - and the four parameter rows copied forward, so that row pos + 1 of every stack
+  // holds the last estimated parameters for whoever indexes the stacks by row
+  const bool frozen = (a.annealing & 8) != 0;
+  const bool bad = ((a.info1[2] | a.info1[3] | a.info2[0] | a.info2[1]) != 0) & !frozen;
   const double n0 = a.n0[0], Nf = a.Nf[0] + 1.0;
   const long p = a.pos[0], nxt = p + 1;
   const double n0n = bad ? n0 : n0 + 1.0;
@@ -402,22 +408,28 @@ __device__ __forceinline__ void chain_finish2_body(const Finish2Args& a, int& la
     const bool obs = i >= tt;           // item 0 = internal (A, Gamma): (f_post, f_sm_prev); item 1 = observation (C, Sigma): (y, f_post)
     const long e = obs ? i - tt : i;
     const int r_ = (int)(e / T), c_ = (int)(e % T);
-    double m = a.W[i], r = a.W[2 * tt + i], sc = a.W[4 * tt + i];
-    if (!bad) {
-      const double er = obs ? a.y[r_] - a.f_post[r_] : a.f_post[r_] - a.f_sm_prev[r_];
-      const double ec = obs ? a.y[c_] - a.f_post[c_] : a.f_post[c_] - a.f_sm_prev[c_];
-      m = ((n0 - 2.0) * m + a.part[i]) / (n0 - 1.0);
-      r = a.Snew[i];
-      sc = ((n0 - 2.0) * sc + er * ec) / (n0 - 1.0);
-      if (!dry) {
-        a.W[i] = m;
-        a.W[2 * tt + i] = r;
-        a.W[4 * tt + i] = sc;
-      }
-    }
-    (obs ? a.stC : a.stA)[nxt * tt + e] = m;
+    double* sm = obs ? a.stC : a.stA;
     double* sg = obs ? a.stS : a.stG;
-    sg[nxt * tt + e] = sc * scl + sg[e] * ann;
+    if (frozen) {
+      sm[nxt * tt + e] = sm[p * tt + e];
+      sg[nxt * tt + e] = sg[p * tt + e];
+    } else {
+      double m = a.W[i], r = a.W[2 * tt + i], sc = a.W[4 * tt + i];
+      if (!bad) {
+        const double er = obs ? a.y[r_] - a.f_post[r_] : a.f_post[r_] - a.f_sm_prev[r_];
+        const double ec = obs ? a.y[c_] - a.f_post[c_] : a.f_post[c_] - a.f_sm_prev[c_];
+        m = ((n0 - 2.0) * m + a.part[i]) / (n0 - 1.0);
+        r = a.Snew[i];
+        sc = ((n0 - 2.0) * sc + er * ec) / (n0 - 1.0);
+        if (!dry) {
+          a.W[i] = m;
+          a.W[2 * tt + i] = r;
+          a.W[4 * tt + i] = sc;
+        }
+      }
+      sm[nxt * tt + e] = m;
+      sg[nxt * tt + e] = sc * scl + sg[e] * ann;
+    }
     if (!obs) {                          // the state lists (scatter)
       const double cp = a.c_post[e];
       a.stP[nxt * tt + e] = cp;
@@ -439,11 +451,11 @@ __device__ __forceinline__ void chain_finish2_body(const Finish2Args& a, int& la
   __syncthreads();
   if (last && threadIdx.x == 0) {
     if (!dry) {
-      a.n0[0] = n0n;
+      if (!frozen) a.n0[0] = n0n;
       a.Nf[0] = Nf;
       a.pos[0] = nxt;
     }
-    a.bad_count[0] += bad ? 1 : 0;
+    if (!frozen) a.bad_count[0] += bad ? 1 : 0;
     if (a.bad_count[1] == 0 && (a.info1[0] | a.info1[1]) != 0) a.bad_count[1] = (int32_t)nxt;
     a.sync[0] = 0;
   }

@@ -18,6 +18,7 @@ from .steplist import StepList
 f64 = torch.float64
 _p = ops._ptr
 _STACKS = ("A", "G", "C", "S", "Psm", "P", "F", "Fsm")          # order of hgp_chain_gather_desc.st
+_PARAMS = _STACKS[:4]                                            # the parameter stacks (an estimation limit freezes them)
 _LISTS = {"A": "A", "G": "Gamma", "C": "C", "S": "Sigma", "Psm": "cov_f_sm", "P": "cov_f", "F": "f_star", "Fsm": "f_star_sm"}
 # a chain's gathered previous state `ws` (written by the gather kernel): six T x T matrices, then two T-vectors
 _WS = ("A", "G", "C", "S", "Psm", "c0", "m0", "Fsm")
@@ -71,7 +72,9 @@ class Chain:
     @classmethod
     def from_model(cls, gp, rows):
         """Stacks with room for `rows` rows holding the model's lists, its position and counters, and its two MNIW distributions
-        (internal, observation) as one tensor: W[0] = means, W[1] = right covariances, W[2] = scales, each [2,T,T]."""
+        (internal, observation) as one tensor: W[0] = means, W[1] = right covariances, W[2] = scales, each [2,T,T].  The
+        parameter lists of a model with an estimation limit are shorter than its state lists: the rows behind them hold the
+        last parameters, as the frozen finish (flag 8, include/hdpgpc_hip.h) leaves them."""
         T = gp.x_basis.shape[0]
         L = len(gp.f_star)
         dev = gp.device
@@ -79,7 +82,11 @@ class Chain:
         for key in _STACKS:
             shape = (T, 1) if key in ("F", "Fsm") else (T, T)
             buf = torch.empty((rows,) + shape, dtype=f64, device=dev)
-            buf[:L] = getattr(gp, _LISTS[key]).stack().reshape((L,) + shape)
+            rows_ = getattr(gp, _LISTS[key]).stack()
+            n = rows_.shape[0]
+            buf[:n] = rows_.reshape((n,) + shape)
+            if n < L:
+                buf[n:L] = buf[n - 1]
             buf[L:].zero_()
             setattr(ch, key, buf)
         ch.pos = torch.tensor([L - 1], dtype=torch.int64, device=dev)
@@ -103,11 +110,13 @@ class Chain:
             buf[:old.shape[0]] = old
             setattr(self, key, buf)
 
-    def bind_model(self, gp, L, n0):
-        """The model's lists as views of the first L rows of the stacks, its MNIW distributions as views of W with count n0.
+    def bind_model(self, gp, L, n0, Lp=None):
+        """The model's lists as views of the first L rows of the stacks (the four parameter lists: of the first Lp rows, default
+        L; min(L, estimation limit) for a model that has one), its MNIW distributions as views of W with count n0.
         The only binder: kernels write the stacks and W in place, and NEW lists (new stamps, steplist.py) are what tells the model
         that they did - whoever lets a step write rows a model can see binds again."""
-        views = tuple(StepList(getattr(self, key)[:L]) for key in _STACKS)
+        Lp = L if Lp is None else Lp
+        views = tuple(StepList(getattr(self, key)[:Lp if key in _PARAMS else L]) for key in _STACKS)
         for key, lst in zip(_STACKS, views):
             setattr(gp, _LISTS[key], lst)
         W = self.W
@@ -127,14 +136,16 @@ class Chain:
                 return False
         return True
 
-    def build_lists(self, shared, c, alloc=None):
+    def build_lists(self, shared, c, alloc=None, frozen=False):
         """The member step as ONE launch per dependency level (hgp_chain.hip): every product of the step is an item of a
         device-resident list whose pointers are fixed for the life of the chain; the two inversions carry their right-hand
         sides.  14 launches per member, no torch arithmetic, no allocation (measured: a dependent launch costs ~4.5 us
         whatever it does, so launches - not flops - were the step's time).  128 < T <= 256: the inversions are the
         cooperative inverse-only kernels and Z rhs is one more list level behind each of them (16 launches).
         shared, c: this chain is chain c of shared_buffers (one batched inversion for all of them).  alloc(*shape) (optional):
-        where the step's own buffers come from (a pool hands out slices of its arena); zeroed.  Needs self.ws."""
+        where the step's own buffers come from (a pool hands out slices of its arena); zeroed.  Needs self.ws.
+        frozen: the step of a chain at its estimation limit (finish flag 8, member_step(..., frozen=True)): the same items in
+        the same order minus what only the two MNIW updates consume - SINV, MS, S__, S_, part and the LV_RHS2 level."""
         T = self.T
         riding = T <= _ffi.MAX_T_WAVE
         dev = self.ws.device
@@ -162,13 +173,15 @@ class Chain:
         # after INV1 (Z = L^-1 of P, Sk, R0', R1';  Y = Z rhs):  K = (C Pk)^T Sk^-1 = Y1^T Z1,  J = (A c0)^T P^-1 = Y0^T Z0
         lv[4].add(Y4[1], Z4[1], K_t, transA=True)
         lv[4].add(Y4[0], Z4[0], J, transA=True)
-        lv[4].add(Z4[2], Z4[2], SINV[0], transA=True)
-        lv[4].add(Z4[3], Z4[3], SINV[1], transA=True)
+        if not frozen:
+            lv[4].add(Z4[2], Z4[2], SINV[0], transA=True)
+            lv[4].add(Z4[3], Z4[3], SINV[1], transA=True)
         lv[5].add(K_t, innov, f_post, D=xm)
         lv[5].add(K_t, C, IKC, alpha=-1.0, add_eye=1.0)
         lv[5].add(K_t, S, KS)
-        lv[5].add(means[0], SINV[0], MS[0])
-        lv[5].add(means[1], SINV[1], MS[1])
+        if not frozen:
+            lv[5].add(means[0], SINV[0], MS[0])
+            lv[5].add(means[1], SINV[1], MS[1])
         lv[6].add(IKC, Pk, T1)
         lv[6].add(KS, K_t, KKt, transB=True)
         lv[6].add(KS, K_t, KKtmP, D=P, transB=True, beta=-1.0)
@@ -177,13 +190,14 @@ class Chain:
         lv[7].add(T1, IKC, CmP, D=KKtmP, transB=True)             # c_post - P for the smoother
         lv[7].add(J, w, f_sm_prev, D=m0)
         lv[8].add(J, CmP, X)
-        lv[8].add(f_sm_prev, f_sm_prev, S__[0], D=SINV[0], transB=True)      # y2 y2^T + R'^-1 (GPI_model.py:1317-1322)
-        lv[8].add(f_post, f_post, S__[1], D=SINV[1], transB=True)
-        lv[8].add(f_post, f_sm_prev, S_[0], D=MS[0], transB=True)            # y1 y2^T + M R'^-1
-        lv[8].add(y, f_post, S_[1], D=MS[1], transB=True)
-        # after INV2 (Zs of S__ + 1e-8 I;  Y3 = Zs S_^T):  S_ S__^-1 = Y3^T Zs
-        lv[9].add(Y3[0], Zs[0], part[0], transA=True)
-        lv[9].add(Y3[1], Zs[1], part[1], transA=True)
+        if not frozen:
+            lv[8].add(f_sm_prev, f_sm_prev, S__[0], D=SINV[0], transB=True)  # y2 y2^T + R'^-1 (GPI_model.py:1317-1322)
+            lv[8].add(f_post, f_post, S__[1], D=SINV[1], transB=True)
+            lv[8].add(f_post, f_sm_prev, S_[0], D=MS[0], transB=True)        # y1 y2^T + M R'^-1
+            lv[8].add(y, f_post, S_[1], D=MS[1], transB=True)
+            # after INV2 (Zs of S__ + 1e-8 I;  Y3 = Zs S_^T):  S_ S__^-1 = Y3^T Zs
+            lv[9].add(Y3[0], Zs[0], part[0], transA=True)
+            lv[9].add(Y3[1], Zs[1], part[1], transA=True)
         lv[9].add(X, J, P_sm_prev, D=c0, transB=True)
         if not riding:
             lvy = [ops.GemmList(dev), ops.GemmList(dev)]          # levels LV_RHS4, LV_RHS2
@@ -191,7 +205,7 @@ class Chain:
             lvy[0].add(Z4[1], RH4[1], Y4[1])                     # Z_S (C P_k)
             lvy[1].add(Zs[0], S_[0], Y3[0], transB=True)         # Z_s S_^T
             lvy[1].add(Zs[1], S_[1], Y3[1], transB=True)
-            lv += lvy
+            lv += lvy[:1] if frozen else lvy
         self.lv = lv
         self.bufs = dict(X4=X4, RH4=RH4, Z4=Z4, Y4=Y4, S__=S__, S_=S_, Zs=Zs, Y3=Y3, part=part, y=y, f_post=f_post, c_post=c_post,
                          f_sm_prev=f_sm_prev, P_sm_prev=P_sm_prev, i4=shared["i4"][c], i2=shared["i2"][c])
@@ -234,11 +248,12 @@ def gather(gdev, lo, hi, T):
     _ffi.check(_ffi.lib.hgp_lds_chain_gather2_batched_f64(base, hi - lo, T, ops._stream()), "chain_gather2_batched")
 
 
-def member_step(levels, shared, gdev, fdev, lo, hi, T, gather_first=True, no_smoother=()):
+def member_step(levels, shared, gdev, fdev, lo, hi, T, gather_first=True, no_smoother=(), frozen=False):
     """One member step of chains [lo, hi), chain-major in every argument:
     levels.run(l, lo, hi) launches level l of those chains; shared: their shared_buffers; gdev / fdev: upload_descs of their
     gather / finish descriptors; gather_first=False: a gather() of this member was already issued; no_smoother: the chains of a
-    step without the pair smoother, whose previous smoothed mean stands where f_sm_prev would."""
+    step without the pair smoother, whose previous smoothed mean stands where f_sm_prev would; frozen: `levels` are
+    build_lists(frozen=True) and fdev carries flag 8 - no second inversion, no LV_RHS2 level."""
     sh = lambda k: shared[k][lo:hi].flatten(0, 1) if k in shared else None          # noqa: E731
     riding = T <= _ffi.MAX_T_WAVE
     if gather_first:
@@ -255,7 +270,9 @@ def member_step(levels, shared, gdev, fdev, lo, hi, T, gather_first=True, no_smo
     for ch in no_smoother:
         ch.bufs["f_sm_prev"].copy_(ws_view(ch.ws, "Fsm", T))
     levels.run(8, lo, hi)
-    if riding:
+    if frozen:
+        pass                      # S__ / S_ were not formed: nothing to invert
+    elif riding:
         ops.chol_inverse_rhs(sh("S__"), sh("Zs"), sh("S_"), sh("Y3"), sh("i2"), rhs_trans=True, add_diag=1e-8)
     else:
         ops.chol_inverse(sh("S__"), 0.0, 1e-8, out=sh("Zs"), info=sh("i2"), work=sh("WK2"))

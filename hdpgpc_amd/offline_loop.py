@@ -71,6 +71,8 @@ class OfflineLoop:
         """GPI_HDP.py:1866-1904: default observation / transition noise from the batch itself (median over the first 10
         grid points of lead 0), new bounds, and every model replaced by a fresh default one."""
         n_f = y.shape[0] - 1
+        if self.estimation_limit_def is not None:                             # GPI_HDP.py:1870-1874
+            n_f = int(min(self.estimation_limit_def, n_f))
         a = y[:n_f, :10, 0].T                                                 # [10, n_f]
         b = y[1:n_f + 1, :10, 0].T
         dev = a - torch.mean(a, dim=1, keepdim=True)
@@ -257,10 +259,18 @@ class OfflineLoop:
     def _fresh_copy(self, gp):
         """gpmodel_deepcopy + reinit of a fitted model (GPI_HDP.py:1289-1292 and its repeats): same kernel and priors, empty
         history."""
-        g = self.gpmodel_deepcopy(gp)
+        g = self._copy_for_rebuild(gp)
         if g.fitted:
             g.reinit_LDS(save_last=False)
             g.reinit_GP(save_last=False)
+        return g
+
+    def _copy_for_rebuild(self, gp):
+        """gpmodel_deepcopy as the variational loop uses it: the copy is rebuilt from its first member on.  The reference
+        constructs such a copy with the default options of GPI_model (GPI_HDP.py:4038-4039), so a rebuilt cluster has NO
+        estimation limit; only models that create_gp_default made carry one.  The traces pin this."""
+        g = self.gpmodel_deepcopy(gp)
+        g.estimation_limit = np.inf
         return g
 
     def _one_member_scores(self, gp_src, x, y, ld, beat, include=True, ycol=None):
@@ -316,7 +326,7 @@ class OfflineLoop:
                     if members != [int(i) for i in gp.indexes]:
                         kind = 1
                         if gp.fitted:
-                            gp = self.gpmodel_deepcopy(gp)
+                            gp = self._copy_for_rebuild(gp)
                             gp.reinit_LDS(save_last=not reparam)
                             gp.reinit_GP(save_last=False)
                         else:

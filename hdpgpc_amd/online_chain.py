@@ -19,7 +19,11 @@ Nothing a candidate computes feeds another one.  Here every cluster model of a l
   are gathered by ONE copy-list launch and scored by one batched call each;
 * ``commit(g, ...)`` is the same step for the cluster that absorbs the beat, for real and without the smoother (the reference's
   commit does not call backwards_pair, GPI_HDP.py:2186-2196): the previous smoothed mean takes the smoother's place in the
-  MNIW update and the previous row is left alone (finish flag 4).
+  MNIW update and the previous row is left alone (finish flag 4);
+* a cluster with an estimation limit E keeps its slot: from the member that makes N' = E on, its finish descriptors (dry and
+  real) carry flag 8 - the state rows as always, no MNIW update, the parameter rows copied forward - so the row-indexed gathers
+  above keep finding the last estimated parameters at row N + 1.  The slot still runs the full level lists: all slots share
+  one set of tile maps.
 """
 import ctypes
 from collections import namedtuple
@@ -180,12 +184,15 @@ class OnlinePool:
 
     @staticmethod
     def supports(g):
-        """The chain step covers: dynamic model, no estimation limit, at least one member, last filtered = last smoothed state
-        (always true for a chain grown online), no tracked rank-1 factor."""
-        if g.N < 1 or g.estimation_limit != np.inf or g._rank1_on() or not g._is_dynamic() or not g._dyn_prior():
+        """The chain step covers: dynamic model, at least one member, last filtered = last smoothed state (always true for a
+        chain grown online), no tracked rank-1 factor; the parameter lists as long as the state lists, or as the estimation
+        limit once the cluster has reached it."""
+        if g.N < 1 or g._rank1_on() or not g._is_dynamic() or not g._dyn_prior():
             return False
         n = len(g.f_star)
-        if not (n == len(g.f_star_sm) == len(g.cov_f) == len(g.cov_f_sm) == len(g.A) == len(g.Gamma) == len(g.C) == len(g.Sigma)):
+        if not (n == len(g.f_star_sm) == len(g.cov_f) == len(g.cov_f_sm)):
+            return False
+        if not (min(n, g.estimation_limit) == len(g.A) == len(g.Gamma) == len(g.C) == len(g.Sigma)):
             return False
         same = lambda a, b: a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape) or bool(torch.equal(a, b))   # noqa: E731
         return same(g.f_star[-1], g.f_star_sm[-1]) and same(g.cov_f[-1], g.cov_f_sm[-1])
@@ -230,7 +237,7 @@ class OnlinePool:
         g = sl.g
         if lat is None:
             lat = self._lat_memo(g)
-        sl.ch.bind_model(g, sl.N + 1, n0)
+        sl.ch.bind_model(g, sl.N + 1, n0, Lp=int(min(sl.N + 1, g.estimation_limit)))
         if lat is not None:
             g._memo_put("lat_all", g._LAT_LISTS, lat, (1.0, len(g.indexes)))
 
@@ -253,10 +260,16 @@ class OnlinePool:
         gd, fd_dry, fd_real = [], [], []
         for c, sl in enumerate(self.slots):
             gd.append(gather_desc(sl.ch))
-            fd_dry.append(finish_desc(sl.ch, int(self.annealing) | 2 | 4, self.badc_all[c]))
-            fd_real.append(finish_desc(sl.ch, int(self.annealing) | 4, self.bad_all[c]))
+            fz = 8 if self._frozen(sl) else 0      # the slot runs the full lists (uniform tile maps); only its finish freezes
+            fd_dry.append(finish_desc(sl.ch, int(self.annealing) | 2 | 4 | fz, self.badc_all[c]))
+            fd_real.append(finish_desc(sl.ch, int(self.annealing) | 4 | fz, self.bad_all[c]))
         self.gdev, self.fdev_dry, self.fdev_real = (upload_descs(d, self.device) for d in (gd, fd_dry, fd_real))
         self.descs_dirty = False
+
+    @staticmethod
+    def _frozen(sl):
+        """Does the slot's next member reach the cluster's estimation limit (N' >= E: no MNIW update, GPI_model.py:974,1092)?"""
+        return sl.N + 1 >= sl.g.estimation_limit
 
     def _step(self, lo, hi, dry, gather_first=True):
         """The member step of slots [lo, hi): a dry run for candidates (nothing of the cluster changes), else the committed step
@@ -419,9 +432,12 @@ class OnlinePool:
         yv = g.cond_to_torch(y).reshape(-1, 1)
         self.ybuf.copy_(yv.reshape(1, T))
         c = g._slot
+        frozen = self._frozen(sl)
         self._step(c, c + 1, dry=False)
         sl.N += 1
         g.N += 1
+        if not frozen and self._frozen(sl):                    # from the next beat on this slot's finish carries flag 8
+            self.descs_dirty = True
         g.indexes.append(int(index))
         g.x_train.append(x_train)
         g.y_train.append(yv)
@@ -441,20 +457,20 @@ class OnlinePool:
             if col is not None and col.shape[0] > int(index):  # the scattered column: two entries change
                 col[ops.to_dev([g.indexes[0], int(index)], torch.int64, self.device)] = out
                 g._memo_put("lat_col", (), col, (new,))
-        self._rebind_lists(sl, float(g.internal_params.n0) + 1.0, lat=new)
-        self._pending = (sl, info)
+        self._rebind_lists(sl, float(g.internal_params.n0) + (0.0 if frozen else 1.0), lat=new)
+        self._pending = (sl, info, frozen)
 
     def finish_commit(self):
         if self._pending is None:
             return
-        (sl, info), self._pending = self._pending, None
+        (sl, info, frozen), self._pending = self._pending, None
         g, c = sl.g, sl.g._slot
         flat = torch.cat([self.bad_all[c].to(f64)] + ([] if info is None else [info.to(f64)])).tolist()     # one round trip
         if flat[1] != 0:
             raise torch.linalg.LinAlgError("posterior: the input is not positive-definite (online step)")
         if any(flat[2:]):
             raise torch.linalg.LinAlgError("log_lat_error: the input is not positive-definite (online step)")
-        updated = int(flat[0]) == sl.bad0
+        updated = frozen or int(flat[0]) == sl.bad0           # (a frozen step has no MNIW update to skip, and did not count one)
         sl.bad0 = int(flat[0])
         if not updated:                                        # the MNIW update was skipped: the distributions kept their count
             if g.verbose:

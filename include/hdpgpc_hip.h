@@ -259,7 +259,13 @@ typedef struct hgp_chain_finish_desc {
   int64_t* pos;
   int32_t* sync;
   int T, annealing;      /* annealing: bit 0 = annealed scales (GPI_model.py:1083-1091); bit 1 = candidate step (new rows are
-                          * written at pos + 1, W / n0 / Nf / pos unchanged); bit 2 = previous smoothed state not rewritten */
+                          * written at pos + 1, W / n0 / Nf / pos unchanged); bit 2 = previous smoothed state not rewritten;
+                          * bit 3 = parameters frozen (a cluster at its estimation limit, GPI_model.py:974,1092): the state rows
+                          * are written as above (bits 1, 2 hold), the whole MNIW tail is skipped - W and n0 untouched, part
+                          * and Snew not read, info1[2..3] and info2 ignored (all four may be stale), bad_count[0] not incremented - and the
+                          * parameter rows are copied forward bitwise, A/G/C/S[pos+1] = A/G/C/S[pos] (also under bit 1), so
+                          * that every reader of row pos + 1 finds the last estimated parameters; Nf and pos advance as
+                          * above (not under bit 1), bad_count[1] still latches info1[0..1] */
 } hgp_chain_finish_desc;
 /* A device-resident list of plain copies dst[0..n) = src[0..n) run as ONE launch (the online step gathers the inputs of its
  * batched a8 / a9 calls from rows of many clusters' stacks).  max_n = the largest n of the list. */
