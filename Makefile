@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC   = hdpgpc_amd/csrc
 SRCS   = $(wildcard $(CSRC)/*.hip)
-HDR    = $(CSRC)/tile_f64.hpp $(CSRC)/hgp_internal.hpp $(CSRC)/panel_prod.hpp include/hdpgpc_hip.h include/hdpgpc_hip_fit.h include/hdpgpc_hip_mds.h include/hdpgpc_hip_ragged.h
+HDR    = $(CSRC)/tile_f64.hpp $(CSRC)/hgp_internal.hpp $(CSRC)/panel_prod.hpp $(wildcard include/*.h)
 OBJDIR = build/obj
 OBJS   = $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 LIB    = hdpgpc_amd/lib/libhdpgpc_hip.so

@@ -1,10 +1,9 @@
 """ctypes binding of libhdpgpc_hip.so, read from include/hdpgpc_hip.h: the header is the one statement of the boundary.
 
 Signatures, struct layouts and the integer #defines all come from parse_header(); an entry point is added by declaring it
-there and wrapping it in ops.py.  include/hdpgpc_hip_fit.h (the batched kernel fit) is a second header of the same library, bound
-into a table of its own (FIT_EXPORTS), and so are include/hdpgpc_hip_mds.h (the MDS embedding, MDS_EXPORTS) and
-include/hdpgpc_hip_ragged.h (the pair path for segments of different lengths, RAGGED_EXPORTS) and include/hdpgpc_hip_project.h
-(projection of ragged batches onto the basis grid, PROJECT_EXPORTS); EXPORTS stays the main header's list.  The product path has no CPU fallback: importing this module without the built library raises.
+there and wrapping it in ops.py.  The library's further headers (HEADERS below) are bound the same way, each into an export table
+of its own; EXPORTS stays the main header's list.  The product path has no CPU fallback: importing this module without the
+built library raises.
 """
 import ctypes
 import os
@@ -16,11 +15,12 @@ from ._cheader import parse_header
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HGP_LIB selects another build of the same library (only the diagnostic `make stamps` build uses it)
 LIB_PATH = os.environ.get("HGP_LIB") or os.path.join(_HERE, "lib", "libhdpgpc_hip.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hdpgpc_hip.h")     # where csrc/hgp_internal.hpp includes it from
-FIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hdpgpc_hip_fit.h")  # the kernel fit: a header and a table of its own
-MDS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hdpgpc_hip_mds.h")  # the MDS embedding: likewise
-RAGGED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hdpgpc_hip_ragged.h")  # ragged pair batches: likewise
-PROJECT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hdpgpc_hip_project.h")  # ragged projection: likewise
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")                          # where csrc/hgp_internal.hpp includes them from
+# (exports attribute of this module, header file): the main header first, then the kernel fit, the MDS embedding, ragged pair
+# batches and ragged projection
+HEADERS = (("EXPORTS", "hdpgpc_hip.h"), ("FIT_EXPORTS", "hdpgpc_hip_fit.h"), ("MDS_EXPORTS", "hdpgpc_hip_mds.h"),
+           ("RAGGED_EXPORTS", "hdpgpc_hip_ragged.h"), ("PROJECT_EXPORTS", "hdpgpc_hip_project.h"))
+HEADER_PATH = os.path.join(_INCLUDE, HEADERS[0][1])
 
 c_dp = ctypes.c_void_p  # device pointers travel as integers
 
@@ -37,37 +37,33 @@ def _load():
         raise ImportError(
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). hdpgpc_amd has no CPU fallback.")
-    for path in (HEADER_PATH, FIT_HEADER_PATH, MDS_HEADER_PATH, RAGGED_HEADER_PATH, PROJECT_HEADER_PATH):
+    paths = [os.path.join(_INCLUDE, header) for _, header in HEADERS]
+    for path in paths:
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: the binding of {LIB_PATH} is read from it. hdpgpc_amd runs from its source tree.")
-    with open(HEADER_PATH) as f:
-        funcs, structs, defines = parse_header(f.read())
-    with open(FIT_HEADER_PATH) as f:
-        fit_funcs, _, fit_defines = parse_header(f.read())
-    with open(MDS_HEADER_PATH) as f:
-        mds_funcs, _, mds_defines = parse_header(f.read())
-    with open(RAGGED_HEADER_PATH) as f:
-        ragged_funcs, _, _ = parse_header(f.read())
-    with open(PROJECT_HEADER_PATH) as f:
-        project_funcs, _, _ = parse_header(f.read())
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**funcs, **fit_funcs, **mds_funcs, **ragged_funcs, **project_funcs}.items():
-        fn = getattr(lib, name)  # AttributeError here = header and library disagree
-        fn.restype = res
-        fn.argtypes = args
+    exports, structs, defines = {}, {}, {}
+    for (attr, _), path in zip(HEADERS, paths):
+        with open(path) as f:
+            funcs, s, d = parse_header(f.read())
+        for name, (res, args) in funcs.items():
+            fn = getattr(lib, name)  # AttributeError here = header and library disagree
+            fn.restype = res
+            fn.argtypes = args
+        exports[attr] = sorted(funcs)
+        structs.update(s)
+        defines.update(d)
     check_abi(lib.hgp_abi_version(), defines["HGP_ABI_VERSION"])
-    return (lib, sorted(funcs), structs, defines, sorted(fit_funcs), fit_defines, sorted(mds_funcs), mds_defines, sorted(ragged_funcs),
-            sorted(project_funcs))
+    return lib, exports, structs, defines
 
 
 def _struct(name, c_name):
     return type(name, (ctypes.Structure,), {"_fields_": _structs[c_name], "__doc__": f"{c_name} of include/hdpgpc_hip.h."})
 
 
-(lib, EXPORTS, _structs, _defines, FIT_EXPORTS, _fit_defines, MDS_EXPORTS, _mds_defines, RAGGED_EXPORTS,
- PROJECT_EXPORTS) = _load()
-FIT_STATE_DOUBLES = _fit_defines["HGP_FIT_STATE_DOUBLES"]
-MDS_STATE_DOUBLES = _mds_defines["HGP_MDS_STATE_DOUBLES"]
+lib, _exports, _structs, _defines = _load()
+globals().update(_exports)          # EXPORTS, FIT_EXPORTS, MDS_EXPORTS, RAGGED_EXPORTS, PROJECT_EXPORTS: sorted names, one list per header
+FIT_STATE_DOUBLES, MDS_STATE_DOUBLES = _defines["HGP_FIT_STATE_DOUBLES"], _defines["HGP_MDS_STATE_DOUBLES"]
 ABI_VERSION, MAX_T_WAVE, MAX_T_COOP = (_defines[k] for k in ("HGP_ABI_VERSION", "HGP_MAX_T_WAVE", "HGP_MAX_T_COOP"))
 GemmItem, ChainGatherDesc = _struct("GemmItem", "hgp_gemm_item"), _struct("ChainGatherDesc", "hgp_chain_gather_desc")
 ChainFinishDesc, CopyItem = _struct("ChainFinishDesc", "hgp_chain_finish_desc"), _struct("CopyItem", "hgp_copy_item")

@@ -245,29 +245,47 @@ int launch_bands(const BandArgs& a, hipStream_t st) {
   return launch_status();
 }
 
+// The caller's workspace of hgp_pred_bands_f64 (doubles), stated once for hgp_pred_bands_ws_bytes and the entry point
+struct BandsWs {
+  double *Kt, *Z, *work, *scal;   // K~ and its inverse factor [S,T,T]; the factor's scratch [S,T,T] (cooperative sizes only); [S,BN_SC]
+  int32_t* finfo;                 // [S] info of the factorisation, in the room of S doubles
+  static constexpr size_t tt(int S, int T) { return (size_t)S * T * T; }
+  static constexpr size_t Kt_off(int, int) { return 0; }
+  static constexpr size_t Z_off(int S, int T) { return Kt_off(S, T) + tt(S, T); }
+  static constexpr size_t work_off(int S, int T) { return Z_off(S, T) + tt(S, T); }
+  static constexpr size_t scal_off(int S, int T) { return work_off(S, T) + (T > HGP_MAX_T_WAVE ? tt(S, T) : 0); }
+  static constexpr size_t finfo_off(int S, int T) { return scal_off(S, T) + (size_t)BN_SC * S; }
+  static constexpr size_t bytes(int S, int T) { return sizeof(double) * (finfo_off(S, T) + S); }
+  static BandsWs carve(void* ws, int S, int T) {
+    double* w = static_cast<double*>(ws);
+    return {w + Kt_off(S, T), w + Z_off(S, T), T > HGP_MAX_T_WAVE ? w + work_off(S, T) : nullptr, w + scal_off(S, T),
+            reinterpret_cast<int32_t*>(w + finfo_off(S, T))};
+  }
+};
+static_assert(BandsWs::bytes(7, 128) == 8 * (2 * 7 * 128 * 128 + 5 * 7) && BandsWs::bytes(7, 129) == 8 * (3 * 7 * 129 * 129 + 5 * 7),
+              "hgp_pred_bands_f64: the workspace callers have sized so far");
+
 }  // namespace
+
+extern "C" size_t hgp_pred_bands_ws_bytes(int S, int T) { return S < 1 || T < 1 ? 0 : BandsWs::bytes(S, T); }
 
 extern "C" int hgp_pred_bands_f64(const double* x_basis, int T, const double* theta3, const double* mean, const double* Sigma,
                                   const int32_t* sigma_idx, int S, const double* xq, int Q, double* mean_q, double* var_q,
-                                  int32_t* info, double* ws, void* stream) {
+                                  int32_t* info, void* ws, size_t ws_bytes, void* stream) {
   if (S < 0 || T < 1 || Q < 0) return -1;
   if (S == 0 || Q == 0) return 0;
   if (!x_basis || !theta3 || !mean || !Sigma || !xq || !mean_q || !var_q || !info || !ws) return -1;
   if (T > HGP_MAX_T_COOP) return -2;
+  if (ws_bytes < BandsWs::bytes(S, T)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  const size_t tt = (size_t)S * T * T;
-  double* Kt = ws;
-  double* Z = ws + tt;
-  double* work = T > HGP_MAX_T_WAVE ? ws + 2 * tt : nullptr;
-  double* scal = ws + (T > HGP_MAX_T_WAVE ? 3 : 2) * tt;
-  int32_t* finfo = reinterpret_cast<int32_t*>(scal + (size_t)BN_SC * S);
-  hipLaunchKernelGGL(k_bands_prep, dim3(S), dim3(256), 0, st, x_basis, T, theta3, Sigma, sigma_idx, Kt, scal);
+  const BandsWs w = BandsWs::carve(ws, S, T);
+  hipLaunchKernelGGL(k_bands_prep, dim3(S), dim3(256), 0, st, x_basis, T, theta3, Sigma, sigma_idx, w.Kt, w.scal);
   int rc = launch_status();
   if (rc) return rc;
-  rc = hgp_chol_inverse_ws_f64(Kt, T, S, 0.0, 0.0, Z, work, finfo, stream);
+  rc = hgp_chol_inverse_ws_f64(w.Kt, T, S, 0.0, 0.0, w.Z, w.work, w.finfo, stream);
   if (rc) return rc;
   const int nb = (T + 15) / 16;
-  BandArgs a{x_basis, T, nb, theta3, mean, Sigma, sigma_idx, S, xq, Q, mean_q, var_q, info, Kt, Z, scal, finfo};
+  BandArgs a{x_basis, T, nb, theta3, mean, Sigma, sigma_idx, S, xq, Q, mean_q, var_q, info, w.Kt, w.Z, w.scal, w.finfo};
   if (nb <= 4) return launch_bands<1>(a, st);
   if (nb <= 8) return launch_bands<2>(a, st);
   if (nb <= 12) return launch_bands<3>(a, st);

@@ -174,22 +174,41 @@ __global__ __launch_bounds__(256) void k_fit_update(FitArgs a) {
   }
 }
 
+// The caller's workspace of hgp_kernel_fit_steps_f64 (doubles), stated once for hgp_kernel_fit_ws_bytes and the entry point
+struct FitWs {
+  double *K, *Z;   // K then K^-1 [B,T,T]; the inverse factor [B,T,T]
+  int32_t* info;   // [B] the factor's status, in the room of B doubles
+  static constexpr size_t tt(int B, int T) { return (size_t)B * T * T; }
+  static constexpr size_t K_off(int, int) { return 0; }
+  static constexpr size_t Z_off(int B, int T) { return K_off(B, T) + tt(B, T); }
+  static constexpr size_t info_off(int B, int T) { return Z_off(B, T) + tt(B, T); }
+  static constexpr size_t bytes(int B, int T) { return sizeof(double) * (info_off(B, T) + B); }
+  static FitWs carve(void* ws, int B, int T) {
+    double* w = static_cast<double*>(ws);
+    return {w + K_off(B, T), w + Z_off(B, T), reinterpret_cast<int32_t*>(w + info_off(B, T))};
+  }
+};
+static_assert(FitWs::bytes(7, 129) == 8 * (2 * 7 * 129 * 129 + 7), "hgp_kernel_fit_steps_f64: the workspace callers have sized so far");
+
 }  // namespace
+
+extern "C" size_t hgp_kernel_fit_ws_bytes(int B, int T) { return B < 1 || T < 1 ? 0 : FitWs::bytes(B, T); }
 
 extern "C" int hgp_kernel_fit_steps_f64(const double* x, long x_stride, const double* Y, int T, int B, const double* bounds, double lr,
                                         int n_steps, int min_iter, int max_iter, double* state, int32_t* status, double* loss_out,
-                                        int loss_ld, double* ws, void* stream) {
+                                        int loss_ld, void* ws, size_t ws_bytes, void* stream) {
   if (T < 1 || B < 1 || n_steps < 0 || x_stride < 0 || !x || !Y || !bounds || !state || !status || !ws) return -1;
   if (loss_out && loss_ld < 1) return -1;
   if (T > HGP_MAX_T_COOP) return -2;
-  hipStream_t st = (hipStream_t)stream;
   const long tt = (long)T * T;
-  double* K = ws;
-  double* Z = ws + (size_t)B * tt;
-  int32_t* info = reinterpret_cast<int32_t*>(ws + (size_t)2 * B * tt);
-  FitArgs a{x, x_stride, Y, T, B, bounds, lr, min_iter, max_iter, state, status, loss_out, loss_ld, K, Z, info};
   const int tiles = (int)((tt + 255) / 256);
   if ((long)tiles * B > 2147483647L) return -2;
+  if (ws_bytes < FitWs::bytes(B, T)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const FitWs w = FitWs::carve(ws, B, T);
+  double *K = w.K, *Z = w.Z;
+  int32_t* info = w.info;
+  FitArgs a{x, x_stride, Y, T, B, bounds, lr, min_iter, max_iter, state, status, loss_out, loss_ld, K, Z, info};
   for (int s = 0; s < n_steps; ++s) {
     hipLaunchKernelGGL(k_fit_gram, dim3((unsigned)(tiles * B)), dim3(256), 0, st, a, tiles);
     if (int rc = launch_status()) return rc;

@@ -179,16 +179,31 @@ __global__ __launch_bounds__(256) void k_mds_finish(MdsArgs a, int P) {
   a.status[b] = end;
 }
 
+// The caller's workspace of hgp_smacof_steps_f64 (doubles), stated once for hgp_smacof_ws_bytes and the entry point
+struct MdsWs {
+  double *Xn, *part;   // X_{k+1} of every start [B,n,p]; the two partial sums of every row of every start [B,n,2]
+  static constexpr size_t Xn_off(int, int, int) { return 0; }
+  static constexpr size_t part_off(int B, int n, int p) { return Xn_off(B, n, p) + (size_t)B * n * p; }
+  static constexpr size_t bytes(int B, int n, int p) { return sizeof(double) * (part_off(B, n, p) + (size_t)B * n * 2); }
+  static MdsWs carve(void* ws, int B, int n, int p) {
+    double* w = static_cast<double*>(ws);
+    return {w + Xn_off(B, n, p), w + part_off(B, n, p)};
+  }
+};
+static_assert(MdsWs::bytes(4, 97, 3) == 8 * 4 * 97 * 5, "hgp_smacof_steps_f64: the workspace callers have sized so far");
+
 }  // namespace
 
+extern "C" size_t hgp_smacof_ws_bytes(int B, int n, int p) { return B < 1 || n < 1 || p < 1 ? 0 : MdsWs::bytes(B, n, p); }
+
 extern "C" int hgp_smacof_steps_f64(const double* delta, int ld, int n, int p, int B, double* X, double eps, int n_steps, int max_iter,
-                                    double* state, int32_t* status, double* stress, int32_t* n_iter, double* ws, void* stream) {
+                                    double* state, int32_t* status, double* stress, int32_t* n_iter, void* ws, size_t ws_bytes, void* stream) {
   if (n < 1 || p < 1 || p > 3 || B < 1 || n_steps < 0 || ld < n) return -1;
   if (!delta || !X || !state || !status || !stress || !n_iter || !ws) return -1;
+  if (ws_bytes < MdsWs::bytes(B, n, p)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  double* Xn = ws;
-  double* part = ws + (size_t)B * n * p;
-  MdsArgs a{delta, ld, n, B, X, eps, max_iter, state, status, stress, n_iter, Xn, part};
+  const MdsWs w = MdsWs::carve(ws, B, n, p);
+  MdsArgs a{delta, ld, n, B, X, eps, max_iter, state, status, stress, n_iter, w.Xn, w.part};
   const unsigned tiles = (unsigned)(((long)n + MDS_ROWS - 1) / MDS_ROWS);
   for (int s = 0; s < n_steps; ++s) {
     if (p == 1) hipLaunchKernelGGL(k_mds_sweep<1>, dim3(tiles), dim3(64 * MDS_ROWS), 0, st, a);

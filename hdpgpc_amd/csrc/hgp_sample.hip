@@ -149,20 +149,37 @@ int launch_sample(const SampleArgs& a, hipStream_t st) {
   return launch_status();
 }
 
+// The caller's workspace of hgp_sample_states_f64 (doubles), stated once for hgp_sample_states_ws_bytes and the entry point
+struct SampleWs {
+  double* L;        // the factors [S,T,T]
+  int32_t* finfo;   // [S] their status, in the room of S doubles
+  static constexpr size_t L_off(int, int) { return 0; }
+  static constexpr size_t finfo_off(int S, int T) { return L_off(S, T) + (size_t)S * T * T; }
+  static constexpr size_t bytes(int S, int T) { return sizeof(double) * (finfo_off(S, T) + S); }
+  static SampleWs carve(void* ws, int S, int T) {
+    double* w = static_cast<double*>(ws);
+    return {w + L_off(S, T), reinterpret_cast<int32_t*>(w + finfo_off(S, T))};
+  }
+};
+static_assert(SampleWs::bytes(7, 129) == 8 * (7 * 129 * 129 + 7), "hgp_sample_states_f64: the workspace callers have sized so far");
+
 }  // namespace
 
+extern "C" size_t hgp_sample_states_ws_bytes(int S, int T) { return S < 1 || T < 1 ? 0 : SampleWs::bytes(S, T); }
+
 extern "C" int hgp_sample_states_f64(const double* mean, const double* cov, const int32_t* cov_idx, int T, int S, const double* z,
-                                     int n, int z_shared, double jitter_rel, double* out, int32_t* info, double* ws, void* stream) {
+                                     int n, int z_shared, double jitter_rel, double* out, int32_t* info, void* ws, size_t ws_bytes,
+                                     void* stream) {
   if (S < 0 || T < 1 || n < 0) return -1;
   if (S == 0 || n == 0) return 0;
   if (!mean || !cov || !z || !out || !info || !ws) return -1;
   if (T > HGP_MAX_T_COOP) return -2;
+  if (ws_bytes < SampleWs::bytes(S, T)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  double* L = ws;
-  int32_t* finfo = reinterpret_cast<int32_t*>(ws + (size_t)S * T * T);
-  if (int rc = hgp_internal_potrf_ws(cov, cov_idx, T, S, jitter_rel, L, finfo, st)) return rc;
+  const SampleWs w = SampleWs::carve(ws, S, T);
+  if (int rc = hgp_internal_potrf_ws(cov, cov_idx, T, S, jitter_rel, w.L, w.finfo, st)) return rc;
   const int nb = (T + 15) / 16;
-  SampleArgs a{mean, cov, cov_idx, T, nb, S, z, n, z_shared ? 0L : (long)n * T, out, info, L, finfo};
+  SampleArgs a{mean, cov, cov_idx, T, nb, S, z, n, z_shared ? 0L : (long)n * T, out, info, w.L, w.finfo};
   if (nb <= 4) return launch_sample<1>(a, st);
   if (nb <= 8) return launch_sample<2>(a, st);
   if (nb <= 12) return launch_sample<3>(a, st);

@@ -77,6 +77,24 @@ def _dev64(t, name):
     return t
 
 
+def _dev_i32(t, n, who, name, shape):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
+        raise TypeError(f"{who}: {name} must be a contiguous int32 tensor [{shape}] on the GPU")
+    return t
+
+
+def _ragged_lengths(who, lengths, N, ld, dev):
+    """lengths= of a ragged batch as an int32 device tensor [N]: host values are checked against [1, ld] here, device values are
+    the kernels' to check (no synchronisation)."""
+    if not torch.is_tensor(lengths) or not lengths.is_cuda:
+        len_h = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
+        if len_h.shape != (N,) or (N and (len_h.min() < 1 or len_h.max() > ld)):
+            raise ValueError(f"{who}: lengths must be [{N}] with entries in [1, {ld}]")
+    elif tuple(lengths.shape) != (N,):
+        raise ValueError(f"{who}: lengths must be [{N}]")
+    return to_dev(lengths, torch.int32, dev)
+
+
 def raise_on_info(info, what):
     """Mirror torch.linalg.cholesky's error behaviour from a per-item LAPACK info tensor (host sync)."""
     host = info.reshape(-1).cpu()          # one copy (torch.nonzero on the device is three launches and a sync: 0.3 ms)
@@ -327,13 +345,7 @@ class PairsPlan:
             info = torch.empty(shape, dtype=torch.int32, device=dev) if want_info else None
         logdet = torch.empty(shape, dtype=torch.float64, device=dev) if want_logdet else None
         if lengths is not None:
-            if not torch.is_tensor(lengths) or not lengths.is_cuda:
-                len_h = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
-                if len_h.shape != (N,) or (N and (len_h.min() < 1 or len_h.max() > Ts)):
-                    raise ValueError(f"PairsPlan.loglik: lengths must be [{N}] with entries in [1, {Ts}]")
-            elif tuple(lengths.shape) != (N,):
-                raise ValueError(f"PairsPlan.loglik: lengths must be [{N}]")
-            lengths = to_dev(lengths, torch.int32, dev)
+            lengths = _ragged_lengths("PairsPlan.loglik", lengths, N, Ts, dev)
         if bool(score) != self._score_out:
             _ffi.check(_ffi.lib.hgp_pairs_plan_set_score_output(self._h, int(bool(score))), "pairs_plan_set_score_output")
             self._score_out = bool(score)
@@ -482,27 +494,33 @@ def kl_sym(meanA, covA, meanB=None, covB=None):
     return out
 
 
-class _StreamWorkspace:
-    """(device index, raw stream handle) -> fp64 workspace of one entry point.  One per stream, so calls queued on different streams
-    of a device never share buffers; it grows to the largest call seen and is kept until release() (pred_bands: S = 2 000 states at
-    T = 90 hold 259 MB).  The key is the raw stream handle: a stream that is created, used for a call and destroyed leaves its
-    entry behind until release()."""
+_WS = {}    # wrapper name -> {(device index, raw stream handle): fp64 workspace}
 
-    def __init__(self):
-        self._ws = {}
 
-    def get(self, dev, need):
-        """(workspace of at least `need` doubles, current stream of dev)"""
-        with torch.cuda.device(dev):
-            stream = _stream()
-        key = (dev.index, stream.value)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(need, dtype=torch.float64, device=dev)
-        return ws, stream
+def _workspace(wrapper, dev, nbytes):
+    """(workspace of at least nbytes bytes - what the library's size function returned - for `wrapper`'s entry point, current stream
+    of dev).  One per wrapper and stream, so calls queued on different streams of a device never share buffers; it grows to the
+    largest call seen and is kept until the wrapper's *_release() (pred_bands: S = 2 000 states at T = 90 hold 259 MB).  The key
+    is the raw stream handle: a stream that is created, used for a call and destroyed leaves its entry behind until then."""
+    with torch.cuda.device(dev):
+        stream = _stream()
+    cache = _WS.setdefault(wrapper, {})
+    key = (dev.index, stream.value)
+    ws = cache.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = cache[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    return ws, stream
 
-    def release(self):
-        self._ws.clear()
+
+def _release_of(wrapper):
+    def release():
+        _WS.pop(wrapper, None)
+    release.__doc__ = f"Drop the cached workspaces of {wrapper} (the memory returns to torch's allocator once queued calls have finished)."
+    return release
+
+
+pred_bands_release, sample_release, kernel_fit_release, smacof_release, project_release = map(
+    _release_of, ("pred_bands", "sample_states", "kernel_fit_steps", "smacof_steps", "project_ragged"))
 
 
 def _stack_index(who, stack, what, idx, idx_name, S, check):
@@ -510,23 +528,15 @@ def _stack_index(who, stack, what, idx, idx_name, S, check):
     if idx is None:
         if stack.shape[0] != S:
             raise ValueError(f"{who}: without {idx_name} the stack holds one {what} per state")
-    elif not (torch.is_tensor(idx) and idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == S):
-        raise TypeError(f"{who}: {idx_name} must be a contiguous int32 tensor [S] on the GPU")
-    elif check and not bool(((idx >= 0) & (idx < stack.shape[0])).all()):
+        return
+    _dev_i32(idx, S, who, idx_name, "S")
+    if check and not bool(((idx >= 0) & (idx < stack.shape[0])).all()):
         raise IndexError(f"{who}: {idx_name} out of range")
 
 
-_bands_ws = _StreamWorkspace()     # hgp_pred_bands_f64
-
-
-def pred_bands_release():
-    """Drop the cached workspaces of pred_bands (the memory returns to torch's allocator once queued calls have finished)."""
-    _bands_ws.release()
-
-
 def pred_bands_ws_doubles(S, T):
-    """HGP_BANDS_WS_DOUBLES of include/hdpgpc_hip.h."""
-    return (3 if T > _ffi.MAX_T_WAVE else 2) * S * T * T + 5 * S
+    """hgp_pred_bands_ws_bytes of include/hdpgpc_hip.h, in doubles."""
+    return _ffi.lib.hgp_pred_bands_ws_bytes(S, T) // 8
 
 
 def pred_bands(x_basis, theta, mean, Sigma, xq, sigma_idx=None, check=False):
@@ -558,25 +568,18 @@ def pred_bands(x_basis, theta, mean, Sigma, xq, sigma_idx=None, check=False):
     info = torch.zeros(S, dtype=torch.int32, device=dev)
     if S == 0 or Q == 0:
         return mean_q, var_q, info
-    ws, stream = _bands_ws.get(dev, pred_bands_ws_doubles(S, T))
+    need = _ffi.lib.hgp_pred_bands_ws_bytes(S, T)
+    ws, stream = _workspace("pred_bands", dev, need)
     _ffi.check(_ffi.lib.hgp_pred_bands_f64(_ptr(x_basis), T, _ptr(theta), _ptr(mean), _ptr(Sigma), _ptr(sigma_idx), S, _ptr(xq), Q,
-                                           _ptr(mean_q), _ptr(var_q), _ptr(info), _ptr(ws), stream), "pred_bands")
+                                           _ptr(mean_q), _ptr(var_q), _ptr(info), _ptr(ws), need, stream), "pred_bands")
     if check:
         raise_on_info(info, "pred_bands")
     return mean_q, var_q, info
 
 
-_sample_ws = _StreamWorkspace()    # hgp_sample_states_f64
-
-
-def sample_release():
-    """Drop the cached workspaces of sample_states (the memory returns to torch's allocator once queued calls have finished)."""
-    _sample_ws.release()
-
-
 def sample_ws_doubles(S, T):
-    """HGP_SAMPLE_WS_DOUBLES of include/hdpgpc_hip.h."""
-    return S * T * T + S
+    """hgp_sample_states_ws_bytes of include/hdpgpc_hip.h, in doubles."""
+    return _ffi.lib.hgp_sample_states_ws_bytes(S, T) // 8
 
 
 def sample_states(mean, cov, z, cov_idx=None, jitter_rel=0.0, check=True):
@@ -604,25 +607,18 @@ def sample_states(mean, cov, z, cov_idx=None, jitter_rel=0.0, check=True):
     info = torch.zeros(S, dtype=torch.int32, device=dev)
     if S == 0 or n == 0:
         return out, info
-    ws, stream = _sample_ws.get(dev, sample_ws_doubles(S, T))
+    need = _ffi.lib.hgp_sample_states_ws_bytes(S, T)
+    ws, stream = _workspace("sample_states", dev, need)
     _ffi.check(_ffi.lib.hgp_sample_states_f64(_ptr(mean), _ptr(cov), _ptr(cov_idx), T, S, _ptr(z), n, int(z.dim() == 2),
-                                              float(jitter_rel), _ptr(out), _ptr(info), _ptr(ws), stream), "sample_states")
+                                              float(jitter_rel), _ptr(out), _ptr(info), _ptr(ws), need, stream), "sample_states")
     if check:
         raise_on_info(info, "sample_states")
     return out, info
 
 
-_fit_ws = _StreamWorkspace()       # hgp_kernel_fit_steps_f64
-
-
-def kernel_fit_release():
-    """Drop the cached workspaces of kernel_fit_steps (the memory returns to torch's allocator once queued calls have finished)."""
-    _fit_ws.release()
-
-
 def kernel_fit_ws_doubles(B, T):
-    """HGP_FIT_WS_DOUBLES of include/hdpgpc_hip_fit.h."""
-    return 2 * B * T * T + B
+    """hgp_kernel_fit_ws_bytes of include/hdpgpc_hip_fit.h, in doubles."""
+    return _ffi.lib.hgp_kernel_fit_ws_bytes(B, T) // 8
 
 
 def kernel_fit_steps(x, Y, bounds, state, status, n_steps, lr=0.1, min_iter=1000, max_iter=4000, loss_out=None):
@@ -640,8 +636,7 @@ def kernel_fit_steps(x, Y, bounds, state, status, n_steps, lr=0.1, min_iter=1000
     bounds, state = _dev64(bounds, "bounds"), _dev64(state, "state")
     if tuple(bounds.shape) != (B, 2) or tuple(state.shape) != (B, _ffi.FIT_STATE_DOUBLES):
         raise ValueError("kernel_fit_steps: bounds must be [B, 2] and state [B, FIT_STATE_DOUBLES]")
-    if not (torch.is_tensor(status) and status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == B):
-        raise TypeError("kernel_fit_steps: status must be a contiguous int32 tensor [B] on the GPU")
+    _dev_i32(status, B, "kernel_fit_steps", "status", "B")
     ld = 0
     if loss_out is not None:
         loss_out = _dev64(loss_out, "loss_out")
@@ -650,23 +645,16 @@ def kernel_fit_steps(x, Y, bounds, state, status, n_steps, lr=0.1, min_iter=1000
         ld = loss_out.shape[1]
     if B == 0 or n_steps == 0:
         return
-    ws, stream = _fit_ws.get(Y.device, kernel_fit_ws_doubles(B, T))
+    need = _ffi.lib.hgp_kernel_fit_ws_bytes(B, T)
+    ws, stream = _workspace("kernel_fit_steps", Y.device, need)
     _ffi.check(_ffi.lib.hgp_kernel_fit_steps_f64(_ptr(x), 0 if x.dim() == 1 else T, _ptr(Y), T, B, _ptr(bounds), float(lr), int(n_steps),
                                                  int(min_iter), int(max_iter), _ptr(state), _ptr(status),
-                                                 _ptr(loss_out) if ld else None, ld, _ptr(ws), stream), "kernel_fit_steps")
-
-
-_mds_ws = _StreamWorkspace()       # hgp_smacof_steps_f64
-
-
-def smacof_release():
-    """Drop the cached workspaces of smacof_steps (the memory returns to torch's allocator once queued calls have finished)."""
-    _mds_ws.release()
+                                                 _ptr(loss_out) if ld else None, ld, _ptr(ws), need, stream), "kernel_fit_steps")
 
 
 def smacof_ws_doubles(B, n, p):
-    """HGP_MDS_WS_DOUBLES of include/hdpgpc_hip_mds.h."""
-    return B * n * (p + 2)
+    """hgp_smacof_ws_bytes of include/hdpgpc_hip_mds.h, in doubles."""
+    return _ffi.lib.hgp_smacof_ws_bytes(B, n, p) // 8
 
 
 def smacof_steps(delta, X, state, status, stress, n_iter, n_steps, eps=1e-6, max_iter=300):
@@ -688,24 +676,16 @@ def smacof_steps(delta, X, state, status, stress, n_iter, n_steps, eps=1e-6, max
     state, stress = _dev64(state, "state"), _dev64(stress, "stress")
     if tuple(state.shape) != (B, _ffi.MDS_STATE_DOUBLES) or stress.numel() != B:
         raise ValueError("smacof_steps: state must be [B, MDS_STATE_DOUBLES] and stress [B]")
-    for t, name in ((status, "status"), (n_iter, "n_iter")):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B):
-            raise TypeError(f"smacof_steps: {name} must be a contiguous int32 tensor [B] on the GPU")
+    _dev_i32(status, B, "smacof_steps", "status", "B")
+    _dev_i32(n_iter, B, "smacof_steps", "n_iter", "B")
     if n_steps < 0:
         raise ValueError("smacof_steps: n_steps < 0")
     if B == 0 or n_steps == 0:
         return
-    ws, stream = _mds_ws.get(X.device, smacof_ws_doubles(B, n, p))
+    need = _ffi.lib.hgp_smacof_ws_bytes(B, n, p)
+    ws, stream = _workspace("smacof_steps", X.device, need)
     _ffi.check(_ffi.lib.hgp_smacof_steps_f64(_ptr(delta), int(ld), n, p, B, _ptr(X), float(eps), int(n_steps), int(max_iter), _ptr(state),
-                                             _ptr(status), _ptr(stress), _ptr(n_iter), _ptr(ws), stream), "smacof_steps")
-
-
-_project_ws = _StreamWorkspace()   # hgp_project_ragged_f64 (ld > 128 only)
-
-
-def project_release():
-    """Drop the cached workspaces of project_ragged."""
-    _project_ws.release()
+                                             _ptr(status), _ptr(stress), _ptr(n_iter), _ptr(ws), need, stream), "smacof_steps")
 
 
 def project_ragged(x, y, lengths, xb, c, ell, jitter=1e-4):
@@ -727,13 +707,7 @@ def project_ragged(x, y, lengths, xb, c, ell, jitter=1e-4):
     D = 1 if y.dim() == 2 else y.shape[2]
     T, dev = xb.numel(), x.device
     if lengths is not None:
-        if not torch.is_tensor(lengths) or not lengths.is_cuda:
-            len_h = np.asarray(lengths.numpy() if torch.is_tensor(lengths) else lengths)
-            if len_h.shape != (N,) or (N and (len_h.min() < 1 or len_h.max() > ld)):
-                raise ValueError(f"project_ragged: lengths must be [{N}] with entries in [1, {ld}]")
-        elif tuple(lengths.shape) != (N,):
-            raise ValueError(f"project_ragged: lengths must be [{N}]")
-        lengths = to_dev(lengths, torch.int32, dev)
+        lengths = _ragged_lengths("project_ragged", lengths, N, ld, dev)
     yp = torch.empty((N, T) if y.dim() == 2 else (N, T, D), dtype=torch.float64, device=dev)
     info = torch.empty(N, dtype=torch.int32, device=dev)
     if N == 0:
@@ -741,7 +715,7 @@ def project_ragged(x, y, lengths, xb, c, ell, jitter=1e-4):
     need = int(_ffi.lib.hgp_project_ragged_ws_bytes(N, ld, T, D))
     ws = None
     if need:
-        ws, stream = _project_ws.get(dev, need // 8)
+        ws, stream = _workspace("project_ragged", dev, need)
     else:
         with torch.cuda.device(dev):
             stream = _stream()

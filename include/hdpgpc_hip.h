@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define HGP_ABI_VERSION 6   /* still 6 with hgp_kl_sym_f64: purely additive, no existing entry changed; 6: + hgp_chol_inverse_ws_f64, candidate / no-smoother flags of the chain finish, - the single-chain gather / scatter / finish glue and its jitter helper (one chain = n_chains 1 of the batched calls); 5: + hgp_pairs_plan_set_score_output, hgp_debug_exp_neg_f64; 3: + hgp_pairs_plan_set_accuracy (solve-based per-pair path), assignment tail, warp fit, member-step lists; 4: + batched chain gather / finish */
+#define HGP_ABI_VERSION 7   /* 7: hgp_pred_bands_f64, hgp_sample_states_f64, hgp_kernel_fit_steps_f64 and hgp_smacof_steps_f64 take `void* ws, size_t ws_bytes` and each has a size function (hgp_*_ws_bytes), - the function-like workspace macros those replace; 6: + hgp_chol_inverse_ws_f64, candidate / no-smoother flags of the chain finish, - the single-chain gather / scatter / finish glue and its jitter helper (one chain = n_chains 1 of the batched calls); 5: + hgp_pairs_plan_set_score_output, hgp_debug_exp_neg_f64; 3: + hgp_pairs_plan_set_accuracy (solve-based per-pair path), assignment tail, warp fit, member-step lists; 4: + batched chain gather / finish */
 /* largest T (basis length) and T* (segment length) served by the register-resident wave kernels */
 #define HGP_MAX_T_WAVE 128
 /* largest T served at all: 128 < T <= 256 runs on cooperative kernels (one workgroup of 4-8 waves per matrix / pair) */
@@ -341,14 +341,15 @@ int hgp_kl_sym_f64(const double* meanA, const double* covA, const double* precA,
  * x_basis [T], T <= HGP_MAX_T_COOP; theta3 [S,3] = (c, ell, noise) per state; mean [S,T]; Sigma a stack [*,T,T] of which state
  * s reads matrix sigma_idx[s] (int32; NULL: s; the values are NOT range-checked: the caller guarantees 0 <= sigma_idx[s] < the
  * stack's length); xq [Q], any order, any Q >= 1; mean_q, var_q [S,Q]; info [S].
- * ws: caller-provided workspace of HGP_BANDS_WS_DOUBLES(S, T) doubles (K~, its inverse factor, per-state scalars).
+ * ws: caller-provided workspace of at least hgp_pred_bands_ws_bytes(S, T) bytes (K~, its inverse factor, per-state scalars; 0 for
+ * S < 1 or T < 1); ws_bytes: what the caller provides - less than that is -1, before any HIP call.
  * info[s] != 0 (the failing pivot of K~_s, or -1 when diag Sigma_s is not finite): both output rows of s are NaN, the other
  * states are unaffected.  An output element depends on its own state and query point only and is reduced in an order fixed
  * by T: the same bits for any Q, any position in xq, any S. */
-#define HGP_BANDS_WS_DOUBLES(S, T) ((size_t)((T) > HGP_MAX_T_WAVE ? 3 : 2) * (size_t)(S) * (T) * (T) + (size_t)5 * (S))
+size_t hgp_pred_bands_ws_bytes(int S, int T);
 int hgp_pred_bands_f64(const double* x_basis, int T, const double* theta3, const double* mean, const double* Sigma,
                        const int32_t* sigma_idx, int S, const double* xq, int Q, double* mean_q, double* var_q, int32_t* info,
-                       double* ws, void* stream);
+                       void* ws, size_t ws_bytes, void* stream);
 
 /* a14 - draws from the Gaussians of cluster states: what GPI_model.sample_last (GPI_model.py:953-961) and
  * IterativeGaussianProcess.sample_y (GPI.py:564-608) take from numpy's multivariate_normal, as the map from standard normals
@@ -358,13 +359,14 @@ int hgp_pred_bands_f64(const double* x_basis, int T, const double* theta3, const
  * mean [S,T], T <= HGP_MAX_T_COOP; cov a stack [*,T,T], only read (int32 cov_idx; NULL: s; the values are NOT range-checked: the
  * caller guarantees 0 <= cov_idx[s] < the stack's length); z standard normals, [n,T] used by every state (z_shared != 0) or
  * [S,n,T]; out [S,n,T]; info [S].
- * ws: caller-provided workspace of HGP_SAMPLE_WS_DOUBLES(S, T) doubles (the factors and their status).
+ * ws: caller-provided workspace of at least hgp_sample_states_ws_bytes(S, T) bytes (the factors and their status; 0 for S < 1 or
+ * T < 1); ws_bytes: what the caller provides - less than that is -1, before any HIP call.
  * info[s] != 0 (the first pivot that was not positive, or -1 when diag cov_m is not finite): all n T outputs of s are NaN, the
  * other states are unaffected.  A draw depends on mean[s], cov_m and z_j only and is summed in an order fixed by T: the same bits
  * for any S, n, z_shared, any position of the state in the call and of the draw in z. */
-#define HGP_SAMPLE_WS_DOUBLES(S, T) ((size_t)(S) * (T) * (T) + (size_t)(S))
+size_t hgp_sample_states_ws_bytes(int S, int T);
 int hgp_sample_states_f64(const double* mean, const double* cov, const int32_t* cov_idx, int T, int S, const double* z, int n,
-                          int z_shared, double jitter_rel, double* out, int32_t* info, double* ws, void* stream);
+                          int z_shared, double jitter_rel, double* out, int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

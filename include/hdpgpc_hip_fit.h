@@ -1,7 +1,7 @@
 /* hdpgpc_hip_fit.h - the kernel hyper-parameter fit of libhdpgpc_hip.so: a second header of the same C-ABI, in the conventions
  * of hdpgpc_hip.h (device pointers owned by the caller, `stream` a hipStream_t as void*, nothing allocated, freed or synchronised
  * inside a call; 0 = work enqueued, -1 = bad argument, -2 = size not supported, >= 1000 = 1000 + hipError_t; fp64, row-major).
- * The entry below is additive: hdpgpc_hip.h and HGP_ABI_VERSION are unchanged by it.
+ * The entries below belong to the same library and version as hdpgpc_hip.h: HGP_ABI_VERSION there covers them.
  */
 #ifndef HDPGPC_HIP_FIT_H
 #define HDPGPC_HIP_FIT_H
@@ -40,7 +40,8 @@ extern "C" {
  * the noise; loss_out (may be NULL) [B, loss_ld]: iteration `it` writes column it - 1 if it <= loss_ld.
  * T <= HGP_MAX_T_COOP of hdpgpc_hip.h (-2 above); T < 1, B < 1, n_steps < 0, x_stride < 0 or a NULL x, Y, bounds, state, status
  * or ws is -1, before any HIP call.
- * ws: caller-provided workspace of HGP_FIT_WS_DOUBLES(B, T) doubles (K then K^-1, the inverse factor, the factor's status).
+ * ws: caller-provided workspace of at least hgp_kernel_fit_ws_bytes(B, T) bytes (K then K^-1, the inverse factor, the factor's
+ * status; 0 for B < 1 or T < 1); ws_bytes: what the caller provides - less than that is -1, before any HIP call.
  *
  * Every Adam step is a fixed sequence of launches for all B fits (Gram, the batched Cholesky family of hdpgpc_hip.h, one
  * product, one update: four launches for T <= HGP_MAX_T_WAVE, five above); nothing returns to the host between them, no launch
@@ -48,10 +49,10 @@ extern "C" {
  * own x, y and bounds only and every sum runs in an order fixed by T: the same bits for any B, any position in the batch and
  * any split of the iterations over calls. */
 #define HGP_FIT_STATE_DOUBLES 32
-#define HGP_FIT_WS_DOUBLES(B, T) ((size_t)2 * (size_t)(B) * (T) * (T) + (size_t)(B))
+size_t hgp_kernel_fit_ws_bytes(int B, int T);
 int hgp_kernel_fit_steps_f64(const double* x, long x_stride, const double* Y, int T, int B, const double* bounds, double lr,
                              int n_steps, int min_iter, int max_iter, double* state, int32_t* status, double* loss_out,
-                             int loss_ld, double* ws, void* stream);
+                             int loss_ld, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

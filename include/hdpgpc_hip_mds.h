@@ -1,7 +1,7 @@
 /* hdpgpc_hip_mds.h - the MDS embedding of a distance matrix (metric SMACOF) of libhdpgpc_hip.so: a further header of the same
  * C-ABI, in the conventions of hdpgpc_hip.h (device pointers owned by the caller, `stream` a hipStream_t as void*, nothing
  * allocated, freed or synchronised inside a call; 0 = work enqueued, -1 = bad argument, >= 1000 = 1000 + hipError_t; fp64,
- * row-major).  The entry below is additive: hdpgpc_hip.h and HGP_ABI_VERSION are unchanged by it.
+ * row-major).  The entries below belong to the same library and version as hdpgpc_hip.h: HGP_ABI_VERSION there covers them.
  */
 #ifndef HDPGPC_HIP_MDS_H
 #define HDPGPC_HIP_MDS_H
@@ -39,8 +39,9 @@ extern "C" {
  *   written.  A start whose status is not 0 is frozen: no call touches its X, state, status, stress or n_iter again.
  * An all-zero state and status is the beginning: there is no init entry.
  * n < 1, p outside 1..3, B < 1, n_steps < 0, ld < n or a NULL delta, X, state, status, stress, n_iter or ws is -1, before any
- * HIP call.  ws: caller-provided workspace of HGP_MDS_WS_DOUBLES(B, n, p) doubles (X_{k+1} of every start, then the two partial
- * sums of every row of every start).
+ * HIP call.  ws: caller-provided workspace of at least hgp_smacof_ws_bytes(B, n, p) bytes (X_{k+1} of every start, then the two
+ * partial sums of every row of every start; 0 for B, n or p < 1); ws_bytes: what the caller provides - less than that is -1,
+ * before any HIP call.
  *
  * Every pass is two launches whatever B is (the sweep over delta for all starts; the reduction, stop rule and hand-over of
  * every start); nothing returns to the host between them, no launch waits on another workgroup, and a call enqueues n_steps
@@ -48,10 +49,10 @@ extern "C" {
  * runs in an order fixed by n and p: the same bits for any B, any position in the batch and any split of the passes over
  * calls. */
 #define HGP_MDS_STATE_DOUBLES 8
-#define HGP_MDS_WS_DOUBLES(B, n, p) ((size_t)(B) * (size_t)(n) * (size_t)((p) + 2))
+size_t hgp_smacof_ws_bytes(int B, int n, int p);
 int hgp_smacof_steps_f64(const double* delta, int ld, int n, int p, int B, double* X /* [B,n,p] in/out */, double eps, int n_steps,
                          int max_iter, double* state /* [B, HGP_MDS_STATE_DOUBLES] */, int32_t* status /* [B] */,
-                         double* stress /* [B] */, int32_t* n_iter /* [B] */, double* ws /* HGP_MDS_WS_DOUBLES(B, n, p) */,
+                         double* stress /* [B] */, int32_t* n_iter /* [B] */, void* ws, size_t ws_bytes /* hgp_smacof_ws_bytes(B, n, p) */,
                          void* stream);
 
 #ifdef __cplusplus

@@ -1,7 +1,7 @@
 /* hdpgpc_hip_project.h - projection of segments of different lengths onto the basis grid: a further header of libhdpgpc_hip.so's
  * C-ABI, in the conventions of hdpgpc_hip.h (device pointers owned by the caller, `stream` a hipStream_t as void*, nothing
  * allocated, freed or synchronised inside a call; 0 = work enqueued, -1 = bad argument, -2 = size not supported, >= 1000 =
- * 1000 + hipError_t; fp64, row-major).  The entries below are additive: hdpgpc_hip.h and HGP_ABI_VERSION are unchanged by them.
+ * 1000 + hipError_t; fp64, row-major).  The entries below belong to the same library and version as hdpgpc_hip.h: its HGP_ABI_VERSION covers them.
  */
 #ifndef HDPGPC_HIP_PROJECT_H
 #define HDPGPC_HIP_PROJECT_H

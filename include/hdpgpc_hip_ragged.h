@@ -1,8 +1,8 @@
 /* hdpgpc_hip_ragged.h - the per-(segment, cluster) path of libhdpgpc_hip.so for segments of different lengths: a further header
  * of the same C-ABI, in the conventions of hdpgpc_hip.h (device pointers owned by the caller, `stream` a hipStream_t as void*,
  * nothing allocated, freed or synchronised inside a call; 0 = work enqueued, -1 = bad argument, -2 = size not supported,
- * >= 1000 = 1000 + hipError_t; fp64, row-major).  The entry below is additive: hdpgpc_hip.h and HGP_ABI_VERSION are unchanged
- * by it.  Usable alone or next to hdpgpc_hip.h, whose plan it takes (the typedef below repeats that header's: C11 / C++).
+ * >= 1000 = 1000 + hipError_t; fp64, row-major).  The entry below belongs to the same library and version as hdpgpc_hip.h: its
+ * HGP_ABI_VERSION covers it.  Usable alone or next to hdpgpc_hip.h, whose plan it takes (the typedef below repeats that header's: C11 / C++).
  */
 #ifndef HDPGPC_HIP_RAGGED_H
 #define HDPGPC_HIP_RAGGED_H

@@ -39,7 +39,7 @@ def test_library_exports_every_declared_symbol():
 @pytest.mark.skipif(not os.path.exists(LIB), reason="library not built (run __graft_entry__.build())")
 def test_ctypes_binding_loads_without_a_gpu():
     from hdpgpc_amd import _ffi
-    assert _ffi.lib.hgp_abi_version() == 6
+    assert _ffi.lib.hgp_abi_version() == 7
     assert set(_ffi.EXPORTS) == set(header_symbols())
     # argument validation happens before any HIP call
     assert _ffi.lib.hgp_gram_rbf_f64(None, 4, None, 4, 1.0, 1.0, 0.0, None, None) == -1
@@ -111,8 +111,10 @@ PINNED = {
     "hgp_trsv_lower_solve_f64": (i32, [vp, i32, vp, i32, vp, vp, vp]),
     "hgp_lml_grad_f64": (i32, [vp, vp, vp, i32, f64, f64, f64, vp, vp]),
     "hgp_kl_sym_f64": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp]),
-    "hgp_pred_bands_f64": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
-    "hgp_sample_states_f64": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, f64, vp, vp, vp, vp]),
+    "hgp_pred_bands_ws_bytes": (sz, [i32, i32]),
+    "hgp_pred_bands_f64": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "hgp_sample_states_ws_bytes": (sz, [i32, i32]),
+    "hgp_sample_states_f64": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, f64, vp, vp, vp, sz, vp]),
 }
 
 
@@ -126,26 +128,27 @@ def test_parser_reproduces_the_pinned_binding():
     assert sorted(funcs) == sorted(PINNED) == header_symbols()
     for name, sig in PINNED.items():
         assert funcs[name] == sig, name
-    assert defines == {"HGP_ABI_VERSION": 6, "HGP_MAX_T_WAVE": 128, "HGP_MAX_T_COOP": 256}
+    assert defines == {"HGP_ABI_VERSION": 7, "HGP_MAX_T_WAVE": 128, "HGP_MAX_T_COOP": 256}
 
 
 STRUCTS = {"hgp_gemm_item": ("GemmItem", 104), "hgp_chain_gather_desc": ("ChainGatherDesc", 128),
            "hgp_chain_finish_desc": ("ChainFinishDesc", 192), "hgp_copy_item": ("CopyItem", 24)}
-WS_SHAPES = [(1, 1), (7, 128), (7, 129), (3, 256)]      # both sides of the wave / cooperative switch
+# hgp_pred_bands_ws_bytes(S, T) and hgp_sample_states_ws_bytes(S, T) as the header's two workspace macros gave
+# them (doubles, times 8) before the library reported its workspaces itself: a caller that sized its buffer by
+# the macro stays correct.  Both sides of the wave / cooperative switch.
+BANDS_WS_BYTES = {(1, 1): 56, (7, 128): 1835288, (7, 129): 2795968, (3, 256): 4718712}
+SAMPLE_WS_BYTES = {(1, 1): 16, (7, 128): 917560, (7, 129): 931952, (3, 256): 1572888}
 
 
 @pytest.fixture(scope="module")
 def c_probe(tmp_path_factory):
-    """{key: value} as the C compiler sees the header: sizeof of every struct, offsetof of every field, the workspace macros."""
+    """{key: value} as the C compiler sees the header: sizeof of every struct, offsetof of every field."""
     _, structs, _ = parsed()
     assert sorted(structs) == sorted(STRUCTS)
     probes = []
     for s, fields in structs.items():
         probes.append((f"sizeof {s}", f"sizeof({s})"))
         probes += [(f"{s}.{name}", f"offsetof({s}, {name})") for name, _ in fields]
-    for S, T in WS_SHAPES:
-        probes.append((f"bands {S} {T}", f"HGP_BANDS_WS_DOUBLES({S}, {T})"))
-        probes.append((f"sample {S} {T}", f"HGP_SAMPLE_WS_DOUBLES({S}, {T})"))
     d = tmp_path_factory.mktemp("c_probe")
     body = "\n".join(f'  printf("{k}=%zu\\n", (size_t)({expr}));' for k, expr in probes)
     (d / "probe.c").write_text(f'#include <stdio.h>\n#include "hdpgpc_hip.h"\nint main(void) {{\n{body}\n  return 0;\n}}\n')
@@ -170,11 +173,13 @@ def test_struct_layouts_match_the_c_compiler(c_probe):
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="library not built (run __graft_entry__.build())")
-def test_workspace_sizes_match_the_header_macros(c_probe):
-    from hdpgpc_amd import ops
-    for S, T in WS_SHAPES:
-        assert ops.pred_bands_ws_doubles(S, T) == c_probe[f"bands {S} {T}"], (S, T)
-        assert ops.sample_ws_doubles(S, T) == c_probe[f"sample {S} {T}"], (S, T)
+def test_workspace_bytes_are_pinned():
+    from hdpgpc_amd import _ffi, ops
+    for pinned, size_fn, doubles in ((BANDS_WS_BYTES, _ffi.lib.hgp_pred_bands_ws_bytes, ops.pred_bands_ws_doubles),
+                                     (SAMPLE_WS_BYTES, _ffi.lib.hgp_sample_states_ws_bytes, ops.sample_ws_doubles)):
+        assert {shape: size_fn(*shape) for shape in pinned} == pinned
+        assert {shape: 8 * doubles(*shape) for shape in pinned} == pinned
+        assert size_fn(0, 16) == size_fn(2, 0) == size_fn(-1, 16) == 0
 
 
 @pytest.mark.parametrize("decl, names", [
@@ -199,7 +204,7 @@ def test_parser_raises_on_what_it_cannot_map(decl, names):
 @pytest.mark.skipif(not os.path.exists(LIB), reason="library not built (run __graft_entry__.build())")
 def test_abi_guard_refuses_a_library_of_another_header():
     from hdpgpc_amd import _ffi
-    _ffi.check_abi(6, 6)
+    _ffi.check_abi(7, 7)
     with pytest.raises(ImportError, match="library built from another header: rebuild"):
-        _ffi.check_abi(6, 7)
-    assert _ffi.ABI_VERSION == 6 and (_ffi.MAX_T_WAVE, _ffi.MAX_T_COOP) == (128, 256)
+        _ffi.check_abi(7, 8)
+    assert _ffi.ABI_VERSION == 7 and (_ffi.MAX_T_WAVE, _ffi.MAX_T_COOP) == (128, 256)

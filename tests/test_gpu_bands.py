@@ -317,3 +317,28 @@ def test_driver_surface(capsys):
         assert np.array_equal(ev["mean"][j], mj[0].cpu().numpy()) and np.array_equal(ev["var"][j], vj[0].cpu().numpy())
     part = up.plot_partial_models(sw, [0], None, None, 0, time_instant=[1, n - 1])
     assert np.array_equal(part[0]["mean"], ev["mean"][[1, n - 1]])
+
+
+# ------------------------------------------------------------------------------------------ the caller's workspace
+@pytest.mark.parametrize("T", [16, 128, 129])
+def test_direct_call_stays_inside_the_reported_workspace(T):
+    """hgp_pred_bands_f64 on exactly hgp_pred_bands_ws_bytes(S, T) bytes between two guard pads, both layouts (the factor's
+    scratch exists for T > 128 only): the pads keep their bits and the outputs are the wrapper's, bit for bit."""
+    import ws_guard
+    from hdpgpc_amd import _ffi
+    S, Q = 2, 3
+    case = synthetic(np.random.default_rng(500 + T), T, S, Q)
+    want = case.run()
+    xb, theta, mean, Sig, idx, xq = case._d
+    need = _ffi.lib.hgp_pred_bands_ws_bytes(S, T)
+    buf, ws = ws_guard.guarded(need, DEV)
+    mean_q, var_q = torch.empty_like(want[0]), torch.empty_like(want[1])
+    info = torch.zeros(S, dtype=torch.int32, device=DEV)
+    P = ops._ptr
+    assert _ffi.lib.hgp_pred_bands_f64(P(xb), T, P(theta), P(mean), P(Sig), P(idx), S, P(xq), Q, P(mean_q), P(var_q), P(info), ws, need,
+                                       ops._stream()) == 0
+    torch.cuda.synchronize()
+    ws_guard.assert_pads_untouched(buf)
+    assert not info.cpu().numpy().any()
+    for got, ref in zip((mean_q, var_q, info), want):
+        ws_guard.assert_same_bits(got, ref)

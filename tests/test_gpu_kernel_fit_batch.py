@@ -199,3 +199,30 @@ def test_gpi_hdp_fit_kernels():
     assert np.array_equal(th[:, 0], want[:, 0])
     assert np.array_equal(th[:, 2], np.clip(want[:, 2], *bounds))
     assert sw.gpmodels[0][0].gp.kernel.params() == before and sw.fixed_theta is None and not sw.gpmodels[0][0].fitted
+
+
+@pytest.mark.parametrize("T", [8, 129])
+def test_direct_call_stays_inside_the_reported_workspace(T):
+    """hgp_kernel_fit_steps_f64, one step, on exactly hgp_kernel_fit_ws_bytes(B, T) bytes between two guard pads, both inversion
+    routes: the pads keep their bits and state, status and the loss are the wrapper's, bit for bit."""
+    import ws_guard
+    from hdpgpc_amd import _ffi, ops
+    B, dev = 2, "cuda:0"
+    x = torch.arange(float(T), dtype=torch.float64, device=dev)
+    Y = torch.as_tensor(np.stack([synth(T, s)[1] for s in range(B)]), device=dev)
+    bounds = torch.as_tensor([B1, B2], dtype=torch.float64, device=dev)
+    fresh = lambda: (torch.zeros((B, _ffi.FIT_STATE_DOUBLES), dtype=torch.float64, device=dev),  # noqa: E731
+                     torch.zeros(B, dtype=torch.int32, device=dev), torch.full((B, 1), -7.0, dtype=torch.float64, device=dev))
+    want = fresh()
+    ops.kernel_fit_steps(x, Y, bounds, want[0], want[1], 1, loss_out=want[2])
+    state, status, loss = fresh()
+    need = _ffi.lib.hgp_kernel_fit_ws_bytes(B, T)
+    buf, ws = ws_guard.guarded(need, dev)
+    P = ops._ptr
+    assert _ffi.lib.hgp_kernel_fit_steps_f64(P(x), 0, P(Y), T, B, P(bounds), 0.1, 1, 1000, 4000, P(state), P(status), P(loss), 1, ws, need,
+                                             ops._stream()) == 0
+    torch.cuda.synchronize()
+    ws_guard.assert_pads_untouched(buf)
+    assert status.tolist() == [0, 0] and bool(torch.isfinite(loss).all())
+    for got, ref in zip((state, status, loss), want):
+        ws_guard.assert_same_bits(got, ref)

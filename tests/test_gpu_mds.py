@@ -297,3 +297,27 @@ def test_mds_embedding_on_the_golden_model(capsys):
     for fn in (up.plot_MDS, up.plot_MDS_plotly):
         assert np.array_equal(fn(sw, None, None, 0), KL)
     assert "figures are not part of" in capsys.readouterr().out
+
+
+@pytest.mark.parametrize("p", [1, 2, 3])
+def test_direct_call_stays_inside_the_reported_workspace(p):
+    """hgp_smacof_steps_f64 on exactly hgp_smacof_ws_bytes(B, n, p) bytes between two guard pads: the pads keep their bits and
+    X, state, status, stress and n_iter are the wrapper's, bit for bit."""
+    import ws_guard
+    from hdpgpc_amd import _ffi, ops
+    B, n, n_steps, eps, max_iter = 2, 5, 4, 1e-6, 300
+    _, D = mds_ref.drifting_groups(n, seed=3)
+    X0, Dd = starts(n, p, B, seed=p), dev(D)
+    want = run(Dd, X0, n_steps, eps, max_iter)
+    X, state = dev(X0), torch.zeros((B, _ffi.MDS_STATE_DOUBLES), dtype=torch.float64, device=DEV)
+    status, n_iter = torch.zeros(B, dtype=torch.int32, device=DEV), torch.full((B,), -7, dtype=torch.int32, device=DEV)
+    stress = torch.full((B,), -7.0, dtype=torch.float64, device=DEV)
+    need = _ffi.lib.hgp_smacof_ws_bytes(B, n, p)
+    buf, ws = ws_guard.guarded(need, DEV)
+    P = ops._ptr
+    assert _ffi.lib.hgp_smacof_steps_f64(P(Dd), n, n, p, B, P(X), eps, n_steps, max_iter, P(state), P(status), P(stress), P(n_iter), ws,
+                                         need, ops._stream()) == 0
+    torch.cuda.synchronize()
+    ws_guard.assert_pads_untouched(buf)
+    for got, ref in zip((X, state, status, stress, n_iter), want):
+        ws_guard.assert_same_bits(got, ref)

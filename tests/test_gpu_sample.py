@@ -253,3 +253,27 @@ def test_input_is_symmetrised_and_untouched():
     ref = np.stack([mean[s] + z.cpu().numpy() @ factor(sym[idx[s]] + 1e-2 * np.mean(np.abs(np.diag(sym[idx[s]]))) * np.eye(T)).T
                     for s in range(S)])
     assert_gate(jit.cpu().numpy(), ref, "jitter_rel 1e-2")
+
+
+# ------------------------------------------------------------------------------------------ the caller's workspace
+@pytest.mark.parametrize("T", [16, 129])
+def test_direct_call_stays_inside_the_reported_workspace(T):
+    """hgp_sample_states_f64 on exactly hgp_sample_states_ws_bytes(S, T) bytes between two guard pads: the pads keep their bits
+    and the outputs are the wrapper's, bit for bit."""
+    import ws_guard
+    from hdpgpc_amd import _ffi
+    S, n = 2, 3
+    rng = np.random.default_rng(500 + T)
+    mean, cov, idx = synthetic(rng, T, S)
+    mean, cov, idx, z = dev(mean), dev(cov), dev(idx, torch.int32), dev(rng.standard_normal((n, T)))
+    want = ops.sample_states(mean, cov, z, cov_idx=idx)
+    need = _ffi.lib.hgp_sample_states_ws_bytes(S, T)
+    buf, ws = ws_guard.guarded(need, DEV)
+    out, info = torch.empty_like(want[0]), torch.zeros(S, dtype=torch.int32, device=DEV)
+    P = ops._ptr
+    assert _ffi.lib.hgp_sample_states_f64(P(mean), P(cov), P(idx), T, S, P(z), n, 1, 0.0, P(out), P(info), ws, need, ops._stream()) == 0
+    torch.cuda.synchronize()
+    ws_guard.assert_pads_untouched(buf)
+    assert not info.cpu().numpy().any()
+    for got, ref in zip((out, info), want):
+        ws_guard.assert_same_bits(got, ref)

@@ -22,8 +22,12 @@ MDS_HEADER = os.path.join(ROOT, "include", "hdpgpc_hip_mds.h")
 needs_lib = pytest.mark.skipif(not os.path.exists(LIB), reason="library not built (run __graft_entry__.build())")
 GATE = 1e-9
 
-i32, f64, vp = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
-PINNED = {"hgp_smacof_steps_f64": (i32, [vp, i32, i32, i32, i32, vp, f64, i32, i32, vp, vp, vp, vp, vp, vp])}
+i32, f64, vp, sz = ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t
+PINNED = {"hgp_smacof_ws_bytes": (sz, [i32, i32, i32]),
+          "hgp_smacof_steps_f64": (i32, [vp, i32, i32, i32, i32, vp, f64, i32, i32, vp, vp, vp, vp, vp, sz, vp])}
+# hgp_smacof_ws_bytes(B, n, p) as the header's workspace macro gave it (doubles, times 8) before the library reported its
+# workspace itself: a caller that sized its buffer by the macro stays correct
+WS_BYTES = {(4, 97, 3): 15520, (1, 1, 1): 24}
 
 
 def inputs(n, kind):
@@ -87,13 +91,23 @@ def test_mds_header_parses_to_the_pinned_binding():
 @needs_lib
 def test_mds_table_is_separate_from_the_main_headers():
     from hdpgpc_amd import _cheader, _ffi, ops
-    assert _ffi.MDS_EXPORTS == ["hgp_smacof_steps_f64"] and _ffi.MDS_STATE_DOUBLES == 8
-    assert "hgp_smacof_steps_f64" not in _ffi.EXPORTS and "hgp_smacof_steps_f64" not in _ffi.FIT_EXPORTS
+    assert _ffi.MDS_EXPORTS == sorted(PINNED) and _ffi.MDS_STATE_DOUBLES == 8
+    assert not set(PINNED) & set(_ffi.EXPORTS) and not set(PINNED) & set(_ffi.FIT_EXPORTS)
     with open(os.path.join(ROOT, "include", "hdpgpc_hip.h")) as f:
         assert _ffi.EXPORTS == sorted(_cheader.parse_header(f.read())[0])
-    fn = _ffi.lib.hgp_smacof_steps_f64
-    assert (fn.restype, list(fn.argtypes)) == PINNED["hgp_smacof_steps_f64"]
+    for name, sig in PINNED.items():
+        fn = getattr(_ffi.lib, name)
+        assert (fn.restype, list(fn.argtypes)) == sig, name
     assert ops.smacof_ws_doubles(4, 97, 3) == 4 * 97 * 5
+
+
+@needs_lib
+def test_workspace_bytes_are_pinned():
+    from hdpgpc_amd import _ffi, ops
+    size_fn = _ffi.lib.hgp_smacof_ws_bytes
+    assert {shape: size_fn(*shape) for shape in WS_BYTES} == WS_BYTES
+    assert {shape: 8 * ops.smacof_ws_doubles(*shape) for shape in WS_BYTES} == WS_BYTES
+    assert size_fn(0, 5, 2) == size_fn(2, 0, 2) == size_fn(2, 5, 0) == size_fn(2, -5, 2) == 0
 
 
 @needs_lib
@@ -103,10 +117,10 @@ def test_bad_arguments_return_before_any_hip_call():
     buf = (ctypes.c_double * 64)()             # never dereferenced: every call below returns before a launch
     q = ctypes.cast(buf, vp)
 
-    def call(n=4, p=2, B=1, ld=None, n_steps=1, **ptr):
+    def call(n=4, p=2, B=1, ld=None, n_steps=1, ws_bytes=1 << 40, **ptr):
         a = {k: ptr.get(k, q) for k in ("delta", "X", "state", "status", "stress", "n_iter", "ws")}
         return fn(a["delta"], n if ld is None else ld, n, p, B, a["X"], 1e-6, n_steps, 10, a["state"], a["status"], a["stress"],
-                  a["n_iter"], a["ws"], None)
+                  a["n_iter"], a["ws"], ws_bytes, None)
 
     assert call(n=0) == -1 and call(n=-2) == -1
     assert call(p=0) == -1 and call(p=4) == -1
@@ -115,3 +129,5 @@ def test_bad_arguments_return_before_any_hip_call():
     assert call(ld=3) == -1
     for k in ("delta", "X", "state", "status", "stress", "n_iter", "ws"):
         assert call(**{k: None}) == -1, k
+    need = _ffi.lib.hgp_smacof_ws_bytes(2, 5, 2)   # one byte short, everything else valid: refused (no GPU here: before any HIP call)
+    assert need > 0 and call(n=5, p=2, B=2, ws_bytes=need - 1) == -1

@@ -51,7 +51,7 @@ def test_ragged_table_is_separate_from_the_main_headers():
     assert _ffi.RAGGED_EXPORTS == [NAME]
     assert _ffi.EXPORTS == sorted(parsed(HEADER)[0])
     assert NAME not in _ffi.EXPORTS and NAME not in _ffi.FIT_EXPORTS and NAME not in _ffi.MDS_EXPORTS
-    assert _ffi.ABI_VERSION == 6
+    assert _ffi.ABI_VERSION == 7
     fn = getattr(_ffi.lib, NAME)
     assert (fn.restype, list(fn.argtypes)) == PINNED[NAME]
 

@@ -96,7 +96,7 @@ def test_project_table_is_separate_from_the_main_headers():
         assert all(name not in t for t in (_ffi.EXPORTS, _ffi.FIT_EXPORTS, _ffi.MDS_EXPORTS, _ffi.RAGGED_EXPORTS))
         fn = getattr(_ffi.lib, name)
         assert (fn.restype, list(fn.argtypes)) == PINNED[name]
-    assert _ffi.ABI_VERSION == 6
+    assert _ffi.ABI_VERSION == 7
 
 
 def test_workspace_size():

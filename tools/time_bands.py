@@ -70,7 +70,7 @@ def one(S, T, Q, reps):
     P = ops._ptr
 
     def entry(q):
-        _ffi.check(_ffi.lib.hgp_pred_bands_f64(P(xb), T, P(theta), P(mean), P(Sig), None, S, P(xq), q, P(mq), P(vq), P(info), P(ws),
+        _ffi.check(_ffi.lib.hgp_pred_bands_f64(P(xb), T, P(theta), P(mean), P(Sig), None, S, P(xq), q, P(mq), P(vq), P(info), P(ws), ws.numel() * 8,
                                                ops._stream()), "pred_bands")
 
     n_loop = min(S, LOOP_MAX)

@@ -74,7 +74,7 @@ def one(n, reps, sk_max_n, sk_iters):
         state.zero_()
         status.zero_()
         _ffi.check(_ffi.lib.hgp_smacof_steps_f64(Pt(Dd), n, n, P, B, Pt(X), 0.0, ITERS, ITERS + 1, Pt(state), Pt(status), Pt(stress),
-                                                 Pt(n_it), Pt(ws), ops._stream()), "smacof_steps")
+                                                 Pt(n_it), Pt(ws), ws.numel() * 8, ops._stream()), "smacof_steps")
 
     rec = {"n": n, "B": B, "p": P, "passes": ITERS, "launches_per_iteration": LAUNCHES_PER_ITERATION, "delta_MB": n * n * 8 / 1e6}
     rec["entry_ms"], rec["entry_all_ms"] = event_ms(entry, reps)

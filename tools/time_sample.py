@@ -67,7 +67,7 @@ def one(S, T, n, reps, inner):
     P = ops._ptr
 
     def fused():
-        _ffi.check(_ffi.lib.hgp_sample_states_f64(P(mean), P(cov), None, T, S, P(z), n, 1, 0.0, P(out), P(info), P(ws), ops._stream()),
+        _ffi.check(_ffi.lib.hgp_sample_states_f64(P(mean), P(cov), None, T, S, P(z), n, 1, 0.0, P(out), P(info), P(ws), ws.numel() * 8, ops._stream()),
                    "sample_states")
 
     def composed():
