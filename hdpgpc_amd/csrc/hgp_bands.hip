@@ -7,7 +7,7 @@
 //
 // without the [Q,Q] covariance or any [T,Q] intermediate ever reaching HBM.  Three launches whatever S and Q are:
 //   1. k_bands_prep   one workgroup per state: jitter_s, the iso decision, K~_s into the workspace
-//   2. the batched inverse factor Z_s = chol(K~_s)^-1 of the Cholesky family (hgp_factor.hip), workspace to workspace
+//   2. the batched inverse factor Z_s = chol(K~_s)^-1 of the L^-1 family (hgp_inverse.hip), workspace to workspace
 //   3. k_bands        one workgroup per (state, share of the query panels): per panel of 64 queries
 //        E = K* (exp_neg4, registers -> LDS)        V  = Z E          W0 = Z^T V
 //        R = E - K~ W0                              V2 = Z R          W  = W0 + Z^T V2      (one refinement step: the solve

@@ -6,7 +6,7 @@
 // Here every dependency level is one launch of k_gemm_list: a device-resident list of heterogeneous items
 //     C = alpha op(A) op(B) + beta D        (any M x N x K <= 256; vectors are N = 1; D may alias nothing or be a vector)
 // with all pointers fixed for the life of the chain (the state rows of the step are gathered into one workspace first), and
-// the two Cholesky inversions of the step carry their right-hand sides along (k_wave_inv_rhs: Z = L^-1 and Y = L^-1 op(B) from
+// the two Cholesky inversions of the step carry their right-hand sides along (hgp_inverse.hip: Z = L^-1 and Y = L^-1 op(B) from
 // one factorisation), which removes a product level behind each of them.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -85,243 +85,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_gemm_list(const hgp_gemm_item* _
       if (q.C2) q.C2[(size_t)i * q.ldc + col] = v;
     }
   }
-}
-
-// -------------------------------------------------------------------------------------------- inverse with riding RHS
-struct InvRhsArgs {
-  const double* A;       // [b,T,T]
-  int T, b;
-  double jitter_rel, add;
-  double* Linv;          // [b,T,T]  Z = L^-1 (may be NULL: only the solves are wanted)
-  const double* rhs;     // [b,T,T] or NULL
-  const int32_t* rhs_on; // [b] or NULL: item m carries a right-hand side iff rhs_on[m] != 0 (NULL: all do when rhs != NULL)
-  int rhs_trans;         // solve against rhs^T
-  double* rhs_out;       // [b,T,T]  Y = L^-1 op(rhs)
-  int32_t* info;
-};
-
-template <int NB>
-__global__ __launch_bounds__(64 * WAVES) void k_wave_inv_rhs(InvRhsArgs a) {
-  __shared__ __attribute__((aligned(16))) double scr_all[WAVES * DIAG_SCR];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int g = lane >> 4, c = lane & 15;
-  const int w = blockIdx.x * WAVES + wave;
-  const int m = w / (2 * NB), Jq = w % (2 * NB);
-  const int T = a.T;
-  if (m >= a.b) return;
-  const bool is_rhs = Jq >= NB;
-  const int Jc = is_rhs ? Jq - NB : Jq;
-  if (16 * Jc >= T) return;
-  const bool skip = (is_rhs && (!a.rhs || (a.rhs_on && a.rhs_on[m] == 0))) || (!is_rhs && !a.Linv);
-  if (skip) {     // an item nobody factors (no Linv wanted, right-hand side switched off) still reports a defined status
-    if (Jq == 0 && !a.Linv && lane == 0 && a.info && (!a.rhs || (a.rhs_on && a.rhs_on[m] == 0))) a.info[m] = 0;
-    return;
-  }
-  double* scr = scr_all + wave * DIAG_SCR;
-  const double* A = a.A + (size_t)m * T * T;
-  d4 U[NB * (NB + 1) / 2];
-  d4 R[NB];
-  if constexpr (NB <= 6) load_sym_upper_burst<NB>(U, A, T, T, lane, scr);   // one exposed load latency instead of NB
-  else load_sym_upper<NB>(U, A, T, T, lane, scr);
-  {
-    double sh = a.add;
-    if (a.jitter_rel != 0.0) sh += a.jitter_rel * fmax(diag_abs_mean<NB>(U, T, lane, a.add), F64_EPS);
-    if (sh != 0.0) add_diag<NB>(U, sh, T, lane);
-  }
-  if (!is_rhs) {
-#pragma unroll
-    for (int K = 0; K < NB; ++K)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) R[K][r] = (K == Jc && g + 4 * r == c) ? 1.0 : 0.0;
-  } else {
-    const double* B = a.rhs + (size_t)m * T * T;
-#pragma unroll
-    for (int K = 0; K < NB; ++K)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = 16 * K + g + 4 * r, j = 16 * Jc + c;
-        R[K][r] = (i < T && j < T) ? (a.rhs_trans ? B[(size_t)j * T + i] : B[(size_t)i * T + j]) : 0.0;
-      }
-  }
-  PivotAcc pa;
-  pa.init();
-  wave_factor<NB, 1>(U, R, scr, nullptr, nullptr, lane, pa, nullptr, 0, T);
-  double* Z = (is_rhs ? a.rhs_out : a.Linv) + (size_t)m * T * T;
-#pragma unroll
-  for (int K = 0; K < NB; ++K)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * K + g + 4 * r, j = 16 * Jc + c;
-      if (i < T && j < T) Z[(size_t)i * T + j] = (is_rhs || K >= Jc) ? R[K][r] : 0.0;
-    }
-  if (Jq == (a.Linv ? 0 : NB) && lane == 0 && a.info) a.info[m] = pa.info;   // the first panel sees every pivot
-}
-
-template <int NB>
-void launch_inv_rhs(const InvRhsArgs& a, hipStream_t st) {
-  const int waves = a.b * 2 * NB;
-  hipLaunchKernelGGL(k_wave_inv_rhs<NB>, dim3((waves + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a);
-}
-
-// The same job for SMALL batches (the member step of a few chains: 4 or 2 matrices per chain), where the launch is one exposed
-// latency and a wave that factors the whole matrix by itself is the whole of it (31 us at T = 90: six serial diag16 plus ~280
-// dependent MFMAs on one SIMD).  Here a WORKGROUP of four waves takes each (matrix, panel): the tiles are dealt over the waves
-// (Coop<NB>), only the pivot chain stays serial.  NB is padded to a multiple of four (identity blocks); the padded steps are not
-// taken (kstop).  Arithmetic per tile is that of wave_factor (same operations in the same order): results identical bit for bit.
-template <int NB>
-__global__ __launch_bounds__(64 * WAVES) void k_coop_inv_rhs(InvRhsArgs a) {
-  using C = Coop<NB>;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const auto [rowbuf, Rbuf, Wbuf, scr, red, redi] = C::lds(smem);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c = lane & 15;
-  const int T = a.T, nblk = (T + 15) >> 4;
-  const int m = blockIdx.x, Jq = blockIdx.y;            // gridDim.y = 2 nblk: panels of L^-1, then panels of L^-1 op(B)
-  const bool is_rhs = Jq >= nblk;
-  const int Jc = is_rhs ? Jq - nblk : Jq;
-  const bool skip = (is_rhs && (!a.rhs || (a.rhs_on && a.rhs_on[m] == 0))) || (!is_rhs && !a.Linv);
-  if (skip) {
-    if (Jq == 0 && !a.Linv && threadIdx.x == 0 && a.info && (!a.rhs || (a.rhs_on && a.rhs_on[m] == 0))) a.info[m] = 0;
-    return;
-  }
-  const double* A = a.A + (size_t)m * T * T;
-  d4 U[C::NT];
-  coop_load_sym_upper<NB>(U, A, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
-  __syncthreads();   // rowbuf served as per-wave staging for the loader
-  coop_regularise<NB>(U, a.add, a.jitter_rel, T, wave, lane, red);
-  const double* B = is_rhs ? a.rhs + (size_t)m * T * T : nullptr;
-  for (int K = wave; K < NB; K += WAVES) {
-    d4 v;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * K + g + 4 * r, j = 16 * Jc + c;
-      if (!is_rhs) v[r] = (K == Jc && g + 4 * r == c) ? 1.0 : 0.0;
-      else v[r] = (i < T && j < T) ? (a.rhs_trans ? B[(size_t)j * T + i] : B[(size_t)i * T + j]) : 0.0;
-    }
-    lds_tile_store(Rbuf, K, lane, v);
-  }
-  __syncthreads();
-  PivotAcc pa;
-  pa.init();
-  coop_factor<NB, true>(U, rowbuf, Rbuf, Wbuf, scr, wave, lane, pa, nullptr, 0, T, nullptr, nullptr, 0, nullptr, nullptr, nblk);
-  double* Z = (is_rhs ? a.rhs_out : a.Linv) + (size_t)m * T * T;
-  for (int K = wave; K < nblk; K += WAVES) {
-    const d4 z = lds_tile_load(Rbuf, K, lane);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * K + g + 4 * r, j = 16 * Jc + c;
-      if (i < T && j < T) Z[(size_t)i * T + j] = (is_rhs || K >= Jc) ? z[r] : 0.0;
-    }
-  }
-  if (Jq == (a.Linv ? 0 : nblk) && a.info) {   // the first panel sees every pivot
-    int info;
-    (void)coop_logdet_info(pa, wave, lane, red, redi, info);
-    if (threadIdx.x == 0) a.info[m] = info;
-  }
-}
-
-// ... and with the DATAFLOW factorisation (cooph_factor_df<NB, 1>, NB / 2 waves per workgroup, NB = the even number of 16-blocks:
-// no padding at T = 90): no workgroup barrier inside the factorisation - the wave that owns block K + 1 solves only that panel tile,
-// updates its diagonal tile from the accumulator, factors it and publishes W_{K+1} and Z_{K+1} while the others are still in the
-// trailing update of step K.  The barrier version above spends 4.5 us per block step for 1.2 us of diag16_acc.
-// Its dynamic LDS: the factorisation's buffers (three row buffers, W and Z of every block, per-wave scratch), red[8], then the
-// factorisation's flag block with the waves' status words behind it.
-template <int NB>
-struct CoophInvLds {
-  using C = CoopH<NB>;
-  using Df = typename C::template DfLds<1>;
-  static constexpr int DF = 0, RED = DF + Df::DOUBLES, FLAGS = RED + 8;   // doubles
-  static constexpr size_t BYTES = sizeof(double) * FLAGS + sizeof(int) * C::DF_INTS;
-  static_assert(RED % 2 == 0 && BYTES <= LDS_MAX_BYTES, "k_cooph_inv_rhs: LDS");
-  HGP_LDS_DOUBLES(df, DF)     // base of the Df members
-  HGP_LDS_DOUBLES(red, RED)   // [8]
-  HGP_LDS_INTS(flags, FLAGS, 0)
-  HGP_LDS_INTS(redi, FLAGS, C::DF_REDI)
-};
-
-template <int NB>
-__global__ __launch_bounds__(64 * CoopH<NB>::NW) void k_cooph_inv_rhs(InvRhsArgs a) {
-  using C = CoopH<NB>;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  using L = CoophInvLds<NB>;
-  using Df = typename L::Df;
-  double *df = L::df(smem), *red = L::red(smem);
-  int *flags = L::flags(smem), *redi = L::redi(smem);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c = lane & 15;
-  const int T = a.T, nblk = (T + 15) >> 4;
-  const int m = blockIdx.x, Jq = blockIdx.y;            // gridDim.y = 2 nblk: panels of L^-1, then panels of L^-1 op(B)
-  const bool is_rhs = Jq >= nblk;
-  const int Jc = is_rhs ? Jq - nblk : Jq;
-  const bool skip = (is_rhs && (!a.rhs || (a.rhs_on && a.rhs_on[m] == 0))) || (!is_rhs && !a.Linv);
-  if (skip) {
-    if (Jq == 0 && !a.Linv && threadIdx.x == 0 && a.info && (!a.rhs || (a.rhs_on && a.rhs_on[m] == 0))) a.info[m] = 0;
-    return;
-  }
-  double* scr = Df::scr(df) + wave * DIAG_SCR;
-  const double* A = a.A + (size_t)m * T * T;
-  d4 U[C::NT];
-#pragma unroll
-  for (int i_ = 0; i_ < C::NT; ++i_) U[i_] = (d4){0.0, 0.0, 0.0, 0.0};
-  cooph_load_sym_upper<NB>(U, A, T, T, wave, lane, scr);
-  cooph_regularise<NB>(U, a.add, a.jitter_rel, T, wave, lane, red);
-  // my two tiles of the right-hand side panel: block rows JA = wave and JB = NB - 1 - wave
-  const double* B = is_rhs ? a.rhs + (size_t)m * T * T : nullptr;
-  d4 RA, RB;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int K = h == 0 ? wave : NB - 1 - wave;
-    d4 v;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * K + g + 4 * r, j = 16 * Jc + c;
-      if (!is_rhs) v[r] = (K == Jc && g + 4 * r == c) ? 1.0 : 0.0;
-      else v[r] = (i < T && j < T) ? (a.rhs_trans ? B[(size_t)j * T + i] : B[(size_t)i * T + j]) : 0.0;
-    }
-    if (h == 0) RA = v;
-    else RB = v;
-  }
-  PivotAcc pa;
-  pa.init();
-  cooph_factor_df<NB, 1>(U, Df::row0(df), Df::row1(df), Df::row2(df), Df::Wall(df), scr, flags, wave, lane, pa, T, nullptr, &RA, &RB,
-                         Df::zbuf(df));
-  double* Z = (is_rhs ? a.rhs_out : a.Linv) + (size_t)m * T * T;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int K = h == 0 ? wave : NB - 1 - wave;
-    const d4 z = h == 0 ? RA : RB;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * K + g + 4 * r, j = 16 * Jc + c;
-      if (i < T && j < T) Z[(size_t)i * T + j] = (is_rhs || K >= Jc) ? z[r] : 0.0;
-    }
-  }
-  if (Jq == (a.Linv ? 0 : nblk) && a.info) {   // the first panel sees every pivot: the earliest bad one over the waves
-    if (lane == 0) redi[wave] = pa.info;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int inf = 0;
-      for (int w = 0; w < C::NW; ++w)
-        if (redi[w] != 0 && (inf == 0 || redi[w] < inf)) inf = redi[w];
-      a.info[m] = inf;
-    }
-  }
-}
-
-template <int NB>
-int launch_cooph_inv_rhs(const InvRhsArgs& a, hipStream_t st) {
-  const size_t lds = CoophInvLds<NB>::BYTES;
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_cooph_inv_rhs<NB>), lds)) return rc_;
-  hipLaunchKernelGGL(k_cooph_inv_rhs<NB>, dim3(a.b, 2 * ((a.T + 15) >> 4)), dim3(64 * CoopH<NB>::NW), lds, st, a);
-  return launch_status();
-}
-
-template <int NB>
-int launch_coop_inv_rhs(const InvRhsArgs& a, hipStream_t st) {
-  const size_t lds = sizeof(double) * Coop<NB>::LDS_DOUBLES;
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_inv_rhs<NB>), lds)) return rc_;
-  hipLaunchKernelGGL(k_coop_inv_rhs<NB>, dim3(a.b, 2 * ((a.T + 15) >> 4)), dim3(64 * WAVES), lds, st, a);
-  return launch_status();
 }
 
 // -------------------------------------------------------------------------------------------- fused glue of the step
@@ -693,28 +456,6 @@ int hgp_gemm_list_mapped_f64(const hgp_gemm_item* items_dev, int n_items, const 
   if (!items_dev || !tile_map_dev || n_items < 0 || n_items > 65535 || total_tiles <= 0) return -1;
   hipLaunchKernelGGL(k_gemm_list, dim3((total_tiles + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, (hipStream_t)stream, items_dev, n_items,
                      tile_map_dev, total_tiles);
-  return launch_status();
-}
-
-int hgp_chol_inverse_rhs_batched_f64(const double* A, int T, int b, double jitter_rel, double add_diag, double* Linv, const double* rhs,
-                                     const int32_t* rhs_on, int rhs_trans, double* rhs_out, int32_t* info, void* stream) {
-  if (b == 0) return 0;
-  if (!A || T <= 0 || b < 0 || (!Linv && !rhs) || (rhs && !rhs_out)) return -1;
-  if (T > HGP_MAX_T_WAVE) return -2;
-  InvRhsArgs a{A, T, b, jitter_rel, add_diag, Linv, rhs, rhs_on, rhs_trans, rhs_out, info};
-  hipStream_t st = (hipStream_t)stream;
-  // few matrices (the member step of a few chains): one workgroup per (matrix, panel) - latency; many: one wave each - throughput
-  // (tools/time_inv_rhs.py; while the workgroups fit the chip in one round - beyond that the one-wave kernel wins)
-  constexpr int coop_max_wg = 256;
-  // T > 64: the dataflow form (T = 90: 21.7 us, barrier form 27.1, one wave per panel 30.3; T = 128: 28.0 / 30.6 / 51.5; two
-  // workgroups per CU at NB = 6); 32 < T <= 64: the barrier form (T = 50: 13.1 us against 14.7 / 16.5); T <= 32 is one wave anyway
-  const long wgs = (long)b * 2 * ((T + 15) >> 4);
-  if (T > 64 && wgs <= (nb_for(T) == 6 ? 2 : 1) * (long)coop_max_wg) {
-    return nb_for(T) == 6 ? launch_cooph_inv_rhs<6>(a, st) : launch_cooph_inv_rhs<8>(a, st);   // own choice: T > 64 only has {6, 8}
-  } else if (T > 32 && T <= 64 && wgs <= coop_max_wg) {
-    return launch_coop_inv_rhs<4>(a, st);
-  }
-  dispatch_nb_wave(T, [&](auto nb) { launch_inv_rhs<decltype(nb)::value>(a, st); });
   return launch_status();
 }
 

@@ -1,4 +1,4 @@
-// The Cholesky family (a3 / a4 / a6): factor, inverse factor and scoring of batched SPD matrices.
+// The Cholesky family (a3 / a4 / a6): factor and scoring of batched SPD matrices (the inverse factor: hgp_inverse.hip).
 // One wavefront owns one SPD matrix (<= 128 x 128) in MFMA accumulator registers, one workgroup a larger one (<= 256); see tile_f64.hpp.
 #include <mutex>
 
@@ -47,53 +47,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_wave_potrf(PotrfArgs a) {
     if (a.info) a.info[m] = pa.info;
     if (a.logdet) a.logdet[m] = pa.logdet();
   }
-}
-
-// L^{-1} of the regularised matrix, one wave per (matrix, block column): the identity block column Jc rides along
-// the factorisation as its 16 right-hand sides.  Reads A (never writes it), so it runs BEFORE an in-place k_wave_potrf.
-template <int NB>
-__global__ __launch_bounds__(64 * WAVES) void k_wave_inv(PotrfArgs a) {
-  __shared__ __attribute__((aligned(16))) double scr_all[WAVES * DIAG_SCR];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int g = lane >> 4, c = lane & 15;
-  const int w = blockIdx.x * WAVES + wave;
-  const int m = w / NB, Jc = w % NB;
-  const int T = a.T;
-  if (m >= a.b || 16 * Jc >= T) return;
-  double* scr = scr_all + wave * DIAG_SCR;
-  const double* A = a.A + (size_t)m * T * T;
-  d4 U[NB * (NB + 1) / 2];
-  d4 R[NB];
-  if (a.symmetric) load_upper_only<NB>(U, A, T, T, lane);
-  else if constexpr (NB <= 6) load_sym_upper_burst<NB>(U, A, T, T, lane, scr);   // latency-bound: all loads in flight at once
-  else load_sym_upper<NB>(U, A, T, T, lane, scr);
-  {
-    double sh = a.add;
-    if (a.jitter_rel != 0.0) sh += a.jitter_rel * fmax(diag_abs_mean<NB>(U, T, lane, a.add), F64_EPS);
-    if (sh != 0.0) add_diag<NB>(U, sh, T, lane);
-  }
-#pragma unroll
-  for (int K = 0; K < NB; ++K)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) R[K][r] = (K == Jc && g + 4 * r == c) ? 1.0 : 0.0;
-  PivotAcc pa;
-  pa.init();
-  wave_factor<NB, 1>(U, R, scr, nullptr, nullptr, lane, pa, nullptr, 0, T);
-  double* Z = a.Linv + (size_t)m * T * T;
-#pragma unroll
-  for (int K = 0; K < NB; ++K)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * K + g + 4 * r, j = 16 * Jc + c;
-      if (i < T && j < T) Z[(size_t)i * T + j] = (K >= Jc) ? R[K][r] : 0.0;
-    }
-  if (a.inv_info && Jc == 0 && lane == 0 && a.info) a.info[m] = pa.info;   // block column 0 sees every pivot
-}
-
-template <int NB>
-void launch_wave_inv(const PotrfArgs& a, hipStream_t st) {
-  const int waves = a.b * NB;
-  hipLaunchKernelGGL(k_wave_inv<NB>, dim3((waves + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a);
 }
 
 // -------------------------------------------------------------------------------------- a4 + a6
@@ -327,125 +280,6 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_potrf(PotrfArgs a) {
   }
 }
 
-// Z = L^-1 from L and the inverses of its diagonal blocks (already sitting in Z's diagonal blocks): block column Kc of Z by ONE
-// wave - forward substitution by blocks,  Z_IK = -W_I sum_{K <= j < I} L_Ij Z_jK  (I = K + 1 .. NB - 1), the column's tiles in
-// registers (accumulator layout = the B operand of the next product), L and W read from memory in A-operand order.  The block
-// columns are independent: 16 waves per 256 x 256 matrix, each one pass over its part of L - instead of one more cooperative
-// factorisation per block column (k_coop_inv: NB redundant factorisations per matrix, 3.4 ms for 256 matrices of 256).
-template <int NB>
-__global__ __launch_bounds__(64 * WAVES) void k_trtri(const double* __restrict__ Lall, double* __restrict__ Zall, int T, int b,
-                                                      const int32_t* __restrict__ info) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int g = lane >> 4, c = lane & 15;
-  const int w = blockIdx.x * WAVES + wave;
-  const int m = w / NB, Kc = w % NB;
-  if (m >= b || 16 * Kc >= T) return;
-  const double* L = Lall + (size_t)m * T * T;
-  double* Z = Zall + (size_t)m * T * T;
-  const int nb = (T + 15) >> 4;
-  d4 Zc[NB];                                       // Z_IK, I = Kc .. nb - 1 (statically indexed: slot I)
-#pragma unroll
-  for (int I = 0; I < NB; ++I) {
-    if (I == Kc) {                                 // diagonal block: W_K, read back in accumulator layout v[r] = X[g + 4 r][c]
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * I + g + 4 * r, col = 16 * I + c;
-        Zc[I][r] = (row < T && col < T) ? Z[(size_t)row * T + col] : ((row == col) ? 1.0 : 0.0);
-      }
-    } else {
-      Zc[I] = (d4){0.0, 0.0, 0.0, 0.0};
-    }
-  }
-#pragma unroll
-  for (int I = 1; I < NB; ++I) {
-    if (I > Kc && I < nb) {
-      d4 acc0 = (d4){0.0, 0.0, 0.0, 0.0}, acc1 = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int j = 0; j < I; ++j) {
-        if (j >= Kc) {
-          double av[4];
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {            // A operand of L_Ij: lane (g, c) holds L[16 I + c][16 j + 4 s + g]
-            const int row = 16 * I + c, col = 16 * j + 4 * s + g;
-            av[s] = (row < T) ? L[(size_t)row * T + col] : 0.0;
-          }
-          if (j & 1) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc1 = mfma(av[s], Zc[j][s], acc1);
-          } else {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc0 = mfma(av[s], Zc[j][s], acc0);
-          }
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc0[r] += acc1[r];
-      double wv[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {                // A operand of W_I (diagonal block I of Z)
-        const int row = 16 * I + c, col = 16 * I + 4 * s + g;
-        wv[s] = (row < T && col < T) ? Z[(size_t)row * T + col] : ((row == col) ? 1.0 : 0.0);
-      }
-      d4 z = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < 4; ++s) z = mfma_sub(wv[s], acc0[s], z);      // -W_I acc
-      Zc[I] = z;
-    }
-  }
-  const bool bad = info && info[m] != 0;
-#pragma unroll
-  for (int I = 0; I < NB; ++I) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * I + g + 4 * r, col = 16 * Kc + c;
-      if (row < T && col < T && I != Kc) Z[(size_t)row * T + col] = bad ? __builtin_nan("") : ((I > Kc) ? Zc[I][r] : 0.0);
-    }
-  }
-}
-
-// Linv[:, 16 Jc ..] = L^{-1} e for block column Jc = blockIdx.y: factor again with the identity block as right-hand
-// side (reads A, which must still hold the input: launched BEFORE k_coop_potrf on the same stream).
-template <int NB>
-__global__ __launch_bounds__(64 * WAVES) void k_coop_inv(PotrfArgs a) {
-  using C = Coop<NB>;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const auto [rowbuf, Rbuf, Wbuf, scr, red, redi] = C::lds(smem);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c = lane & 15;
-  const int m = blockIdx.x, Jc = blockIdx.y;
-  const int T = a.T;
-  if (16 * Jc >= T) return;
-  const double* A = a.A + (size_t)m * T * T;
-  d4 U[C::NT];
-  coop_load_sym_upper<NB>(U, A, T, T, wave, lane, rowbuf + wave * DIAG_SCR);
-  __syncthreads();   // rowbuf served as per-wave staging for the loader
-  coop_regularise<NB>(U, a.add, a.jitter_rel, T, wave, lane, red);
-  for (int K = wave; K < NB; K += WAVES) {
-    d4 v;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = (K == Jc && g + 4 * r == c) ? 1.0 : 0.0;
-    lds_tile_store(Rbuf, K, lane, v);
-  }
-  __syncthreads();
-  PivotAcc pa;
-  pa.init();
-  coop_factor<NB, true>(U, rowbuf, Rbuf, Wbuf, scr, wave, lane, pa, nullptr, 0, T);
-  double* Z = a.Linv + (size_t)m * T * T;
-  for (int K = wave; K < NB; K += WAVES) {
-    const d4 z = lds_tile_load(Rbuf, K, lane);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = 16 * K + g + 4 * r, j = 16 * Jc + c;
-      if (i < T && j < T) Z[(size_t)i * T + j] = (K >= Jc) ? z[r] : 0.0;
-    }
-  }
-  if (a.inv_info && Jc == 0) {   // inverse-only call: block column 0 saw every pivot
-    int info;
-    (void)coop_logdet_info(pa, wave, lane, red, redi, info);
-    if (threadIdx.x == 0 && a.info) a.info[m] = info;
-  }
-}
-
 template <int NB>
 int launch_coop_score(const ScoreArgs& a, hipStream_t st) {
   const size_t lds = sizeof(double) * Coop<NB>::LDS_DOUBLES;
@@ -458,21 +292,9 @@ template <int NB>
 int launch_coop_potrf(const PotrfArgs& a, hipStream_t st) {
   const size_t lds = sizeof(double) * Coop<NB>::LDS_DOUBLES;
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_potrf<NB>), lds)) return rc_;
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_inv<NB>), lds)) return rc_;
   hipLaunchKernelGGL(k_coop_potrf<NB>, dim3(a.b), dim3(64 * WAVES), lds, st, a);
-  if (a.Linv) {   // L^-1 from L: the factor kernel left the diagonal blocks' inverses in Linv, k_trtri fills in the block columns
-    const int waves = a.b * NB;
-    hipLaunchKernelGGL(k_trtri<NB>, dim3((waves + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a.Aout ? a.Aout : a.A, a.Linv, a.T, a.b,
-                       a.info);
-  }
-  return launch_status();
-}
-
-template <int NB>
-int launch_coop_inv_only(const PotrfArgs& a, hipStream_t st) {   // L^-1 without the in-place factor (A untouched)
-  const size_t lds = sizeof(double) * Coop<NB>::LDS_DOUBLES;
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_inv<NB>), lds)) return rc_;
-  hipLaunchKernelGGL(k_coop_inv<NB>, dim3(a.b, NB), dim3(64 * WAVES), lds, st, a);
+  // L^-1 from L: the factor kernel left the diagonal blocks' inverses in Linv, k_trtri (hgp_inverse.hip) fills in the block columns
+  if (a.Linv) hgp_internal_trtri(a.Aout ? a.Aout : a.A, a.Linv, a.T, a.b, a.info, st);
   return launch_status();
 }
 
@@ -494,19 +316,15 @@ int hgp_internal_ensure_dynamic_lds(const void* fn, size_t bytes) {
   return 0;
 }
 
-int hgp_internal_chol_inverse(const PotrfArgs& a, int NB, hipStream_t st) {
-  if (NB > 8) return dispatch_nb_coop(16 * NB, [&](auto nb) { return launch_coop_potrf<decltype(nb)::value>(a, st); });
-  // one workgroup per block column (the trailing updates split over its four waves) halves the latency at T = 128
-  if (NB == 8) return launch_coop_inv_only<8>(a, st);
-  dispatch_nb_wave(16 * NB, [&](auto nb) { launch_wave_inv<decltype(nb)::value>(a, st); });
-  return launch_status();
+int hgp_internal_potrf_coop(const PotrfArgs& a, hipStream_t st) {
+  return dispatch_nb_coop(a.T, [&](auto nb) { return launch_coop_potrf<decltype(nb)::value>(a, st); });
 }
 
 int hgp_internal_potrf_ws(const double* A, const int32_t* idx, int T, int b, double jitter_rel, double* L, int32_t* info, hipStream_t st) {
   PotrfArgs a{const_cast<double*>(A), T, b, jitter_rel, 0.0, nullptr, nullptr, info};
   a.Aout = L;
   a.src_idx = idx;
-  if (T > HGP_MAX_T_WAVE) return dispatch_nb_coop(T, [&](auto nb) { return launch_coop_potrf<decltype(nb)::value>(a, st); });
+  if (T > HGP_MAX_T_WAVE) return hgp_internal_potrf_coop(a, st);
   dispatch_nb_wave(T, [&](auto nb) {
     hipLaunchKernelGGL(k_wave_potrf<decltype(nb)::value>, dim3((b + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a);
   });
@@ -522,11 +340,11 @@ int hgp_potrf_batched_f64(double* A, int T, int b, double jitter_rel, double add
   if (T > HGP_MAX_T_COOP) return -2;
   PotrfArgs a{A, T, b, jitter_rel, add_diag, Linv, logdet, info};
   hipStream_t st = (hipStream_t)stream;
-  if (T > HGP_MAX_T_WAVE) return dispatch_nb_coop(T, [&](auto nb) { return launch_coop_potrf<decltype(nb)::value>(a, st); });
+  if (T > HGP_MAX_T_WAVE) return hgp_internal_potrf_coop(a, st);
+  // L^-1 first, from the input still in A (one wave per block column); info comes from the factor kernel behind it
+  if (Linv) hgp_internal_wave_inverse(InvArgs{A, T, b, jitter_rel, add_diag, Linv, /*info=*/nullptr}, st);
   dispatch_nb_wave(T, [&](auto nb) {
-    constexpr int NB = decltype(nb)::value;
-    if (Linv) launch_wave_inv<NB>(a, st);
-    hipLaunchKernelGGL(k_wave_potrf<NB>, dim3((b + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a);
+    hipLaunchKernelGGL(k_wave_potrf<decltype(nb)::value>, dim3((b + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a);
   });
   return launch_status();
 }
@@ -565,35 +383,6 @@ int hgp_score_each_f64(const double* Y, int ldy, const double* mean, long mean_s
     });
   });
   return launch_status();
-}
-
-int hgp_chol_inverse_batched_f64(const double* A, int T, int b, double jitter_rel, double add_diag, double* Linv,
-                                 int32_t* info, void* stream) {
-  if (b == 0) return 0;
-  if (!A || !Linv || T <= 0 || b < 0) return -1;
-  if (T > HGP_MAX_T_COOP) return -2;
-  PotrfArgs a{const_cast<double*>(A), T, b, jitter_rel, add_diag, Linv, nullptr, info};
-  a.inv_info = 1;
-  hipStream_t st = (hipStream_t)stream;
-  if (T > HGP_MAX_T_WAVE) return dispatch_nb_coop(T, [&](auto nb) { return launch_coop_inv_only<decltype(nb)::value>(a, st); });
-  dispatch_nb_wave(T, [&](auto nb) { launch_wave_inv<decltype(nb)::value>(a, st); });
-  return launch_status();
-}
-
-// The same inverse with a caller-provided workspace work[b,T,T] (T > 128 only; may be NULL): for batches that would fill the
-// chip several times over with the per-block-column kernel (b * NB workgroups, every one a full factorisation) the matrix is
-// factored ONCE into the workspace and L^-1 follows from L by block columns (k_trtri).  Small batches keep the per-block-column
-// kernel: one launch, 97 us at T = 256 against 146 + 73 us for factor + k_trtri.
-int hgp_chol_inverse_ws_f64(const double* A, int T, int b, double jitter_rel, double add_diag, double* Linv, double* work,
-                            int32_t* info, void* stream) {
-  if (b == 0) return 0;
-  if (!A || !Linv || T <= 0 || b < 0) return -1;
-  if (T > HGP_MAX_T_COOP) return -2;
-  const int nb = T <= 192 ? 12 : 16;
-  if (T <= HGP_MAX_T_WAVE || !work || (long)b * nb <= 512) return hgp_chol_inverse_batched_f64(A, T, b, jitter_rel, add_diag, Linv, info, stream);
-  PotrfArgs a{const_cast<double*>(A), T, b, jitter_rel, add_diag, Linv, nullptr, info};
-  a.Aout = work;
-  return dispatch_nb_coop(T, [&](auto nbc) { return launch_coop_potrf<decltype(nbc)::value>(a, (hipStream_t)stream); });
 }
 
 }  // extern "C"

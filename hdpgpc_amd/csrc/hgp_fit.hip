@@ -3,7 +3,7 @@
 // time.  One Adam step of ALL fits is a fixed sequence of launches and nothing returns to the host between them:
 //   1. k_fit_gram     K_b = c RBF(ell) + noise I from the raw parameters in the fit's state row (a frozen fit: the identity,
 //                     so that the shared factor launch has nothing to fail on)
-//   2. the batched inverse factor of the Cholesky family (hgp_factor.hip): Z_b = L_b^-1, info_b
+//   2. the batched inverse factor of the L^-1 family (hgp_inverse.hip): Z_b = L_b^-1, info_b
 //                     (T <= 128: one launch, one wave per block column;  above: in-place cooperative factor + k_trtri, two launches)
 //   3. K^-1 = Z^T Z   one batched product on the matrix core (hgp_gemm.hip), into the buffer K came from
 //   4. k_fit_update   one workgroup per fit: alpha = K^-1 r, the loss, the three traces of hgp_lml_grad_f64, the chain rule to the

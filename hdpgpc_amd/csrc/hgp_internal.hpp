@@ -1,6 +1,7 @@
 // Host-side declarations shared by the translation units of libhdpgpc_hip.so (not part of the C-ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -89,23 +90,47 @@ struct hgp_pairs_plan {
   int score_out = 0;            // hgp_pairs_plan_set_score_output: out_quad receives -0.5 quad - 0.5 Ts log(2 pi)
 };
 
-// hgp_factor.hip: arguments of the factor / inverse-factor kernels
+// hgp_factor.hip: arguments of the factor kernels
 struct PotrfArgs {
   double* A;
   int T, b;
   double jitter_rel, add;
-  double* Linv;
+  double* Linv;     // L^-1 is wanted too: read by the cooperative factor (T > 128: its diagonal blocks, the rest by k_trtri); the one-wave factor ignores it
   double* logdet;
   int32_t* info;
-  int inv_info = 0;   // k_wave_inv also reports info (used when no in-place factor follows)
-  int symmetric = 0;  // the caller guarantees A == A^T bit for bit: only the upper tiles are read
-  double* Aout = nullptr;   // factor kernels: L goes here instead of over A (hgp_chol_inverse_ws_f64, hgp_internal_potrf_ws)
-  const int32_t* src_idx = nullptr;   // factor kernels: item m reads matrix src_idx[m] of A (NULL: m); needs Aout
+  double* Aout = nullptr;   // L goes here instead of over A (hgp_internal_potrf_ws, hgp_internal_chol_inverse)
+  const int32_t* src_idx = nullptr;   // item m reads matrix src_idx[m] of A (NULL: m); needs Aout
 };
 // L[b,T,T] = the a3 factor of A[idx[m]] (idx NULL: A[m]) for m < b, zeros above the diagonal; A is only read.  One launch.
 int hgp_internal_potrf_ws(const double* A, const int32_t* idx, int T, int b, double jitter_rel, double* L, int32_t* info, hipStream_t st);
-// Z = chol(A)^-1 for a plan of NB tiles (inverse factor only below NB = 12; A receives L from there on)
-int hgp_internal_chol_inverse(const PotrfArgs& a, int NB, hipStream_t st);
+// 128 < T <= HGP_MAX_T_COOP: the cooperative factor as the arguments say, and L^-1 -> a.Linv behind it when that is set (hgp_internal_trtri)
+int hgp_internal_potrf_coop(const PotrfArgs& a, hipStream_t st);
+
+// hgp_inverse.hip: arguments of every kernel that produces L^-1 (one 16-column panel per wave / workgroup rides a factorisation)
+struct InvArgs {
+  // the first 64 bytes, one cache line of kernel arguments: everything the plain forms read (the one-wave kernel is latency-bound from
+  // its first instruction to its last store, and a second line costs it 0.2 us - profiles/inverse_ab_bench.txt)
+  const double* A;       // [b,T,T], only read
+  int T, b;
+  double jitter_rel, add;
+  double* Linv;          // [b,T,T]  Z = L^-1 (may be NULL when rhs is given: only the solves are wanted)
+  int32_t* info;         // [b] or NULL: not reported (a factor kernel behind this launch writes it)
+  const double* rhs = nullptr;   // [b,T,T] or NULL
+  int rhs_trans = 0;     // solve against rhs^T
+  int symmetric = 0;     // the caller guarantees A == A^T bit for bit: only the upper tiles are read (k_wave_inv<NB, false>; the others ignore it)
+  // read by the forms with right-hand sides only
+  const int32_t* rhs_on = nullptr;   // [b] or NULL: item m carries a right-hand side iff rhs_on[m] != 0 (NULL: all do when rhs != NULL)
+  double* rhs_out = nullptr;         // [b,T,T]  Y = L^-1 op(rhs)
+};
+static_assert(offsetof(InvArgs, rhs_on) == 64, "InvArgs: the plain forms' arguments fill the first 64 bytes");
+// Z = chol(A)^-1 -> a.Linv for a plan of NB tiles (a.T = 16 NB; no right-hand sides).  Below NB = 12 only a.A is read and
+// factor_out is not touched; from NB = 12 on the matrix is factored first and factor_out [b,T,T] RECEIVES L (zeros above the
+// diagonal blocks) - it may be a.A itself, which is then overwritten: both callers pass their own matrix.
+int hgp_internal_chol_inverse(const InvArgs& a, int NB, double* factor_out, hipStream_t st);
+// T <= HGP_MAX_T_WAVE, no right-hand sides: Z -> a.Linv by one wave per (matrix, block column), one launch; a.A is only read
+void hgp_internal_wave_inverse(const InvArgs& a, hipStream_t st);
+// Z = L^-1 from L [b,T,T] and the inverses of its diagonal blocks already in Z's diagonal blocks (T > 128); NaN where info[m] != 0
+void hgp_internal_trtri(const double* L, double* Z, int T, int b, const int32_t* info, hipStream_t st);
 // hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device), under a lock
 int hgp_internal_ensure_dynamic_lds(const void* fn, size_t bytes);
 

@@ -1,7 +1,7 @@
 // The pairs plan: the per-cluster operators of the explicit-operator pair kernels (hgp_pairs.hip) and of the solve-based kernel
 // (hgp_pairs_acc.hip), the layout of the plan's device buffer, and the C-ABI of the plan and of hgp_loglik_pairs_f64.
 //
-// hgp_pairs_plan_update, TP <= 128:  k_prep_build (K~, S, scalars) -> inverse factor Z = L^-1 (hgp_factor.hip) -> k_plan_ops<NB>
+// hgp_pairs_plan_update, TP <= 128:  k_prep_build (K~, S, scalars) -> inverse factor Z = L^-1 (hgp_inverse.hip) -> k_plan_ops<NB>
 // (M', a', ||K~^-1||_inf and the routing flags in ONE launch: every workgroup recomputes from Z the strips of Kinv = Z^T Z,
 // P = S Kinv and the two tiles of Q = Kinv P its tile pair of M' needs; Kinv, P and Q never reach memory) -> the operands of the
 // solve-based kernel for the flagged clusters (hgp_internal_acc_prep).
@@ -532,10 +532,10 @@ int hgp_pairs_plan_update(hgp_pairs_plan* p, const double* x_basis, const double
   PrepArgs pa{x_basis, mean, Sigma, T, TP, K, p->d_theta, p->d_scal, p->d_A, p->d_S, p->d_xb};
   hipLaunchKernelGGL(k_prep_build, dim3(K, 8), dim3(256), 0, st, pa);
   // Z = chol(K~)^{-1}  (the factor itself is not needed)
-  PotrfArgs fa{p->d_A, TP, K, 0.0, 0.0, p->d_Z, nullptr, info};
-  fa.inv_info = 1;
-  fa.symmetric = 1;   // k_prep_build writes K~ from (x_i - x_j)^2: exactly symmetric
-  if (int rc = hgp_internal_chol_inverse(fa, p->NB, st)) return rc;
+  // symmetric = 1: k_prep_build writes K~ from (x_i - x_j)^2, exactly symmetric
+  InvArgs fa{p->d_A, TP, K, 0.0, 0.0, p->d_Z, info};
+  fa.symmetric = 1;
+  if (int rc = hgp_internal_chol_inverse(fa, p->NB, p->d_A, st)) return rc;   // TP > 128: K~ is overwritten by its factor
   if (!p->coop) {
     // TP <= 128: M', a', ||K~^-1||_inf and the routing flags in one launch behind the inverse; Kinv, P, Q never reach memory
     PlanOpsArgs oa{p->d_Z, p->d_S, mean, p->d_scal, T, K, p->d_Mp, p->d_ap, p->acc_tol, p->d_acc_list, p->d_fb,

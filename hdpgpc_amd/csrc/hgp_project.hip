@@ -11,7 +11,7 @@
 // whose product form loses two digits at the drivers' length-scale 3), arranged so that neither needs a transposed tile.  The
 // [T, L] cross-Gram never exists in memory: HBM sees x, y and yp.
 //
-// 128 < ld <= 256: composed from the cooperative kernels of hgp_factor.hip - k_project_build writes K~ (identity for rows that
+// 128 < ld <= 256: composed from the cooperative factor (hgp_factor.hip) and k_trtri (hgp_inverse.hip) - k_project_build writes K~ (identity for rows that
 // need no factor), hgp_internal_chol_inverse leaves L and Z = L^-1 in the workspace, k_project_apply (one workgroup per (segment,
 // 16 leads)) forms alpha = Z^T Z y with one step of refinement against K~ rebuilt on the fly, alpha += Z^T Z (y - K~ alpha)
 // (IterativeGaussianProcess._spd_solve), and yp = K(xb, x) alpha.  Two launches plus the factor's two, one C call.
@@ -345,8 +345,8 @@ int hgp_project_ragged_f64(const double* x, const double* y, const int32_t* leng
   a.Z = a.Kt + (size_t)N * ld * ld;
   hipLaunchKernelGGL(k_project_build, dim3(N), dim3(PROJ_THREADS), 0, st, a);
   if (int rc_ = launch_status()) return rc_;
-  PotrfArgs pf{a.Kt, ld, N, 0.0, 0.0, a.Z, nullptr, info};
-  if (int rc_ = hgp_internal_chol_inverse(pf, (ld + 15) >> 4, st)) return rc_;
+  InvArgs pf{a.Kt, ld, N, 0.0, 0.0, a.Z, info};
+  if (int rc_ = hgp_internal_chol_inverse(pf, (ld + 15) >> 4, a.Kt, st)) return rc_;   // K~ <- L
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_project_apply), ProjectApplyLds::BYTES)) return rc_;
   hipLaunchKernelGGL(k_project_apply, dim3(N, nch), dim3(PROJ_THREADS), ProjectApplyLds::BYTES, st, a);
   return launch_status();

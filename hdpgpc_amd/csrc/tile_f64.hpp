@@ -905,7 +905,7 @@ __device__ __forceinline__ double coop_factor(d4 (&U)[Coop<NB>::NT], double* row
   // accumulator tile of U_KJ (K < J) IS the A operand of L[J, K] = U_KJ^T, so it is stored as it stands, 32 bytes per lane, at
   // tile index J (J - 1) / 2 + K; the inverses W_K of the diagonal blocks (A-operand order already) at tile index K of Wpack.
   // Wout (optional): the inverses W_K = L_KK^{-1} of the diagonal blocks go to the diagonal blocks of this [n, ldw] matrix -
-  // they ARE the diagonal blocks of L^{-1}; k_trtri (hgp_factor.hip) fills in the rest from L.
+  // they ARE the diagonal blocks of L^{-1}; k_trtri (hgp_inverse.hip) fills in the rest from L.
   // kstop (optional, the same in every thread): block steps K >= kstop are not taken - for callers whose blocks from kstop on are
   // identity padding (their factor is the identity, nothing of it is read) and who only want the right-hand side / the pivots.
   using C = Coop<NB>;
@@ -1352,7 +1352,7 @@ __device__ __forceinline__ void df_wait_all_ge(int* tdone, int v, int lane, int*
 }
 
 // row0 / row1 / row2, Wall, zbuf: the members of CoopH<NB>::DfLds<RHS>; scr: the calling wave's diag16 scratch; flags: the DF_FLAGS
-// counters of CoopH<NB> (zeroed here).  (The members travel as pointers: with the struct as the parameter k_cooph_inv_rhs allocates
+// counters of CoopH<NB> (zeroed here).  (The members travel as pointers: with the struct as the parameter k_cooph_inv allocates
 // its registers differently.)
 // Two refinements on the critical path (the chain diag16(K) -> W_K -> tile (K, K+1) -> tile (K+1, K+1) -> diag16(K+1)):
 //  * the owner of block K + 1 solves ONLY that panel tile first, updates its diagonal tile straight from the accumulator (no LDS
@@ -1364,7 +1364,7 @@ __device__ __forceinline__ void df_wait_all_ge(int* tdone, int v, int lane, int*
 //  read issued together with the LDS tile the update needs anyway (no extra round trip), the mate sleeping only while diag16_acc
 //  runs: 14.16 vs 13.34 ms per 32 768 pairs - the MFMA time the mate loses is not given back by the shorter chain.)
 // RP (round 4): instead of the single vector dvec, a block column of 16 right-hand sides rides the factorisation (the inversions
-// of the member step, k_cooph_inv_rhs).  Tile I of it lives in the registers of the wave that owns block column I (*RAp for its column
+// of the member step, k_cooph_inv in hgp_inverse.hip).  Tile I of it lives in the registers of the wave that owns block column I (*RAp for its column
 // JA, *RBp for JB); Z_K = W_K R_K is formed by the pivot wave right behind diag16_acc and published in zbuf ([NB] tiles of LDS)
 // together with W_K; R_J -= U_KJ^T Z_K follows each panel tile while it is still in its accumulator.  On exit the tiles hold L^-1 R.
 // RHS = 2: no right-hand side at all (a8 / a9 above T = 128: the factor is wanted, packed).  Lpack / Wpack (optional, any mode): the

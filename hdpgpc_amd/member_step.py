@@ -138,8 +138,8 @@ class Chain:
 
     def build_lists(self, shared, c, alloc=None, frozen=False):
         """The member step as ONE launch per dependency level (hgp_chain.hip): every product of the step is an item of a
-        device-resident list whose pointers are fixed for the life of the chain; the two inversions carry their right-hand
-        sides.  14 launches per member, no torch arithmetic, no allocation (measured: a dependent launch costs ~4.5 us
+        device-resident list whose pointers are fixed for the life of the chain; the two inversions (hgp_inverse.hip) carry their
+        right-hand sides.  14 launches per member, no torch arithmetic, no allocation (measured: a dependent launch costs ~4.5 us
         whatever it does, so launches - not flops - were the step's time).  128 < T <= 256: the inversions are the
         cooperative inverse-only kernels and Z rhs is one more list level behind each of them (16 launches).
         shared, c: this chain is chain c of shared_buffers (one batched inversion for all of them).  alloc(*shape) (optional):

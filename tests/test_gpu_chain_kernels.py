@@ -1,5 +1,5 @@
-"""Direct tests of the member-step entry points of hgp_chain.hip through the C-ABI: the device-resident
-product lists and the Cholesky inverse with riding right-hand sides, against NumPy."""
+"""Direct tests of the member-step entry points through the C-ABI: the device-resident product lists of
+hgp_chain.hip and the Cholesky inverse of hgp_inverse.hip, plain and with riding right-hand sides, against NumPy."""
 import numpy as np
 import pytest
 import torch
@@ -105,7 +105,7 @@ def test_chol_inverse_with_riding_right_hand_sides(T, rhs_trans):
 
 @pytest.mark.parametrize("T", [17, 40, 50, 64, 70, 90, 100, 113, 128])
 def test_chol_inverse_rhs_small_and_large_batches_agree_bit_for_bit(T):
-    """Few matrices take one workgroup per (matrix, panel) (k_coop_inv_rhs), many take one wave per panel (k_wave_inv_rhs): the same
+    """Few matrices take one workgroup per (matrix, panel) (k_coop_inv / k_cooph_inv), many take one wave per panel (k_wave_inv): the same
     tile arithmetic in the same order, so a matrix must come out identical whichever batch it rides in - including its info."""
     from hdpgpc_amd import ops
     rng = np.random.default_rng(100 + T)
@@ -178,3 +178,75 @@ def test_chol_inverse_shift_and_jitter_in_one_pass(T):
     ref = torch.linalg.inv(torch.linalg.cholesky(0.5 * (A + A.transpose(1, 2)) + shift[:, None, None] * torch.eye(T, dtype=torch.float64)))
     for m in range(3):
         assert np.allclose(Z[m].cpu().numpy(), ref[m].numpy(), rtol=1e-10, atol=1e-12 * float(ref[m].abs().max()))
+
+
+def _nearly_symmetric_batch(T, seed, b=3):
+    """The matrices of the first inverse test of this file: SPD plus a slightly non-symmetric perturbation."""
+    rng = np.random.default_rng(seed)
+    Q = rng.normal(size=(b, T, T))
+    return Q @ Q.transpose(0, 2, 1) / T + np.eye(T) + 1e-3 * rng.normal(size=(b, T, T))
+
+
+def _inverse_both_entries(A, jitter_rel, add_diag):
+    """(Z, info) of the plain entry and of the right-hand-side entry called without right-hand sides, as NumPy arrays."""
+    from hdpgpc_amd import ops
+    dA = dev(A)
+    Zp, ip = ops.chol_inverse(dA, jitter_rel, add_diag)
+    Zr = torch.full(A.shape, np.nan, dtype=torch.float64, device="cuda")
+    ir = torch.full((A.shape[0],), -7, dtype=torch.int32, device="cuda")
+    ops.chol_inverse_rhs(dA, Zr, None, None, ir, jitter_rel=jitter_rel, add_diag=add_diag)
+    torch.cuda.synchronize()
+    return Zp.cpu().numpy(), ip.tolist(), Zr.cpu().numpy(), ir.tolist()
+
+
+@pytest.mark.parametrize("T", [17, 50, 90, 128])
+def test_chol_inverse_plain_entry_equals_rhs_entry_bit_for_bit(T):
+    """One body per kernel of the L^-1 family: the plain entry (one wave per block column) and the right-hand-side entry without
+    right-hand sides (T = 17: one wave, NB = 2 padded; 50: Coop<4>; 90: CoopH<6>, padded, burst loader; 128: CoopH<8>) give the
+    same bits and the same status, a matrix that is not positive definite included."""
+    A = _nearly_symmetric_batch(T, 300 + T)
+    A[1] = -A[1]
+    Zp, ip, Zr, ir = _inverse_both_entries(A, 0.0, 1e-8)
+    assert ip == [0, 1, 0] and ir == [0, 1, 0]
+    for m in (0, 2):
+        assert np.array_equal(Zp[m], Zr[m])
+
+
+def test_chol_inverse_plain_entry_equals_rhs_entry_with_jitter():
+    """The same with add_diag and jitter_rel in one call: the regulariser in one pass, written out (one wave) and shared (CoopH)."""
+    Zp, ip, Zr, ir = _inverse_both_entries(_nearly_symmetric_batch(96, 396), 1e-3, 0.5)
+    assert ip == [0, 0, 0] and ir == [0, 0, 0]
+    assert np.array_equal(Zp, Zr)
+
+
+def test_potrf_info_comes_from_the_factor_kernel():
+    """hgp_potrf_batched_f64 with Linv launches the inverse first (told not to report) and the factor behind it: info and the bits
+    of L must not depend on whether L^-1 was asked for.  This pins the result, not who wrote it - both kernels see the same pivots."""
+    from hdpgpc_amd import ops
+    A = _nearly_symmetric_batch(33, 333)
+    A[1] = -A[1]
+    L1, info1, _ = ops.potrf_batched(dev(A), 0.0, 0.0, want_inv=True)
+    L0, info0 = ops.potrf_batched(dev(A), 0.0, 0.0, want_inv=False)
+    torch.cuda.synchronize()
+    assert info1.tolist() == info0.tolist() == [0, 1, 0]
+    assert L1.cpu().numpy().tobytes() == L0.cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("T,Tbig", [(144, 192), (200, 208)])
+def test_chol_inverse_padding_steps_change_nothing(T, Tbig):
+    """A matrix of order T and diag(A, I) of order Tbig take the same cooperative kernel (Coop<12>; Coop<16> with a partial last
+    block): the block steps over the identity - padding in one, data in the other - leave the bits of L^-1 as they are."""
+    from hdpgpc_amd import ops
+    rng = np.random.default_rng(T)
+    Q = rng.normal(size=(2, T, T))
+    A = Q @ Q.transpose(0, 2, 1) / T + np.eye(T)
+    Abig = np.tile(np.eye(Tbig), (2, 1, 1))
+    Abig[:, :T, :T] = A
+    Z, info = ops.chol_inverse(dev(A), 0.0, 0.0)
+    Zbig, info_big = ops.chol_inverse(dev(Abig), 0.0, 0.0)
+    torch.cuda.synchronize()
+    assert info.tolist() == [0, 0] and info_big.tolist() == [0, 0]
+    Z, Zbig = Z.cpu().numpy(), Zbig.cpu().numpy()
+    assert np.array_equal(Zbig[:, :T, :T], Z)
+    assert np.array_equal(Zbig[:, T:, T:], np.tile(np.eye(Tbig - T), (2, 1, 1)))
+    assert not Zbig[:, :T, T:].any() and not Zbig[:, T:, :T].any()

@@ -1,4 +1,4 @@
-"""The batched tile GEMM (hgp_gemm.hip) and the list GEMM (hgp_chain.hip) on the paths the product's shapes never take: the
+"""The batched tile GEMM (hgp_gemm.hip) and the list GEMM (hgp_chain.hip, which kept it when the inverses moved to hgp_inverse.hip) on the paths the product's shapes never take: the
 one-wave-per-32x32-block kernel k_gemm22, batches beyond one grid (chunks of 65535), beta != 0 reading C, operands with
 lda > cols and batch strides larger than a matrix (or zero), both transposes at once, every side of the dispatch's Kd boundaries,
 and each launch form of ops.GemmList on its own.

@@ -203,7 +203,7 @@ def test_producer_full_pass_weighted_reproduces_reference_state(tag, members):
 
 
 def test_producer_step_forms_agree():
-    """The member step exists in two forms - one launch per dependency level, replayed from hipGraphs (hgp_chain.hip driven by
+    """The member step exists in two forms - one launch per dependency level, replayed from hipGraphs (hgp_chain.hip and hgp_inverse.hip driven by
     chain_batch, the default) and the eager methods (use_graphs=False).  They order the same arithmetic differently (B^T A^-1 as
     (Z B)^T Z against B^T (Z^T Z)): every list must agree to 1e-9."""
     g = golden("state_t45.npz")

@@ -4,8 +4,8 @@ Each directory holds the device assembly of one build, one .s per translation un
     hipcc <the Makefile's FLAGS> --cuda-device-only -S -o DIR/<unit>.s hdpgpc_amd/csrc/<unit>.hip
 Kernels are paired by mangled name, whichever unit they sit in, so a kernel that moved between units pairs with itself.
 Reported per kernel: present / missing, whether the .amdhsa_kernel block (registers, LDS, scratch) is identical, and whether the
-body is identical once comments are gone and the per-function counter is taken out of the local labels (.LBB<n>_<m>,
-.Lfunc_end<n>).  OLD=NEW rewrites DIR_A's text first, for a kernel whose mangled name changed because an argument type moved
+body is identical once comments are gone and the per-unit counters are taken out of the local labels (.LBB<n>_<m>,
+.Lfunc_end<n>, .Lpost_getpc<n>).  OLD=NEW rewrites DIR_A's text first, for a kernel whose mangled name changed because an argument type moved
 (NS_9PotrfArgsE=9PotrfArgs: out of the anonymous namespace).  A plain text comparison: it knows no instruction.  Exit status 0
 only when nothing differs."""
 import difflib
@@ -21,6 +21,7 @@ def normalise(lines):
         l = l.split(";", 1)[0].rstrip()
         l = re.sub(r"\.LBB\d+_", ".LBB_", l)
         l = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", l)
+        l = re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", l)
         if l.strip():
             out.append(l)
     return out
