@@ -140,6 +140,23 @@ struct PairsBand {
   }
 };
 
+// Operand addresses of band_sweeps.  LDS pointers are kept as 32-bit addresses of the LDS address space, so that a compile-time
+// offset below LDS_IMM_SPAN becomes the 16-bit immediate of ds_read.
+typedef const __attribute__((address_space(3))) char* lds_cbytes;
+typedef const __attribute__((address_space(3))) double lds_cdouble;
+constexpr unsigned LDS_IMM_SPAN = 65536;
+// Opaque in place: the registers keep their values, the compiler forgets them.  No instruction, no copy.
+__device__ __forceinline__ void launder_lds(lds_cbytes& a, lds_cbytes& b) { asm volatile("" : "+v"(a), "+v"(b)); }
+// The same for a uniform global pointer, which stays in an SGPR pair: what is added to the result can only be the VGPR offset
+// and the immediate of a scalar-base global_load.
+typedef const __attribute__((address_space(1))) char* global_cbytes;
+typedef const __attribute__((address_space(1))) double global_cdouble;
+typedef const __attribute__((address_space(1))) d2 global_cd2;
+__device__ __forceinline__ global_cbytes launder_sgpr(global_cbytes p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
 template <int NB, int RD_>
 __device__ __forceinline__ void band_sweeps(d4 (&cov)[NB * (NB + 1) / 2], const double* __restrict__ Mu, const double* E,
                                             int lane_in, double cc, double noise, int Ts
@@ -152,31 +169,52 @@ __device__ __forceinline__ void band_sweeps(d4 (&cov)[NB * (NB + 1) / 2], const 
   constexpr int RD = RD_;   // ring slots (half-blocks in flight): NB <= 6 has the registers for eight at one wave per SIMD
   double ra[RD][2][NH], re[RD][2];
   d4 BJ[NH];
-  // Every operand address of the sweeps is  (uniform base + compile-time constant) + ONE of two lane offsets: Mu is uniform
-  // (the cluster index comes through v_readfirstlane), so the M' loads take the scalar-base form of global_load and the E reads
-  // an immediate offset - the ~14 VALU instructions of address arithmetic per ring fill (1.5 k per pair) are gone.
-  const unsigned moff0 = (unsigned)((lane_in >> 4) * TP + 2 * (lane_in & 15));   // row g of M', tile-pair interleaved column 2c
-  const unsigned eoff0 = (unsigned)((lane_in >> 4) * TP + (lane_in & 15));       // row g, column c (E, and the odd last tile of M')
+  // Every operand address of the sweeps is  (uniform base + compile-time constant) + ONE per-lane byte offset, and no VALU
+  // instruction computes it (checked in the ISA, tools/band_region_counts.py: at NB = 8 all 217 loads of the region are
+  // `global_load_dwordx4 v, voff, s[base:base+1] offset:imm`, all 514 E reads `ds_read_b64 v, vaddr offset:imm`):
+  //  * M' (Mu is uniform: the cluster index comes through v_readfirstlane): one SGPR-pair base per fill, made opaque where the
+  //    fill stands (launder_sgpr: an s_add_u32 / s_addc_u32 pair, no load merged across fills), the lane offset mvo as the
+  //    32-bit VGPR offset of the scalar-base form of global_load, the rest as immediate.  The base points between the fill's two
+  //    k-steps (rows 4 TP doubles = 4 KiB apart at NB = 8), so both fit the signed 13-bit immediate.
+  //  * E: ds_read immediates reach 64 KiB and E spans 16 NB TP doubles (128 KiB at NB = 8), so there are two lane addresses
+  //    64 KiB apart, elo and ehi, and e_at picks one at compile time.  They are laundered IN PLACE before every read (no copy, no
+  //    instruction).  That also keeps two reads from being paired into a ds_read2st64_b64: the pair saves no instruction, since
+  //    the column offset 128 J is no multiple of its 512-byte unit and costs a v_add_u32 - and a VALU instruction cannot issue
+  //    beside the f64 MFMA, an LDS instruction can.
+  // (Before: `v_lshl_add_u64` of the lane offset onto the base, then 64-bit VALU adds of the constants, per load; a `v_add_u32`
+  // in front of every E read beyond 64 KiB: 2 018 -> 1 084 non-MFMA VALU instructions in the sweeps at NB = 8, 1 082 -> 442 at
+  // NB = 6; profiles/bandops_isa_counts.txt.)
+  const unsigned mvo = 8u * (unsigned)((lane_in >> 4) * TP + 2 * (lane_in & 15));    // row g of M', tile-pair interleaved column 2c
+  const unsigned evo = 8u * (unsigned)((lane_in >> 4) * TP + (lane_in & 15));        // row g, column c (the odd last tile of M')
+  lds_cbytes elo = (lds_cbytes)E + evo, ehi = elo + LDS_IMM_SPAN;                     // row g, column c of E
+  static_assert(sizeof(double) * TP * TP <= 2 * LDS_IMM_SPAN, "band_sweeps: E beyond the two lane addresses");
+  auto e_at = [&](int idx) -> double {   // E[g + row][c + col], idx = row TP + col a constant once unrolled: one ds_read, immediate offset
+    const unsigned off = 8u * (unsigned)idx;
+    launder_lds(elo, ehi);
+    return *reinterpret_cast<lds_cdouble*>((off < LDS_IMM_SPAN ? elo : ehi) + (off % LDS_IMM_SPAN));
+  };
   auto fill = [&](auto tc) {
     constexpr int t = decltype(tc)::value;
     constexpr auto it = PB::item(t);
     if constexpr (it.valid) {
       constexpr int slot = t % RD, rm = PB::rows(it.J, it.h);
-      const unsigned moff = (unsigned)launder((int)moff0), eoff = (unsigned)launder((int)eoff0);   // opaque per fill: no merging / hoisting of the loads of different fills
+      constexpr int krow = 16 * it.Lt + 8 * it.hb;   // first row of the fill's two k-steps
+      constexpr long MID = 8 * 2 * TP;               // bytes: half way between them
+      global_cbytes mb = launder_sgpr((global_cbytes)(Mu + 16 * NH * it.h + (size_t)krow * TP) + MID);
 #pragma unroll
       for (int s_ = 0; s_ < 2; ++s_) {
         if (!PB::alive(it.Lt, it.J, 2 * it.hb + s_)) continue;
-        const double* row_ = Mu + 16 * NH * it.h + (size_t)(16 * it.Lt + 4 * (2 * it.hb + s_)) * TP;
+        global_cbytes row_ = mb + ((long)8 * 4 * s_ * TP - MID);
 #pragma unroll
         for (int P_ = 0; P_ < NH / 2; ++P_) {
           if ((rm >> (2 * P_)) & 3) {
-            const d2 t_ = *reinterpret_cast<const d2*>(row_ + 32 * P_ + moff);
+            const d2 t_ = *reinterpret_cast<global_cd2*>(row_ + 8 * 32 * P_ + (size_t)mvo);
             ra[slot][s_][2 * P_] = t_[0];
             ra[slot][s_][2 * P_ + 1] = t_[1];
           }
         }
-        if ((NH & 1) && ((rm >> (NH - 1)) & 1)) ra[slot][s_][NH - 1] = (row_ + 16 * (NH - 1))[eoff];
-        re[slot][s_] = (E + (16 * it.Lt + 4 * (2 * it.hb + s_)) * TP + 16 * it.J)[eoff];
+        if ((NH & 1) && ((rm >> (NH - 1)) & 1)) ra[slot][s_][NH - 1] = *reinterpret_cast<global_cdouble*>(row_ + 8 * 16 * (NH - 1) + (size_t)evo);
+        re[slot][s_] = e_at((krow + 4 * s_) * TP + 16 * it.J);
       }
     }
   };
@@ -199,7 +237,6 @@ __device__ __forceinline__ void band_sweeps(d4 (&cov)[NB * (NB + 1) / 2], const 
     fill(std::integral_constant<int, t + RD>{});
     if constexpr (it.last) {
       const int g = lane_in >> 4, c = lane_in & 15;
-      const unsigned eoff = (unsigned)launder((int)eoff0);
       HGP_ACC(1);
       constexpr int NG = PB::ngroups(J, h);
       double af[2][4];
@@ -209,7 +246,7 @@ __device__ __forceinline__ void band_sweeps(d4 (&cov)[NB * (NB + 1) / 2], const 
           constexpr auto gp = PB::group(J, h, n_);
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            if (PB::alive(NH * h + gp.i, gp.I, r)) af[n_ & 1][r] = (E + (16 * (NH * h + gp.i) + 4 * r) * TP + 16 * gp.I)[eoff];
+            if (PB::alive(NH * h + gp.i, gp.I, r)) af[n_ & 1][r] = e_at((16 * (NH * h + gp.i) + 4 * r) * TP + 16 * gp.I);
         }
       };
       ldaf(std::integral_constant<int, 0>{});
@@ -219,7 +256,7 @@ __device__ __forceinline__ void band_sweeps(d4 (&cov)[NB * (NB + 1) / 2], const 
           d4 kt = (d4){0.0, 0.0, 0.0, 0.0};
           if ((PB::kmask(J) >> I) & 1) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) kt[r] = cc * (E + (16 * ((I + NH) % NB) + 4 * r) * TP + 16 * J)[eoff];
+            for (int r = 0; r < 4; ++r) kt[r] = cc * e_at((16 * ((I + NH) % NB) + 4 * r) * TP + 16 * J);
           }
           if (I == J) {
 #pragma unroll
