@@ -90,6 +90,24 @@ struct hgp_pairs_plan {
   int score_out = 0;            // hgp_pairs_plan_set_score_output: out_quad receives -0.5 quad - 0.5 Ts log(2 pi)
 };
 
+// TP <= 128: what the plan update keeps per cluster from call to call.  K~ = ker(xb, xb; theta) + jitter I, its
+// inverse factor Z and K~^-1 depend on the basis grid and, through the jitter 1e-4 mean|diag Sigma_k|, on ONE number of cluster k's
+// Sigma: a cluster whose grid and jitter have the bits of the call that computed them keeps d_A, d_Z, d_Kinv and info.  The
+// words live at the start of the Q area, which these sizes do not use otherwise; hgp_pairs_plan_create zeroes them.
+struct PlanReuse {
+  long long* key_jit;   // [K] bits of the jitter that d_A, d_Z, d_Kinv of cluster k were computed with
+  int32_t* valid;       // [K] d_Z, d_Kinv, key_jit, info of cluster k are complete and belong to d_xb: set LAST by k_plan_ops
+  int32_t* same;        // [K] this call's decision of k_prep_build, read by the launches behind it
+  int32_t* factored;    // [K] d_A of cluster k holds the factor L instead of K~ (k_acc_factor ran on it)
+  int32_t* info;        // [K] status of the factorisation that produced d_Z
+  static constexpr size_t BYTES_PER_CLUSTER = sizeof(long long) + 4 * sizeof(int32_t);
+};
+static inline PlanReuse plan_reuse(const hgp_pairs_plan* p) {
+  long long* key = reinterpret_cast<long long*>(p->d_Q);
+  int32_t* w = reinterpret_cast<int32_t*>(key + p->K);
+  return PlanReuse{key, w, w + p->K, w + 2 * p->K, w + 3 * p->K};
+}
+
 // hgp_factor.hip: arguments of the factor kernels
 struct PotrfArgs {
   double* A;
@@ -121,6 +139,9 @@ struct InvArgs {
   // read by the forms with right-hand sides only
   const int32_t* rhs_on = nullptr;   // [b] or NULL: item m carries a right-hand side iff rhs_on[m] != 0 (NULL: all do when rhs != NULL)
   double* rhs_out = nullptr;         // [b,T,T]  Y = L^-1 op(rhs)
+  // the plan update only (NULL for every other caller, who runs the kernels compiled without this test): item m is left alone -
+  // Linv and info of m keep what an earlier launch wrote - iff keep[m] != 0
+  const int32_t* keep = nullptr;     // [b]
 };
 static_assert(offsetof(InvArgs, rhs_on) == 64, "InvArgs: the plain forms' arguments fill the first 64 bytes");
 // Z = chol(A)^-1 -> a.Linv for a plan of NB tiles (a.T = 16 NB; no right-hand sides).  Below NB = 12 only a.A is read and

@@ -61,7 +61,9 @@ struct InvPanel {
 };
 
 // One wave per (matrix, panel), T <= 128.  Reads A (never writes it), so it may run BEFORE an in-place factor of the same A.
-template <int NB, bool RHS>
+// KEEP (the plan update, a.keep != NULL): an item whose keep word is set is left alone; the instances without it are the kernels
+// of every other caller, and do not read the word.
+template <int NB, bool RHS, bool KEEP = false>
 __global__ __launch_bounds__(64 * WAVES) void k_wave_inv(InvArgs a) {
   __shared__ __attribute__((aligned(16))) double scr_all[WAVES * DIAG_SCR];
   constexpr int NP = (RHS ? 2 : 1) * NB;
@@ -70,6 +72,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_wave_inv(InvArgs a) {
   const int m = w / NP;
   const int T = a.T;
   if (m >= a.b) return;
+  if constexpr (KEEP) {
+    if (a.keep[m] != 0) return;
+  }
   const InvPanel<RHS> pn(w % NP, NB);
   if (16 * pn.Jc >= T || pn.skip(a, m, lane == 0)) return;
   double* scr = scr_all + wave * DIAG_SCR;
@@ -97,6 +102,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_wave_inv(InvArgs a) {
 template <int NB, bool RHS>
 void launch_wave_inv(const InvArgs& a, hipStream_t st) {
   const int waves = a.b * (RHS ? 2 : 1) * NB;
+  if constexpr (!RHS && NB < 8) {   // the plan's sizes of the one-wave form (hgp_internal_chol_inverse)
+    if (a.keep) {
+      hipLaunchKernelGGL((k_wave_inv<NB, false, true>), dim3((waves + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a);
+      return;
+    }
+  }
   hipLaunchKernelGGL((k_wave_inv<NB, RHS>), dim3((waves + WAVES - 1) / WAVES), dim3(64 * WAVES), 0, st, a);
 }
 
@@ -108,7 +119,7 @@ void launch_wave_inv(const InvArgs& a, hipStream_t st) {
 // with NB panels, of which those beyond T leave at once, exactly as before the two forms shared this body: the steps over the
 // padding change no bit, and a run-time stop costs the instances for T > 128 the unrolled step loop (NB = 12: 800 bytes of
 // scratch, 154 us instead of 55 at T = 144; DESIGN.md 4, "The L^-1 family").
-template <int NB, bool RHS>
+template <int NB, bool RHS, bool KEEP = false>
 __global__ __launch_bounds__(64 * WAVES) void k_coop_inv(InvArgs a) {
   using C = Coop<NB>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -116,6 +127,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_inv(InvArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int T = a.T, nblk = (T + 15) >> 4;
   const int m = blockIdx.x;
+  if constexpr (KEEP) {
+    if (a.keep[m] != 0) return;   // the plan update: this item's Z and info stand (see k_wave_inv)
+  }
   if constexpr (!RHS) {
     if (16 * (int)blockIdx.y >= T) return;   // plain form: gridDim.y = NB
   }
@@ -143,6 +157,13 @@ __global__ __launch_bounds__(64 * WAVES) void k_coop_inv(InvArgs a) {
 template <int NB, bool RHS>
 int launch_coop_inv(const InvArgs& a, hipStream_t st) {
   const size_t lds = sizeof(double) * Coop<NB>::LDS_DOUBLES;
+  if constexpr (!RHS && NB == 8) {   // the plan's size of this form (hgp_internal_chol_inverse)
+    if (a.keep) {
+      if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_inv<NB, false, true>), lds)) return rc_;
+      hipLaunchKernelGGL((k_coop_inv<NB, false, true>), dim3(a.b, NB), dim3(64 * WAVES), lds, st, a);
+      return launch_status();
+    }
+  }
   if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_coop_inv<NB, RHS>), lds)) return rc_;
   hipLaunchKernelGGL((k_coop_inv<NB, RHS>), dim3(a.b, RHS ? 2 * ((a.T + 15) >> 4) : NB), dim3(64 * WAVES), lds, st, a);
   return launch_status();
@@ -353,6 +374,7 @@ void hgp_internal_wave_inverse(const InvArgs& a, hipStream_t st) {
 //                                      otherwise                               Wave<2|4|6|8, rhs>, 2 b nblk waves
 //   hgp_internal_chol_inverse          NB < 8                                  Wave<2|4|6, plain> (the only reader of `symmetric`)
 //     (a plan of NB tiles)             NB == 8                                 Coop<8, plain>
+//                                      NB <= 8 with a.keep (the plan update)   the KEEP instances of the two rows above
 //                                      NB > 8                                  factor into factor_out + k_trtri
 //   hgp_potrf_batched_f64 with Linv    T <= 128: Wave<2|4|6|8, plain> with info = NULL (hgp_internal_wave_inverse) before the in-place factor;
 //                                      above: factor + k_trtri

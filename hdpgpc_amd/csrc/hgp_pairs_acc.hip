@@ -54,11 +54,14 @@ __global__ void k_acc_flags(double* scal, int K, double tol, int32_t* acc_list) 
 // ------------------------------------------------------------------------------------------------ factor (T <= 128)
 // L = chol(K~) for the flagged clusters, one wave per cluster, written over the lower triangle of A (the upper
 // triangle keeps K~; nothing reads it afterwards).  For T > 128 the plan update has already factored in place.
+// factored[k] (PlanReuse): A of cluster k holds L already - the plan update kept the cluster's K~ from an earlier call, and this
+// kernel ran on it then; k_prep_build clears the word whenever it rebuilds K~.
 template <int NB>
-__global__ __launch_bounds__(64) void k_acc_factor(double* A, int TP, const double* scal, int32_t* info) {
+__global__ __launch_bounds__(64) void k_acc_factor(double* A, int TP, const double* scal, int32_t* info, int32_t* factored) {
   __shared__ __attribute__((aligned(16))) double scr[DIAG_SCR];
   const int k = blockIdx.x, lane = threadIdx.x;
   if (scal[8 * k + 7] == 0.0) return;
+  if (factored[k] != 0) return;
   double* Ak = A + (size_t)k * TP * TP;
   d4 U[NB * (NB + 1) / 2];
   d4 R[NB];
@@ -67,6 +70,7 @@ __global__ __launch_bounds__(64) void k_acc_factor(double* A, int TP, const doub
   pa.init();
   wave_factor<NB, 0>(U, R, scr, nullptr, nullptr, lane, pa, Ak, TP, TP);
   if (lane == 0 && info && pa.info != 0) info[k] = pa.info;
+  if (lane == 0) factored[k] = 1;
 }
 
 // ------------------------------------------------------------------------------------------------ operand packing
@@ -499,7 +503,8 @@ int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, bool flags_done
   if (p->acc_tol < 0.0) return launch_status();   // explicit operator everywhere: nothing else to prepare
   if (NB <= 8)   // T <= 128: the plan update computed L^{-1} only; T > 128: d_A already holds L
     dispatch_nb_wave(TP, [&](auto nb) {
-      hipLaunchKernelGGL(k_acc_factor<decltype(nb)::value>, dim3(K), dim3(64), 0, st, p->d_A, TP, p->d_scal, (int32_t*)nullptr);
+      hipLaunchKernelGGL(k_acc_factor<decltype(nb)::value>, dim3(K), dim3(64), 0, st, p->d_A, TP, p->d_scal, (int32_t*)nullptr,
+                         plan_reuse(p).factored);
     });
   AccPrepArgs a{p->d_A, p->d_S, mean, p->d_scal, p->T, TP, NB, p->d_Lop, p->d_LTop, p->d_Dop, p->d_Sop, p->d_mu};
   hipLaunchKernelGGL(k_acc_prep, dim3(K, 8), dim3(256), 0, st, a);

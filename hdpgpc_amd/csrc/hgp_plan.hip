@@ -3,8 +3,10 @@
 //
 // hgp_pairs_plan_update, TP <= 128:  k_prep_build (K~, S, scalars) -> inverse factor Z = L^-1 (hgp_inverse.hip) -> k_plan_ops<NB>
 // (M', a', ||K~^-1||_inf and the routing flags in ONE launch: every workgroup recomputes from Z the strips of Kinv = Z^T Z,
-// P = S Kinv and the two tiles of Q = Kinv P its tile pair of M' needs; Kinv, P and Q never reach memory) -> the operands of the
-// solve-based kernel for the flagged clusters (hgp_internal_acc_prep).
+// P = S Kinv and the two tiles of Q = Kinv P its tile pair of M' needs; P and Q never reach memory) -> the operands of the
+// solve-based kernel for the flagged clusters (hgp_internal_acc_prep).  K~, Z and Kinv of cluster k depend on the grid, theta and
+// the jitter 1e-4 mean|diag Sigma_k| alone: a cluster for which k_prep_build finds all of them unchanged, bit for bit, keeps them
+// (PlanReuse in hgp_internal.hpp) - no Gram build, its inverse workgroups leave at once, k_plan_ops reads its Kinv tiles from d_Kinv.
 // TP = 192, 256:  k_prep_build -> cooperative factor + inverse -> 3 x k_gemm (Kinv, P, Q in memory) -> k_prep_final -> k_acc_flags
 // -> operands (d_A holds L there, and the strips do not fit LDS).
 #include <algorithm>
@@ -30,6 +32,10 @@ struct PrepArgs {
   double* A;            // [K,TP,TP] K~ (identity padded)
   double* S;            // [K,TP,TP] 0.5 (Sigma + Sigma^T) (zero padded)
   double* xb_copy;      // [TP]
+  // TP <= 128 (reuse.same != NULL): K~ of a cluster whose grid and jitter have the bits of the call that computed it is not rebuilt,
+  // and xb_copy, only compared here, is written by k_plan_ops (no workgroup of this launch reads it while another writes it)
+  PlanReuse reuse;
+  int32_t* info;        // the caller's status array (or NULL): a kept cluster reports the status of the call that factored it
 };
 
 __global__ __launch_bounds__(256) void k_prep_build(PrepArgs a) {
@@ -65,6 +71,15 @@ __global__ __launch_bounds__(256) void k_prep_build(PrepArgs a) {
     double d = Sg[(size_t)i * T + i];
     if (!(fabs(d - mS) <= 1e-8 + 1e-5 * fabs(mS))) bad = 1;   // torch.isclose defaults (GPI.py:497)
   }
+  const bool reuse = a.reuse.same != nullptr;
+  if (reuse) {
+    // bit 1: the incoming grid is not, bit for bit, the one the kept operators were computed for (compared as integers:
+    // -0.0 differs from +0.0, a NaN pattern equals itself)
+    const long long* xn = reinterpret_cast<const long long*>(a.xb);
+    const long long* xo = reinterpret_cast<const long long*>(a.xb_copy);
+    for (int i = tid; i < T; i += 256)
+      if (xn[i] != xo[i]) bad |= 2;
+  }
   redi[tid] = bad;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -72,20 +87,41 @@ __global__ __launch_bounds__(256) void k_prep_build(PrepArgs a) {
     __syncthreads();
   }
   const double jit = 1e-4 * fmax(mean_abs, F64_EPS);           // GPI.py:488
+  // Every workgroup of the cluster takes the same decision from words that no workgroup of this launch changes under it: valid
+  // is only ever cleared here, and only when the decision is "differs" whatever valid reads; key_jit and xb_copy belong to k_plan_ops.
+  const bool same = reuse && (redi[0] & 2) == 0 && a.reuse.valid[k] != 0 && a.reuse.key_jit[k] == __double_as_longlong(jit);
   if (tid == 0 && blockIdx.y == 0) {
     double* sc = a.scal + 8 * k;
     sc[0] = c;
     sc[1] = ell;
     sc[2] = noise;
-    sc[3] = redi[0] ? 0.0 : 1.0;
+    sc[3] = (redi[0] & 1) ? 0.0 : 1.0;
     sc[4] = mS;
     sc[5] = jit;
-    sc[6] = 0.0;   // ||K~^{-1}||_inf: accumulated by k_prep_final with an atomic maximum
+    sc[6] = 0.0;   // ||K~^{-1}||_inf: accumulated by k_prep_final / k_plan_ops with an atomic maximum
+    if (reuse) {
+      a.reuse.same[k] = same ? 1 : 0;
+      if (same) {
+        if (a.info) a.info[k] = a.reuse.info[k];
+      } else {
+        a.reuse.valid[k] = 0;      // until the last workgroup of k_plan_ops has seen every store of this call
+        a.reuse.factored[k] = 0;   // d_A is K~ again
+      }
+    }
   }
-  if (k == 0 && blockIdx.y == 0)
+  if (!reuse && k == 0 && blockIdx.y == 0)
     for (int i = tid; i < TP; i += 256) a.xb_copy[i] = (i < T) ? a.xb[i] : 0.0;
   double* Ak = a.A + (size_t)k * TP * TP;
   double* Sk = a.S + (size_t)k * TP * TP;
+  if (same) {   // K~ (or its factor, where k_acc_factor has run) stands: S alone
+    for (int idx = blockIdx.y * 256 + tid; idx < TP * TP; idx += gridDim.y * 256) {
+      int i = idx / TP, j = idx % TP;
+      double sv = 0.0;
+      if (i < T && j < T) sv = 0.5 * (Sg[(size_t)i * T + j] + Sg[(size_t)j * T + i]);
+      Sk[idx] = sv;
+    }
+    return;
+  }
   for (int idx = blockIdx.y * 256 + tid; idx < TP * TP; idx += gridDim.y * 256) {
     int i = idx / TP, j = idx % TP;
     double av, sv = 0.0;
@@ -192,7 +228,7 @@ __global__ __launch_bounds__(256) void k_prep_final(PrepFinalArgs a) {
 }
 
 // ------------------------------------------------------------------ one launch behind the inverse (TP <= 128)
-// M', a', ||K~^-1||_inf and the routing flags from Z = L^-1, without Kinv, P or Q in global memory.  One workgroup per
+// M', a', ||K~^-1||_inf and the routing flags from Z = L^-1, without P or Q in global memory (Kinv: written, not read).  One workgroup per
 // (cluster k, tile pair I < J) recomputes what its two output tiles M'[I][J], M'[J][I] depend on:
 //   Kinv[:, I], Kinv[:, J] (block columns) and Kinv[I, :], Kinv[J, :] (block rows) from Z   - the chains of Kinv = Z^T Z,
 //   P[:, I] = S Kinv[:, I], P[:, J]                                                         - the chains of P = S Kinv,
@@ -216,6 +252,13 @@ struct PlanOpsArgs {
   int32_t* acc_list;
   int32_t* fb;
   unsigned* done;       // finished workgroups, of those that serve a diagonal block, of this launch; zero between launches
+  // Kinv of a cluster that k_prep_build found unchanged (reuse.same) is read from Kinv instead of being recomputed from Z; a cluster
+  // that is computed leaves its Kinv there, with what the next call's comparison needs (grid copy, jitter bits, status)
+  double* Kinv;         // [K][NB][NB] tiles (a, b) of K~^-1 in accumulator layout [lane][4]
+  PlanReuse reuse;
+  const double* xb;     // [T] the caller's grid
+  double* xb_copy;      // [TP]
+  const int32_t* info;  // the caller's status array (or NULL), written by the inverse launch
 };
 
 template <int NB>
@@ -273,28 +316,41 @@ __global__ __launch_bounds__(128 * NB) void k_plan_ops(PlanOpsArgs a) {
   const int q = wave / NB, wa = wave % NB;   // this wave's strip (0: I, 1: J) and tile index along it
   const int Bq = q ? J : I;
 
-  // ---- Kinv strips: tile (wa, Bq) of the block column and tile (Bq, wa) of the block row, from the same two operand streams
+  // ---- Kinv strips: tile (wa, Bq) of the block column and tile (Bq, wa) of the block row, from the same two operand streams.
+  // Tile (a, b) of Kinv is the chain mfma(Z[:, a], Z[:, b]) over ascending k-steps whoever runs it - as element of a block column
+  // (ccol of the wave with wa = a, Bq = b) or of a block row (crow of the wave with Bq = a, wa = b): ONE value per tile, which the
+  // workgroups of the pairs (B, B + 1) leave in a.Kinv, block column B each (the last pair also NB - 1): every tile written once.
+  // An unchanged cluster (same: uniform over the workgroup) takes its two tiles from there, bits as computed; (a, b) is never
+  // taken for (b, a).
+  const bool same = a.reuse.same[k] != 0;
   {
-    const double* Za = Z + 16 * wa + c;
-    const double* Zb = Z + 16 * Bq + c;
+    double* Kc = a.Kinv + (size_t)k * TP * TP + (wa * NB + Bq) * L::TILE + lane * 4;
     d4 ccol = (d4){0.0, 0.0, 0.0, 0.0}, crow = (d4){0.0, 0.0, 0.0, 0.0};
+    if (same) {
+      ccol = *reinterpret_cast<const d4*>(Kc);
+      crow = *reinterpret_cast<const d4*>(a.Kinv + (size_t)k * TP * TP + (Bq * NB + wa) * L::TILE + lane * 4);
+    } else {
+      const double* Za = Z + 16 * wa + c;
+      const double* Zb = Z + 16 * Bq + c;
 #pragma unroll
-    for (int k0 = 0; k0 < NK; k0 += TRIP) {
-      double za[TRIP], zb[TRIP];
+      for (int k0 = 0; k0 < NK; k0 += TRIP) {
+        double za[TRIP], zb[TRIP];
 #pragma unroll
-      for (int u = 0; u < TRIP; ++u) {
-        const int kk = 4 * (k0 + u) + g;
-        za[u] = Za[(size_t)kk * TP];
-        zb[u] = Zb[(size_t)kk * TP];
+        for (int u = 0; u < TRIP; ++u) {
+          const int kk = 4 * (k0 + u) + g;
+          za[u] = Za[(size_t)kk * TP];
+          zb[u] = Zb[(size_t)kk * TP];
+        }
+        // every load of the trip is in flight before its first MFMA: left alone, the scheduler trades them for occupancy this
+        // kernel cannot use and exposes one L2 latency per k-step
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < TRIP; ++u) {
+          ccol = mfma(za[u], zb[u], ccol);   // Kinv[16 wa + .][16 Bq + .]
+          crow = mfma(zb[u], za[u], crow);   // Kinv[16 Bq + .][16 wa + .]
+        }
       }
-      // every load of the trip is in flight before its first MFMA: left alone, the scheduler trades them for occupancy this
-      // kernel cannot use and exposes one L2 latency per k-step
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < TRIP; ++u) {
-        ccol = mfma(za[u], zb[u], ccol);   // Kinv[16 wa + .][16 Bq + .]
-        crow = mfma(zb[u], za[u], crow);   // Kinv[16 Bq + .][16 wa + .]
-      }
+      if (q == 0 ? dI : dJ) *reinterpret_cast<d4*>(Kc) = ccol;
     }
     *reinterpret_cast<d4*>(colS + (q * NB + wa) * L::TILE + lane * 4) = ccol;
 #pragma unroll
@@ -383,6 +439,17 @@ __global__ __launch_bounds__(128 * NB) void k_plan_ops(PlanOpsArgs a) {
   // the thread that counts, behind the barrier that orders the workgroup's atomic maxima before it (a fence in every wave of
   // every workgroup writes the L2 back thousands of times per launch: 108 us for this kernel at NB = 8).
   if (!dI) return;
+  // what the next call compares with, by pair (0, 1) of a cluster that was computed: the jitter's bits and the status beside its
+  // Kinv, and (cluster 0: a changed grid changes every cluster) the grid.  All of it, like the Kinv stores above, by workgroups
+  // that count below, so the valid marks are written behind it.
+  if (!same && I == 0) {
+    if (tid == 0) {
+      a.reuse.key_jit[k] = __double_as_longlong(a.scal[8 * k + 5]);
+      a.reuse.info[k] = a.info ? a.info[k] : 0;
+    }
+    if (k == 0)
+      for (int i = tid; i < TP; i += 128 * NB) a.xb_copy[i] = (i < T) ? a.xb[i] : 0.0;
+  }
   __syncthreads();
   if (tid == 0) {
     __threadfence();
@@ -395,6 +462,9 @@ __global__ __launch_bounds__(128 * NB) void k_plan_ops(PlanOpsArgs a) {
     a.fb[0] = 0;                    // fall-back list of k_pairs: its two counters start every plan state at zero
     a.fb[1 + PAIRS_FB_CAP] = 0;     // (a killed launch cannot leave them set)
     *a.done = 0u;
+    // every cluster is now either computed in full by this launch or was valid before it.  Written last: a launch that dies
+    // earlier leaves the clusters it was computing marked invalid (k_prep_build cleared them), and the next call computes them.
+    for (int kk = 0; kk < a.K; ++kk) a.reuse.valid[kk] = 1;
   }
 }
 
@@ -429,9 +499,9 @@ size_t plan_layout(hgp_pairs_plan* p, int T, int Ts_max, int K, char* base) {
   take(p->d_A, mat);   // K~ then L
   take(p->d_S, mat);
   take(p->d_Z, mat);
-  take(p->d_Kinv, mat);   // Kinv, P, Q: cooperative sizes only (TP <= 128: k_plan_ops keeps them in LDS; the areas keep their size)
-  take(p->d_P, mat);      // TP <= 128: first word = completion counter of k_plan_ops
-  take(p->d_Q, mat);
+  take(p->d_Kinv, mat);   // TP <= 128: Kinv by 16 x 16 tiles in accumulator layout, kept from call to call (k_plan_ops)
+  take(p->d_P, mat);      // P, Q: cooperative sizes only.  TP <= 128: first word of P = completion counter of k_plan_ops,
+  take(p->d_Q, mat);      // start of Q = PlanReuse; the areas keep their size
   take(p->d_Mp, mat);
   take(p->d_ap, (size_t)K * TP * sizeof(double));
   take(p->d_perm, (size_t)K * sizeof(int32_t));
@@ -507,6 +577,11 @@ int hgp_pairs_plan_create(hgp_pairs_plan** plan, int T, int Ts_max, int K, const
     delete p;
     return 1000 + (int)hipGetLastError();
   }
+  // no cluster has operators yet (PlanReuse: start of the Q area; K 24 bytes of the K TP^2 8 it holds)
+  if (!p->coop && hipMemset(p->d_Q, 0, (size_t)K * PlanReuse::BYTES_PER_CLUSTER) != hipSuccess) {
+    delete p;
+    return 1000 + (int)hipGetLastError();
+  }
   if (p->coop && hipMemset(p->d_eflags, 0, (p->nscr + 1) * sizeof(int32_t)) != hipSuccess) {
     delete p;
     return 1000 + (int)hipGetLastError();
@@ -529,17 +604,21 @@ int hgp_pairs_plan_update(hgp_pairs_plan* p, const double* x_basis, const double
   if (!p || !x_basis || !mean || !Sigma) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int K = p->K, T = p->T, TP = p->TP;
-  PrepArgs pa{x_basis, mean, Sigma, T, TP, K, p->d_theta, p->d_scal, p->d_A, p->d_S, p->d_xb};
+  // TP <= 128: the device decides per cluster whether K~, Z and Kinv of an earlier call still hold (k_prep_build compares the grid
+  // and the jitter bit for bit); the host never knows, and issues the same launches either way
+  const PlanReuse reuse = p->coop ? PlanReuse{} : plan_reuse(p);
+  PrepArgs pa{x_basis, mean, Sigma, T, TP, K, p->d_theta, p->d_scal, p->d_A, p->d_S, p->d_xb, reuse, info};
   hipLaunchKernelGGL(k_prep_build, dim3(K, 8), dim3(256), 0, st, pa);
   // Z = chol(K~)^{-1}  (the factor itself is not needed)
   // symmetric = 1: k_prep_build writes K~ from (x_i - x_j)^2, exactly symmetric
   InvArgs fa{p->d_A, TP, K, 0.0, 0.0, p->d_Z, info};
   fa.symmetric = 1;
+  fa.keep = reuse.same;   // a kept cluster's workgroups leave at once
   if (int rc = hgp_internal_chol_inverse(fa, p->NB, p->d_A, st)) return rc;   // TP > 128: K~ is overwritten by its factor
   if (!p->coop) {
-    // TP <= 128: M', a', ||K~^-1||_inf and the routing flags in one launch behind the inverse; Kinv, P, Q never reach memory
+    // TP <= 128: M', a', ||K~^-1||_inf and the routing flags in one launch behind the inverse; P, Q never reach memory
     PlanOpsArgs oa{p->d_Z, p->d_S, mean, p->d_scal, T, K, p->d_Mp, p->d_ap, p->acc_tol, p->d_acc_list, p->d_fb,
-                   reinterpret_cast<unsigned*>(p->d_P)};
+                   reinterpret_cast<unsigned*>(p->d_P), p->d_Kinv, reuse, x_basis, p->d_xb, info};
     if (int rc = dispatch_nb_wave(TP, [&](auto nb) { return launch_plan_ops<decltype(nb)::value>(oa, st); })) return rc;
     // clusters whose explicit operator would lose digits take the solve-based kernel: packed operands of L, Sigma
     int rc = hgp_internal_acc_prep(p, mean, /*flags_done=*/true, st);
