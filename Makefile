@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC   = hdpgpc_amd/csrc
 SRCS   = $(wildcard $(CSRC)/*.hip)
-HDR    = $(CSRC)/tile_f64.hpp $(CSRC)/hgp_internal.hpp $(CSRC)/panel_prod.hpp $(wildcard include/*.h)
+HDR    = $(CSRC)/tile_f64.hpp $(CSRC)/hgp_internal.hpp $(CSRC)/panel_prod.hpp $(CSRC)/hgp_segops.hpp $(wildcard include/*.h)
 OBJDIR = build/obj
 OBJS   = $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 LIB    = hdpgpc_amd/lib/libhdpgpc_hip.so
@@ -18,6 +18,8 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDR)
 # the ragged pair kernels are the templates of the rectangular units, instantiated in units of their own
 $(OBJDIR)/hgp_pairs_ragged.o: $(CSRC)/hgp_pairs.hip
 $(OBJDIR)/hgp_pairs_acc_ragged.o: $(CSRC)/hgp_pairs_acc.hip
+# and so is the streamed band kernel of the segment-operator store
+$(OBJDIR)/hgp_segops.o: $(CSRC)/hgp_pairs.hip
 
 $(LIB): $(OBJS)
 	mkdir -p hdpgpc_amd/lib

@@ -235,8 +235,18 @@ struct PairsRagArgs : PairsArgs {
 };
 template <class Args> constexpr bool pairs_ragged = std::is_base_of<PairsRagArgs, Args>::value;
 
+// The same for the streamed band kernel (hgp_loglik_pairs_segops_f64, hgp_segops.hip): segment n's length, band decision, E blocks
+// and K** tiles come from record n of the segment-operator store (hgp_segops.hpp), which k_segops has brought up to date on the
+// same stream; x and xb are not read, Ts is the row stride of y.  score_add is not read.
+struct PairsSegArgs : PairsArgs {
+  const double* store;   // record of segment 0 of this launch, this length-scale group
+};
+
 #ifdef HGP_STAMPS
 extern unsigned long long* hgp_internal_stamp_dev;
 #endif
 int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t st);
 int hgp_internal_pairs_fast_ragged(const PairsRagArgs& a, int NB, bool coop, hipStream_t st);
+// the mask-driven kernel alone, on the segments that a band kernel launched before it has put on the list a.fb (NB = 6, 8)
+int hgp_internal_pairs_listed(const PairsArgs& a, int NB, hipStream_t st);
+int hgp_internal_pairs_listed_ragged(const PairsRagArgs& a, int NB, hipStream_t st);

@@ -140,6 +140,28 @@ struct PairsBand {
   }
 };
 
+#ifdef HGP_PAIRS_SEGOPS_TU
+// the tile lists of the segment-operator store (hgp_segops.hpp) are exactly the blocks and tiles of the band pattern
+template <int NB>
+constexpr bool segops_pattern_ok() {
+  using SO = SegOps<NB>;
+  int em[NB] = {}, km[NB] = {};
+  for (int t = 0; t < SO::NE; ++t) {
+    const auto b = SO::e_block(t);
+    if (b.Kt < 0 || b.Kt >= NB || b.J < 0 || b.J >= NB || SO::e_slot(b.Kt, b.J) != t) return false;
+    em[b.J] |= 1 << b.Kt;
+  }
+  for (int k = 0; k < SO::NK; ++k) {
+    const auto b = SO::k_tile(k);
+    if (b.Kt < 0 || b.Kt > b.J || b.J >= NB || SO::k_slot(b.Kt, b.J) != SO::NE + k) return false;
+    km[b.J] |= 1 << b.Kt;
+  }
+  for (int J = 0; J < NB; ++J)
+    if (em[J] != PairsBand<NB>::emask(J) || km[J] != PairsBand<NB>::kmask(J)) return false;
+  return true;
+}
+#endif
+
 // Operand addresses of band_sweeps.  LDS pointers are kept as 32-bit addresses of the LDS address space, so that a compile-time
 // offset below LDS_IMM_SPAN becomes the 16-bit immediate of ds_read.
 typedef const __attribute__((address_space(3))) char* lds_cbytes;
@@ -304,7 +326,16 @@ constexpr int PAIRS_OCC2_NB = 4;   // largest NB built for two workgroups per CU
 // its length.  (Macros and not helper templates over the argument struct: handing `a` to a function by reference, though inlined,
 // left the rectangular generic kernels with other code than before - DESIGN 4.4e.  pairs_bad_len below is such a helper, but only
 // the ragged unit instantiates it.)
-#ifdef HGP_PAIRS_RAGGED_TU
+#if defined(HGP_PAIRS_SEGOPS_TU)
+// The streamed band kernel (hgp_segops.hip: this text a third time, k_pairs renamed k_pairs_seg, only <NB, true> instantiated):
+// the segment's length comes from its record of the segment-operator store, like everything else of the prologue.
+using KArgs = PairsSegArgs;
+#define PAIRS_SEG_REC(a, n) ((a).store + (size_t)(n) * SegOps<NB>::REC)
+#define PAIRS_SEG_LEN(a, n, ld) \
+  __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(PAIRS_SEG_REC(a, n) + SegOps<NB>::WORDS)[SegOps<NB>::W_LEN])
+#define PAIRS_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * 1.8378770664093453)   // as the ragged kernels
+#define PAIRS_SKIP_SEGMENTS(a, off) (void)0
+#elif defined(HGP_PAIRS_RAGGED_TU)
 using KArgs = PairsRagArgs;
 #define PAIRS_SEG_LEN(a, n, ld) __builtin_amdgcn_readfirstlane((a).seg_len[n])
 #define PAIRS_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * 1.8378770664093453)   // -0.5 Ts log(2 pi), the host's expression
@@ -357,10 +388,61 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
     }
   }
 
+#ifdef HGP_PAIRS_SEGOPS_TU
+  // Streamed prologue.  Nothing the prologue below builds depends on the cluster state: k_segops (hgp_segops.hip) has built it
+  // once per segment with the same expressions and keeps it in the segment-operator store, and this kernel copies the tiles to
+  // the places in E where the build would have put them.  From the d-phase on the two kernels are the same text.
+  static_assert(BAND && NB >= 6, "the streamed kernel is the band kernel");
+  using SO = SegOps<NB>;
+  static_assert(segops_pattern_ok<NB>(), "SegOps: the tile lists are not the band pattern");
+  const double* rec = PAIRS_SEG_REC(a, n);
+  const int sflag = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(rec + SO::WORDS)[SO::W_FLAG]);
+  if (sflag & SEG_BADLEN) {   // as the ragged kernels
+    for (int kk = a.kbeg + tid; kk < a.kend; kk += 64 * PW) {
+      const int kc = a.perm[kk];
+      if ((a.sel && a.sel[n] != kc) || a.scal[8 * kc + 7] != 0.0) continue;
+      pairs_bad_len(a, a.sel ? (size_t)n : (size_t)n * a.K + kc);
+    }
+    return;
+  }
+  if ((sflag & (SEG_VALID | SEG_BAND)) != (SEG_VALID | SEG_BAND)) {   // not the static pattern: the generic kernel builds its own E
+    if (tid == 0) {
+      const int slot = atomicAdd(&a.fb[0], 1);
+      if (slot < PAIRS_FB_CAP) a.fb[1 + slot] = n;
+    }
+    return;
+  }
+  for (int i = tid; i < TP; i += 64 * PW) ys[i] = (i < Ts) ? a.y[(size_t)n * row_ld + i] : 0.0;
+  if (tid < NB) {
+    amask[tid] = PairsBand<NB>::emask(tid);
+    kmask[tid] = PairsBand<NB>::kmask(tid);
+  }
+  {
+    // 128 lanes x 16 bytes per tile; every load of the lane is in flight before its first LDS write
+    constexpr int TPI = 64 * PW / 128, NPASS = (SO::NT + TPI - 1) / TPI;
+    const int sub = __builtin_amdgcn_readfirstlane(tid >> 7), e2 = 2 * (tid & 127);
+    d2 v[NPASS];
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p) {
+      const int t = TPI * p + sub;
+      if (t < SO::NT) v[p] = *reinterpret_cast<const d2*>(rec + SO::TILE * t + e2);
+    }
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p) {
+      const int t = TPI * p + sub;
+      if (t < SO::NT) {
+        const auto b = SO::lds_block(t);
+        *reinterpret_cast<d2*>(E + (16 * b.Kt + (e2 >> 4)) * TP + 16 * b.J + (e2 & 15)) = v[p];
+      }
+    }
+  }
+  __syncthreads();
+  constexpr bool kcache = true;
+#else
   // Padding (i >= Ts, k >= T) uses far-apart sentinels instead of bounds predicates: every kernel entry that
   // involves a padded point is then exp(-huge) = 0 by itself (all differences stay finite: < 3e152).
   for (int i = tid; i < TP; i += 64 * PW) {
-    xs[i] = (i < Ts) ? a.x[(size_t)n * row_ld + i] / a.ell : 1e150 * (double)(1 + i);
+    xs[i] =(i < Ts) ? a.x[(size_t)n * row_ld + i] / a.ell : 1e150 * (double)(1 + i);
     ys[i] = (i < Ts) ? a.y[(size_t)n * row_ld + i] : 0.0;
     xbs[i] = (i < T) ? a.xb[i] / a.ell : -1e150 * (double)(1 + i);
   }
@@ -476,6 +558,7 @@ __global__ __launch_bounds__((64 * pairs_waves<NB, BAND>()), ((NB <= PAIRS_OCC2_
       for (int r = 0; r < 4; ++r) E[(16 * Kh + g + 4 * r) * TP + 16 * J + c] = (hk[r] < PAIRS_CUT) ? ev[r] : 0.0;
     }
   }
+#endif   // HGP_PAIRS_SEGOPS_TU
 
   HGP_ACC(6);   // prologue: loads, E / K** build, masks (stamps build only)
   const int Kg = a.kend - a.kbeg;
@@ -1171,6 +1254,18 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
 #endif
 }
 
+#ifdef HGP_PAIRS_SEGOPS_TU
+// the streamed band kernel alone, one workgroup per segment of the launch: hgp_segops.hip chains it with k_segops and the generic kernel
+template <int NB>
+int launch_pairs_seg(const KArgs& a, hipStream_t st) {
+  constexpr int PWB = pairs_waves<NB, true>();
+  const size_t ldsb = PairsLds<NB, PWB>::BYTES;
+  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, true>), ldsb)) return rc_;
+  hipLaunchKernelGGL((k_pairs<NB, true>), dim3(a.N), dim3(64 * PWB), ldsb, st, a);
+  return launch_status();
+}
+}  // namespace
+#else
 template <int NB>
 int launch_pairs_cooph(const KArgs& a, hipStream_t st) {
   const size_t lds = PairsCoop<NB>::BYTES;
@@ -1218,7 +1313,25 @@ int launch_pairs(const KArgs& a0, hipStream_t st) {
   return 0;
 }
 
+// k_pairs<NB, false> alone on the list a.fb that a band kernel of another unit (hgp_segops.hip) has filled on this stream
+template <int NB>
+int launch_pairs_listed(const KArgs& a, hipStream_t st) {
+  const size_t lds = PairsLds<NB, pairs_waves<NB, false>()>::BYTES;
+  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, false>), lds)) return rc_;
+  hipLaunchKernelGGL((k_pairs<NB, false>), dim3(a.N), dim3(64 * WAVES), lds, st, a);
+  return launch_status();
+}
+
 }  // namespace
+
+#ifdef HGP_PAIRS_RAGGED_TU
+int hgp_internal_pairs_listed_ragged(const PairsRagArgs& a, int NB, hipStream_t st) {
+#else
+int hgp_internal_pairs_listed(const PairsArgs& a, int NB, hipStream_t st) {
+#endif
+  if (!a.fb) return -1;
+  return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs_listed<decltype(nb)::value>(a, st); });
+}
 
 // dispatch by padded size / kernel family (see hgp_loglik_pairs_f64)
 #ifdef HGP_PAIRS_RAGGED_TU
@@ -1229,3 +1342,4 @@ int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t s
   if (coop) return dispatch_nb_coop(16 * NB, [&](auto nb) { return launch_pairs_cooph<decltype(nb)::value>(a, st); });   // NB/2 waves per pair (CoopH)
   return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs<decltype(nb)::value>(a, st); });
 }
+#endif   // HGP_PAIRS_SEGOPS_TU

@@ -250,7 +250,17 @@ class PairsPlan:
 
     acc_tol selects, per cluster and on the device, between the two evaluations of cov_f (hgp_pairs_plan_set_accuracy):
     clusters whose accuracy_bound() exceeds it (ill-conditioned K~, e.g. the drivers' ini_lengthscale = 3.0) are scored
-    by the solve-based kernel (the reference's operation order, GPI.py:489-501); 0 = all clusters, < 0 = none."""
+    by the solve-based kernel (the reference's operation order, GPI.py:489-501); 0 = all clusters, < 0 = none.
+
+    Segment-operator store (hgp_loglik_pairs_segops_f64, padded sizes 96 and 128): a sampler scores the same segments against
+    changing cluster states, so loglik() keeps what the band kernel builds per segment - E blocks, K** tiles, band decision - in one
+    device buffer per plan, for the (N, row length, device) of the last call; the kernels compare each record's key with the
+    call's x, lengths and basis grid on the bits and rebuild what differs, so nothing is ever invalidated by hand.  The buffer
+    costs about 75 KiB per segment and length-scale group at size 128 (56 KiB at 96); a batch that would need more than
+    SEGOPS_MAX_BYTES (default 1 GiB: the headline batch of 2 048 segments takes 158 MB) is scored without a store, by the
+    entries that build the operators inside the pair kernel."""
+
+    SEGOPS_MAX_BYTES = 1 << 30
 
     def __init__(self, T, Ts_max, theta, device="cuda", acc_tol=1e-9):
         theta = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(-1, 3))
@@ -267,6 +277,7 @@ class PairsPlan:
                                                   _ptr(self._buf), nbytes), "pairs_plan_create")
         self.info = torch.zeros(self.K, dtype=torch.int32, device=device)
         self._routed = False
+        self._segops, self._segops_key = None, None
         self.set_accuracy(acc_tol)
 
     def set_accuracy(self, tol):
@@ -349,6 +360,16 @@ class PairsPlan:
         if bool(score) != self._score_out:
             _ffi.check(_ffi.lib.hgp_pairs_plan_set_score_output(self._h, int(bool(score))), "pairs_plan_set_score_output")
             self._score_out = bool(score)
+        need = _ffi.lib.hgp_pairs_segops_bytes(self._h, N, Ts)
+        if 0 < need <= self.SEGOPS_MAX_BYTES:
+            if self._segops_key != (N, Ts, str(dev)) or self._segops.numel() < need:
+                self._segops = None                      # the old store goes before the new one comes
+                self._segops = torch.zeros(need, dtype=torch.uint8, device=dev)
+                self._segops_key = (N, Ts, str(dev))
+            _ffi.check(_ffi.lib.hgp_loglik_pairs_segops_f64(self._h, _ptr(self._segops), need, _ptr(x), _ptr(y), N, Ts, _ptr(lengths),
+                                                            _ptr(first_noise), _ptr(sel), _ptr(quad), _ptr(logdet), _ptr(info),
+                                                            _stream()), "loglik_pairs_segops")
+            return quad, logdet, info
         if lengths is not None:
             _ffi.check(_ffi.lib.hgp_loglik_pairs_ragged_f64(self._h, _ptr(x), _ptr(y), N, Ts, _ptr(lengths), _ptr(first_noise),
                                                             _ptr(sel), _ptr(quad), _ptr(logdet), _ptr(info), _stream()),
@@ -363,6 +384,10 @@ class PairsPlan:
         loglik) Ts is each segment's own length."""
         q, _, info = self.loglik(x, y, first_noise, want_logdet=False, sel=sel, score=True, lengths=lengths)
         return q, info
+
+    def device_bytes(self):
+        """Device bytes this plan holds: its operator buffer and, once loglik() has made one, its segment-operator store."""
+        return self._buf.numel() + (self._segops.numel() if self._segops is not None else 0)
 
     def close(self):
         if self._h:
@@ -411,14 +436,14 @@ def plan_cache(T, Ts, K, theta, device):
     if plan is None:
         plan = PairsPlan(T, Ts, np.repeat(np.asarray(theta, dtype=np.float64)[None], int(K), 0), device=device)
     _PLANS[key] = plan                                     # most recently used = last
-    total = sum(p._buf.numel() for p in _PLANS.values())
+    total = sum(p.device_bytes() for p in _PLANS.values())
     for k in list(_PLANS):
         if total <= PLAN_CACHE_BYTES or k == key:
             break
         old = _PLANS.pop(k)
-        total -= old._buf.numel()
+        total -= old.device_bytes()
         old.close()
-        old._buf = None
+        old._buf = old._segops = old._segops_key = None
     return plan
 
 
