@@ -16,7 +16,10 @@ driver entry points -
 plus the small public helpers they and the drivers use (``LogLik``, ``_safe_exp``, ``weight_mean``, ``forward``,
 ``backward``, ``coupled_state_coef``, ``compute_trans_A/pi``, ``selected_gpmodels``).  NOT built (each raises
 NotImplementedError): ``include_sample(with_warp=True)`` (the reference's own path raises at its second beat), ``classify=True``,
-several leads online, static models, inducing points, ``bayesian_params=False``.  ``estimation_limit`` IS built (a scalar or one
+several leads online, inducing points, ``bayesian_params=False``.  ``model_type`` IS built for the offline drivers: 'static'
+(Gamma = 0: the cluster's template does not evolve), 'dynamic', or one value per initial cluster; clusters created later take the
+first entry (DESIGN.md sections 4.12, 4.20).  With a static cluster ``include_sample`` and ``include_batch(warp=True)`` raise
+NotImplementedError.  ``estimation_limit`` IS built (a scalar or one
 value per initial cluster: a cluster stops re-estimating its LDS parameters at that many members).
 As in the reference, a cluster that the OFFLINE loop rebuilds from a copy loses its limit (the reference's gpmodel_deepcopy
 builds the copy with default options): after include_batch only clusters that create_gp_default made are still limited.
@@ -108,10 +111,15 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         self.x_basis_ini = np.asarray(x_basis[0] if isinstance(x_basis, list) else x_basis, dtype=np.float64).reshape(-1, 1)
         self.x_basis = [self.x_basis_ini] * self.M
         self.x_basis_warp = x_basis_warp
-        self.model_type_def = _first(model_type)
-        if self.model_type_def != 'dynamic':
-            raise NotImplementedError("static models are not part of this build")
-        self.model_type = [self.model_type_def] * self.M
+        # GPI_HDP.py:48,149-150,190,308-316: 'static' or 'dynamic', one value or one per initial cluster; a cluster created later
+        # takes the first entry (set_default_options, GPI_HDP.py:172,483)
+        types = list(model_type) if isinstance(model_type, (list, tuple, np.ndarray)) else [model_type] * self.M
+        if len(types) != self.M:
+            raise ValueError("model_type: one value, or one per initial cluster")
+        for t in types:
+            if t not in ('static', 'dynamic'):
+                raise ValueError(f"model_type: 'static' or 'dynamic', not {t!r}")
+        self.model_type, self.model_type_def = [str(t) for t in types], str(types[0])
         self.ini_sigma_def, self.ini_gamma_def = float(_first(ini_sigma)), float(_first(ini_gamma))
         osc = _first(ini_outputscale)
         self.ini_outputscale_def = self.ini_sigma_def if osc is None else float(osc)      # GPI_HDP.py:157-158
@@ -152,23 +160,45 @@ class GPI_HDP(OfflineLoop, OnlineLoop):
         self.fmsg = self.margPrObs = None
         self.elbo_last = None
         self.snr_norm = None
-        self.gpmodels = [[self.create_gp_default(m, limits[m]) for m in range(self.M)] for _ in range(self.n_outputs)]
+        self.gpmodels = [[self.create_gp_default(m, limits[m], self.model_type[m]) for m in range(self.M)] for _ in range(self.n_outputs)]
         self.init_global_params(self.M)
 
     # ------------------------------------------------------------------ per-cluster models
-    def create_gp_default(self, i=None, estimation_limit=_DEFAULT):
+    def set_default_options(self, ini_sigma=_DEFAULT, ini_gamma=_DEFAULT, ini_outputscale=_DEFAULT, bound_sigma=_DEFAULT,
+                            bound_gamma=_DEFAULT, annealing=_DEFAULT, model_type=_DEFAULT, estimation_limit=_DEFAULT,
+                            free_deg_MNIV=_DEFAULT):
+        """GPI_HDP.py:468-488: what create_gp_default gives a cluster born from now on (the options this build carries, by
+        keyword; what is not passed stays)."""
+        if model_type is not _DEFAULT and model_type not in ('static', 'dynamic'):
+            raise ValueError(f"model_type: 'static' or 'dynamic', not {model_type!r}")
+        for name, v in (("ini_sigma_def", ini_sigma), ("ini_gamma_def", ini_gamma), ("ini_outputscale_def", ini_outputscale),
+                        ("bound_sigma_def", bound_sigma), ("bound_gamma_def", bound_gamma), ("annealing_def", annealing),
+                        ("model_type_def", model_type), ("estimation_limit_def", estimation_limit), ("free_deg_MNIV", free_deg_MNIV)):
+            if v is not _DEFAULT:
+                setattr(self, name, v)
+
+    def get_default_options(self):
+        """GPI_HDP.py:490-494, as a dict of the options set_default_options takes."""
+        return dict(ini_sigma=self.ini_sigma_def, ini_gamma=self.ini_gamma_def, ini_outputscale=self.ini_outputscale_def,
+                    bound_sigma=self.bound_sigma_def, bound_gamma=self.bound_gamma_def, annealing=self.annealing_def,
+                    model_type=self.model_type_def, estimation_limit=self.estimation_limit_def, free_deg_MNIV=self.free_deg_MNIV)
+
+    def create_gp_default(self, i=None, estimation_limit=_DEFAULT, model_type=_DEFAULT):
         """A fresh cluster model with the default priors (GPI_HDP.py:496-572, without the warping systems); its estimation limit
-        is the default one (the constructor alone hands the initial clusters their own)."""
+        and its type ('static': Gamma = 0, GPR_static; 'dynamic': GPR_dynamic) are the default ones (the constructor alone hands
+        the initial clusters their own)."""
         if estimation_limit is _DEFAULT:
             estimation_limit = self.estimation_limit_def
+        if model_type is _DEFAULT:
+            model_type = self.model_type_def
         kern = RBFWhiteKernel(self.ini_outputscale_def, float(self.ini_lengthscale), self.bound_sigma_def[0], device=self.device)
         gp = GPI_model(kern, self.x_basis_ini, annealing=self.annealing_def, bayesian=self.bayesian_params,
                        estimation_limit=estimation_limit, free_deg_MNIV=self.free_deg_MNIV, verbose=self.verbose)
         gp.noise_bounds = self.bound_sigma_def
-        cond = gp.GPR_dynamic(self.ini_gamma_def, self.ini_sigma_def)
-        gp.initial_conditions(ini_A=cond[0], ini_Gamma=cond[1], ini_C=cond[2], ini_Sigma=cond[3])
+        cond = gp.GPR_static(self.ini_sigma_def) if model_type == 'static' else gp.GPR_dynamic(self.ini_gamma_def, self.ini_sigma_def)
+        gp.initial_conditions(ini_A=cond[0], ini_Gamma=cond[1], ini_C=cond[2], ini_Sigma=cond[3], static=model_type == 'static')
         gp.theta_source = self
-        # the prior scales are gamma I / sigma I by construction (GPR_dynamic): spare return_LDS_param_likelihood its device test
+        # the prior scales are gamma I (0 for a static model) / sigma I by construction: spare return_LDS_param_likelihood its device test
         gp._memo_put("def_diag", (), True, (gp.Sigma_def, gp.Gamma_def))
         return gp
 

@@ -88,6 +88,44 @@ class matrix_normal_inv_wishart:
         return out[0]
 
 
+class inv_wishart:
+    """GPI_model.py:1417-1465 (container): the observation-noise distribution the reference gives a STATIC model at
+    initial_conditions (GPI_model.py:170-175) - C is fixed, only the scale of Sigma has a distribution.  Its posterior is the
+    online step's re-estimation of Sigma for a static cluster (GPI_model.py:1022-1043), which is not built; the offline passes
+    never update it (a static chain is the filter alone, GPI_model.py:377-406)."""
+    m_r_cov = None
+
+    def __init__(self, n0, scale, C_fixed):
+        self.n0, self.scale, self.C_fixed = n0, scale, C_fixed
+        self.m_mean = C_fixed          # (the reference's fit_kernel_params assigns this attribute, GPI_model.py:233)
+
+    def get_mean(self):
+        return self.C_fixed
+
+    def get_C(self):
+        return self.C_fixed
+
+    def get_scale(self, final=False):
+        return self.scale * self.n0 / (self.n0 - 2)
+
+    def set_scale(self, scale):
+        self.scale = scale
+
+    def posterior(self, *args, **kwargs):
+        raise NotImplementedError("inv_wishart.posterior (the online re-estimation of a static model's Sigma) is not built")
+
+
+def _dist_map(m, f):
+    """A distribution object of the same kind with f applied to its tensors (pickling, device moves)."""
+    if m is None:
+        return None
+    if isinstance(m, inv_wishart):
+        new = inv_wishart(m.n0, f(m.scale), f(m.C_fixed))
+        new.m_mean = f(m.m_mean)
+        return new
+    return matrix_normal_inv_wishart(f(m.m_mean), f(m.m_r_cov), m.n0, f(m.scale))
+
+
 class GPI_model:
     def __init__(self, kernel, x_basis, annealing=True, bayesian=False, cuda=True, inducing_points=False,
                  estimation_limit=None, free_deg_MNIV=5, verbose=False):
@@ -136,9 +174,7 @@ class GPI_model:
         for name in ("A_def", "Gamma_def", "C_def", "Sigma_def", "ini_cov_def", "x_basis"):
             d[name] = cpu(d.get(name))
         for name in ("internal_params", "observation_params"):
-            m = d.get(name)
-            if m is not None:
-                d[name] = matrix_normal_inv_wishart(cpu(m.m_mean), cpu(m.m_r_cov), m.n0, cpu(m.scale))
+            d[name] = _dist_map(d.get(name), cpu)
         d["theta_owner_fixed"] = getattr(self.theta_source, "fixed_theta", None)
         return d
 
@@ -161,9 +197,7 @@ class GPI_model:
         for name in ("A_def", "Gamma_def", "C_def", "Sigma_def", "ini_cov_def", "x_basis"):
             setattr(self, name, mv(getattr(self, name)))
         for name in ("internal_params", "observation_params"):
-            m = getattr(self, name)
-            if m is not None:
-                setattr(self, name, matrix_normal_inv_wishart(mv(m.m_mean), mv(m.m_r_cov), m.n0, mv(m.scale)))
+            setattr(self, name, _dist_map(getattr(self, name), mv))
 
     # ------------------------------------------------------------------ state (a12)
     def cond_to_torch(self, x):
@@ -420,8 +454,8 @@ class GPI_model:
         eye = self._eye()
         return eye.clone(), torch.zeros_like(eye), eye.clone(), (0.25 if ini_Sigma is None else ini_Sigma) * eye
 
-    def initial_conditions(self, ini_mean=None, ini_cov=None, ini_A=None, ini_Gamma=None, ini_C=None, ini_Sigma=None):
-        """GPI_model.py:115-175."""
+    def initial_conditions(self, ini_mean=None, ini_cov=None, ini_A=None, ini_Gamma=None, ini_C=None, ini_Sigma=None, static=None):
+        """GPI_model.py:115-175.  static: the caller knows whether ini_Gamma is zero (None: it is looked at, one device round trip)."""
         K = self.gp.kernel(self.x_basis, self.x_basis)
         m0 = self.compute_mean() if ini_mean is None else self.cond_to_torch(ini_mean).reshape(-1, 1)
         c0 = K if ini_cov is None else self.cond_to_torch(ini_cov)
@@ -435,7 +469,10 @@ class GPI_model:
         self.A_def, self.Gamma_def, self.C_def, self.Sigma_def = ini_A, ini_Gamma, ini_C, ini_Sigma
         self.indexes, self.N, self.x_train, self.y_train = [], 0, [], []
         self.internal_params = matrix_normal_inv_wishart(ini_A, None, self.free_deg_MNIV, ini_Gamma)
-        self.observation_params = matrix_normal_inv_wishart(ini_C, None, self.free_deg_MNIV, ini_Sigma)
+        if bool(torch.all(ini_Gamma == 0)) if static is None else static:        # a static model (GPI_model.py:172-175); reinit_LDS gives every model an MNIW, as there
+            self.observation_params = inv_wishart(self.free_deg_MNIV, ini_Sigma, ini_C)
+        else:
+            self.observation_params = matrix_normal_inv_wishart(ini_C, None, self.free_deg_MNIV, ini_Sigma)
 
     def fit_kernel_params(self, x_train, y, alpha_ini, gamma_ini, valid=True):
         """GPI_model.py:207-241.  The gpytorch fit (GPI.py:610-770) is either replaced by ``self.fixed_theta`` (what the

@@ -17,10 +17,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HGP_LIB") or os.path.join(_HERE, "lib", "libhdpgpc_hip.so")
 _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")                          # where csrc/hgp_internal.hpp includes them from
 # (exports attribute of this module, header file): the main header first, then the kernel fit, the MDS embedding, ragged pair
-# batches, ragged projection and the pair path with a segment-operator store
+# batches, ragged projection, the pair path with a segment-operator store and the static filter chain
 HEADERS = (("EXPORTS", "hdpgpc_hip.h"), ("FIT_EXPORTS", "hdpgpc_hip_fit.h"), ("MDS_EXPORTS", "hdpgpc_hip_mds.h"),
            ("RAGGED_EXPORTS", "hdpgpc_hip_ragged.h"), ("PROJECT_EXPORTS", "hdpgpc_hip_project.h"),
-           ("SEGOPS_EXPORTS", "hdpgpc_hip_segops.h"))
+           ("SEGOPS_EXPORTS", "hdpgpc_hip_segops.h"), ("STATIC_EXPORTS", "hdpgpc_hip_static.h"))
 HEADER_PATH = os.path.join(_INCLUDE, HEADERS[0][1])
 
 c_dp = ctypes.c_void_p  # device pointers travel as integers
@@ -63,11 +63,12 @@ def _struct(name, c_name):
 
 
 lib, _exports, _structs, _defines = _load()
-globals().update(_exports)          # EXPORTS, FIT_EXPORTS, MDS_EXPORTS, RAGGED_EXPORTS, PROJECT_EXPORTS, SEGOPS_EXPORTS: sorted names, one list per header
+globals().update(_exports)          # EXPORTS, FIT_EXPORTS, MDS_EXPORTS, RAGGED_EXPORTS, PROJECT_EXPORTS, SEGOPS_EXPORTS, STATIC_EXPORTS: sorted names, one list per header
 FIT_STATE_DOUBLES, MDS_STATE_DOUBLES = _defines["HGP_FIT_STATE_DOUBLES"], _defines["HGP_MDS_STATE_DOUBLES"]
 ABI_VERSION, MAX_T_WAVE, MAX_T_COOP = (_defines[k] for k in ("HGP_ABI_VERSION", "HGP_MAX_T_WAVE", "HGP_MAX_T_COOP"))
 GemmItem, ChainGatherDesc = _struct("GemmItem", "hgp_gemm_item"), _struct("ChainGatherDesc", "hgp_chain_gather_desc")
 ChainFinishDesc, CopyItem = _struct("ChainFinishDesc", "hgp_chain_finish_desc"), _struct("CopyItem", "hgp_copy_item")
+StaticChainDesc = _struct("StaticChainDesc", "hgp_static_chain_desc")
 
 
 class HgpError(RuntimeError):

@@ -18,8 +18,11 @@ basis length T <= 128 in lock-step with the SAME number of launches per member s
 Every other chain runs the same step as a group of one (n_chains = 1): a chain without a partner of its length, and every chain
 with 128 < T <= 256, whose inversions are the cooperative inverse-only kernels with Z rhs one more list level behind each (the
 batch size picks the inversion kernel, so these chains are not batched).  GPI_model.full_pass_weighted is ``run`` over one job.
-Results are bit-identical to running the chains one after the other.  Chains the graphed step does not cover (static models,
-soft members, irregular grids, T > 256, fewer than 4 members) take GPI_model._full_pass_eager.  A chain with an estimation
+Results are bit-identical to running the chains one after the other.  A STATIC model (Gamma = 0) has no pair smoother and no
+parameter update: its chain is the filter alone, and every such chain with h = 1 members on the basis grid and T <= 128 - of any
+length - goes into ONE hgp_static_chain_steps_f64 launch per basis length (_run_static; one workgroup per chain walks its members).
+Chains neither step covers (soft members, irregular grids, T > 256, dynamic chains of fewer than 4 members, static ones with
+T > 128) take GPI_model._full_pass_eager.  A chain with an estimation
 limit runs the full step up to the limit and the frozen step (finish flag 8: no MNIW update, the parameters copied forward)
 behind it, as two consecutive runs (_run_group).
 
@@ -30,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _ffi, ops
-from .member_step import Chain, finish_desc, gather_desc, member_step, shared_buffers, upload_descs, ws_size
+from .member_step import Chain, bind_static, finish_desc, gather_desc, member_step, shared_buffers, upload_descs, ws_size
 
 f64 = torch.float64
 UNROLL = 8                                   # member steps per captured hipGraph
@@ -58,6 +61,24 @@ def _graphable(job):
     return bool(torch.equal(X2[a], gp.x_basis.reshape(1, -1).expand(len(a), -1)))
 
 
+def _on_basis_h1(job):
+    """Every active member has h = 1 and sits on the basis grid."""
+    gp, a = job.gp, job.active
+    if not bool(torch.all(job.resp[a] == 1.0)):
+        return False
+    X2 = job.x[..., 0] if job.x.ndim == 3 else job.x
+    return bool(torch.equal(X2[a], gp.x_basis.reshape(1, -1).expand(len(a), -1)))
+
+
+def _static_fused(job):
+    """The fused static filter chain covers: static model, h = 1 for every active member, the members on the basis grid,
+    T <= 128; any number of members."""
+    gp = job.gp
+    if gp.x_basis.shape[0] > _ffi.MAX_T_WAVE or gp._is_dynamic():
+        return False
+    return _on_basis_h1(job)
+
+
 class _MergedLevels:
     """The level lists of chains that advance together, merged chain-major: level l has per[l] items per chain."""
 
@@ -75,16 +96,21 @@ def run(jobs):
     for j in jobs:
         j.x, j.y = j.gp.cond_to_torch(j.x), j.gp.cond_to_torch(j.y)
     by_T = {}                                          # chains advance in lock-step only with chains of their own basis length
+    static_by_T = {}                                   # static chains: one launch per basis length
     for j in jobs:
         if not len(j.active):
             j.out = j.prev
         elif _graphable(j):
             by_T.setdefault(int(j.gp.x_basis.shape[0]), []).append(j)
+        elif _static_fused(j):
+            static_by_T.setdefault(int(j.gp.x_basis.shape[0]), []).append(j)
         else:
             j.out = j.gp._full_pass_eager(j.x, j.y, j.resp, j.active)
     for T, g in by_T.items():
         for group in ([g] if T <= _ffi.MAX_T_WAVE and len(g) >= 2 else [[j] for j in g]):
             _run_group(group)
+    for T, g in static_by_T.items():
+        _run_static(g, T)
     return [j.out for j in jobs]
 
 
@@ -153,6 +179,56 @@ def _run_group(jobs):
         gp._check_pending()
         j.out = (gp.compute_sq_err_all(j.x, j.y), gp.compute_q_lat_all(j.x))
         del j.ch
+
+
+def _run_static(jobs, T):
+    """The filter chains of static models (all of basis length T <= 128), every member of every chain, in ONE launch
+    (hgp_static_chain_steps_f64), then commit and scores.  What GPI_model._full_pass_eager does for a static model, member by
+    member: include_weighted_sample(h = 1) - the kernel fit before the first member of a model that has none, then the Kalman
+    update from the last smoothed state (for a static model: the last filtered one) - and nothing else."""
+    dev = jobs[0].gp.device
+    descs, keep = [], []
+    for j in jobs:
+        gp = j.gp
+        gp._check_pending()
+        idx0 = j.active[0]
+        if gp.N == 0 and not gp.fitted:                    # include_weighted_sample, GPI_model.py:361-363
+            gp.fit_kernel_params(j.x[idx0].reshape(-1, 1), j.y[idx0], gp.Sigma[-1], gp.Gamma[-1], valid=True)
+        # GPI.py:136-139: a prior covariance that is the kernel Gram itself takes the first-step branch (only a model's first member can)
+        k = gp.gp.kernel
+        first = gp.N == 0 and bool(torch.equal(gp.cov_f_sm[-1], k(gp.x_basis, gp.x_basis)))
+        L, n = len(gp.f_star_sm), len(j.active)
+        Fsm = torch.empty((L + n, T, 1), dtype=f64, device=dev)
+        Psm = torch.empty((L + n, T, T), dtype=f64, device=dev)
+        Fsm[:L] = gp.f_star_sm.stack().reshape(L, T, 1)
+        Psm[:L] = gp.cov_f_sm.stack()
+        j.st = (Fsm, Psm, L, torch.zeros(1, dtype=torch.int32, device=dev))
+        Y = (j.y[..., 0] if j.y.ndim == 3 else j.y).reshape(j.y.shape[0], -1).contiguous()
+        ops_in = (gp.A[-1].contiguous(), gp.C[-1].contiguous(), gp.Sigma[-1].contiguous(), Y,
+                  torch.tensor([L - 1], dtype=torch.int64, device=dev), ops.to_dev(np.asarray(j.active, dtype=np.int64), torch.int64, dev))
+        keep.append(ops_in)
+        A, C, Sigma, Y, pos, y_idx = ops_in
+        descs.append(ops.static_chain_desc(A, C, Sigma, Fsm, Psm, pos, Y, y_idx, j.st[3], n, L - 1, first=first,
+                                           white=(k.constant_value + k.noise_level) - k.constant_value))
+    n_max = max(len(j.active) for j in jobs)
+    ddev = upload_descs(descs, dev)
+    ops.static_chain_steps(ddev, len(jobs), T, n_max)
+    infos = torch.cat([j.st[3] for j in jobs]).tolist()    # waits for the launch: the descriptors and what they point to may go
+    del keep, ddev
+    for j, info in zip(jobs, infos):
+        gp = j.gp
+        Fsm, Psm, L, _ = j.st
+        bind_static(gp, Fsm, Psm, L)
+        for idx in j.active:
+            gp.indexes.append(int(idx))
+            gp.x_train.append(j.x[idx].reshape(-1, 1))
+            gp.y_train.append(j.y[idx].reshape(-1, 1))
+        gp.N += len(j.active)
+        gp.static_chain_calls = getattr(gp, "static_chain_calls", 0) + 1
+        del j.st
+        if info != 0:        # torch.linalg of the reference would have raised at that member
+            raise torch.linalg.LinAlgError("posterior: the input is not positive-definite")
+        j.out = (gp.compute_sq_err_all(j.x, j.y), gp.compute_q_lat_all(j.x))
 
 
 def _advance(jobs, lengths, T, frozen):

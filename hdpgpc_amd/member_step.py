@@ -211,6 +211,32 @@ class Chain:
                          f_sm_prev=f_sm_prev, P_sm_prev=P_sm_prev, i4=shared["i4"][c], i2=shared["i2"][c])
 
 
+def _same_entries(a, b):
+    """Do two per-step lists hold the very same tensors (one stack behind both, or the same objects entry by entry)?"""
+    if len(a) != len(b):
+        return False
+    sa, sb = getattr(a, "stacked", lambda: None)(), getattr(b, "stacked", lambda: None)()
+    if sa is not None or sb is not None:
+        return sa is sb
+    return all(x is y for x, y in zip(a, b))
+
+
+def bind_static(gp, Fsm, Psm, L):
+    """bind_model's sibling for a STATIC model whose filter chain (hgp_static_chain_steps_f64) appended rows L .. to the stacks
+    Fsm [rows,T,1] and Psm [rows,T,T], which hold the model's smoothed lists in their first L rows.  A static model has no
+    smoother: the reference appends the same tensors to the filtered and the smoothed lists (GPI_model.py:317), so the new rows
+    serve both.  Where the two lists held the same entries before (always, unless somebody assigned to one of them) one stack
+    serves both lists; otherwise the filtered lists keep their own first L rows.  The four parameter lists keep their length and
+    the MNIW objects are not touched."""
+    for filt, sm, st in (("f_star", "f_star_sm", Fsm), ("cov_f", "cov_f_sm", Psm)):
+        old_f, old_sm = getattr(gp, filt), getattr(gp, sm)
+        shared = _same_entries(old_f, old_sm)
+        if not shared:
+            own = torch.cat([torch.stack(list(old_f)).reshape((L,) + tuple(st.shape[1:])), st[L:]])
+        setattr(gp, sm, StepList(st))
+        setattr(gp, filt, StepList(st if shared else own))
+
+
 def gather_desc(ch):
     """hgp_chain_gather_desc of a chain; the step reads observation row pos - y_row0 of its Y (y_row0 < 0: Y is the observation
     itself)."""

@@ -805,6 +805,8 @@ class OfflineLoop:
             warp = with_warp
         if self.reduce_outputs:
             raise NotImplementedError("reduce_outputs is not part of this build")
+        if warp and 'static' in [self.model_type_def] + list(self.model_type):
+            raise NotImplementedError("include_batch(warp=True) with static models (model_type='static') is not built")
         self.warp = bool(warp)
         self._drop_online_pools()                 # the loop replaces the cluster models
         self._log(f"------ HDP Hyperparameters ------\ngamma: {self.gamma}\ntransAlpha: {self.transAlpha}\n"

@@ -201,6 +201,12 @@ class OnlineLoop:
         _tick("commit")
 
     def _online_guards(self, with_warp, classify, minibatch):
+        if self.model_type_def == 'static' or any(t == 'static' for t in self.model_type):
+            # the reference's online static branch re-estimates Sigma through inv_wishart.posterior (GPI_model.py:1022-1043,
+            # 1084-1110): a step of its own, not the dynamic one with Gamma = 0
+            raise NotImplementedError("include_sample with static models (model_type='static') is not built: the online step "
+                                      "covers dynamic clusters only; static models run offline (include_batch, "
+                                      "reload_model_from_labels, cluster_new_batch)")
         if with_warp:
             # The reference itself cannot run this path: with one cluster (the second beat of any run) compute_warp_y's greedy
             # branch takes torch.max of an empty tensor (GPI_HDP.py:3313, liks[:-1] with M = 1) and raises RuntimeError -

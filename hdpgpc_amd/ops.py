@@ -749,6 +749,52 @@ def project_ragged(x, y, lengths, xb, c, ell, jitter=1e-4):
     return yp, info
 
 
+def static_chain_ws_doubles(B, T):
+    """hgp_static_chain_ws_bytes of include/hdpgpc_hip_static.h, in doubles."""
+    return _ffi.lib.hgp_static_chain_ws_bytes(B, T) // 8
+
+
+def static_chain_desc(A, C, Sigma, Fs, Ps, pos, Y, y_idx, info, n, pos0, first=False, white=0.0, flags=0):
+    """hgp_static_chain_desc of one chain (include/hdpgpc_hip_static.h): device tensors A, C, Sigma [T,T], the stacks Fs [rows,T]
+    and Ps [rows,T,T] with rows >= pos0 + n + 1, pos [1] int64, Y [*,T], y_idx [n] int64, info [1] int32.  The tensors must outlive
+    the calls that read the descriptor."""
+    T = A.shape[-1]
+    for t, name, shape in ((A, "A", (T, T)), (C, "C", (T, T)), (Sigma, "Sigma", (T, T))):
+        if tuple(_dev64(t, name).shape) != shape:
+            raise ValueError(f"static_chain_desc: {name} must be [T, T]")
+    Fs, Ps, Y = _dev64(Fs, "Fs"), _dev64(Ps, "Ps"), _dev64(Y, "Y")
+    rows = Ps.shape[0]
+    if Fs.numel() != rows * T or tuple(Ps.shape[1:]) != (T, T) or Y.dim() != 2 or Y.shape[1] != T:
+        raise ValueError("static_chain_desc: Fs must be [rows, T], Ps [rows, T, T] and Y [*, T]")
+    if not 0 <= pos0 or pos0 + n + 1 > rows:
+        raise ValueError("static_chain_desc: the stacks need pos0 + n + 1 rows")
+    for t, name, dt, cnt in ((pos, "pos", torch.int64, 1), (y_idx, "y_idx", torch.int64, n), (info, "info", torch.int32, 1)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= cnt):
+            raise TypeError(f"static_chain_desc: {name} must be a contiguous {dt} tensor on the GPU")
+    d = _ffi.StaticChainDesc()
+    d.A, d.C, d.Sigma, d.Fs, d.Ps, d.pos, d.Y, d.y_idx, d.info = (t.data_ptr() for t in (A, C, Sigma, Fs, Ps, pos, Y, y_idx, info))
+    d.white, d.pos0, d.n, d.first, d.flags, d.reserved = float(white), int(pos0), int(n), int(bool(first)), int(flags), 0
+    return d
+
+
+def static_chain_steps(descs_dev, B, T, max_steps):
+    """Up to max_steps members of each of the B static filter chains whose descriptors (static_chain_desc, uploaded as one array:
+    member_step.upload_descs) lie in descs_dev - ONE launch (hgp_static_chain_steps_f64); T <= 128, NotImplementedError above.
+    Nothing is synchronised; the workspace is kept per stream (static_chain_release drops it)."""
+    if not (torch.is_tensor(descs_dev) and descs_dev.is_cuda and descs_dev.dtype == torch.uint8 and descs_dev.is_contiguous()
+            and descs_dev.numel() >= B * ctypes.sizeof(_ffi.StaticChainDesc)):
+        raise TypeError("static_chain_steps: descs_dev must hold B descriptors as bytes on the GPU")
+    if B == 0 or max_steps == 0:
+        return
+    need = int(_ffi.lib.hgp_static_chain_ws_bytes(B, T))
+    ws, stream = _workspace("static_chain_steps", descs_dev.device, max(need, 8))
+    _ffi.check(_ffi.lib.hgp_static_chain_steps_f64(_ptr(descs_dev), int(B), int(T), int(max_steps), _ptr(ws), need, stream),
+               "static_chain_steps")
+
+
+static_chain_release = _release_of("static_chain_steps")
+
+
 def rts_chain(J, P, AM, M, Cv):
     """Sequential part of the RTS smoother for all steps in one launch (in place on M [n,T] and Cv [n,T,T]); T <= 96."""
     n, T = M.shape[0], Cv.shape[1]
