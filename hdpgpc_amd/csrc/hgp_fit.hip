@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void k_fit_update(FitArgs a) {
   {
 #pragma clang fp contract(off)   // the host loop's operation order, no fused multiply-add
     const double glog0 = 0.5 * red[0][0], glog1 = 0.5 * red[1][0], glog2 = 0.5 * noise * red[2][0];
-    const double val = -0.5 * quad - 0.5 * logdet - 0.5 * T * 1.8378770664093453;   // log(2 pi)
+    const double val = -0.5 * quad - 0.5 * logdet - 0.5 * T * LOG_2PI;
     const double loss = -val / T;
     if (a.info[b] != 0) {
       a.status[b] = -1;

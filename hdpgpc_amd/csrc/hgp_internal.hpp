@@ -11,6 +11,7 @@
 #include "../../include/hdpgpc_hip.h"
 
 constexpr int WAVES = 4;  // waves per workgroup of the one-wave-per-item kernels: one per SIMD of a CU
+constexpr double LOG_2PI = 1.8378770664093453;   // log(2 pi): a Gaussian log-density of Ts points carries -0.5 Ts LOG_2PI
 
 static inline int launch_status() {
   hipError_t e = hipGetLastError();
@@ -180,12 +181,6 @@ void hgp_internal_sub_batched(const double* A, const double* B, long sA, long sB
 // hgp_pairs_acc.hip
 // flags_done: the plan update has written the routing flags already (k_plan_ops, TP <= 128)
 int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, bool flags_done, hipStream_t st);
-int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts, const double* first_noise,
-                           const int32_t* sel, double* out_quad, double* out_logdet, int32_t* out_info, hipStream_t st);
-// ragged form (hgp_pairs_acc_ragged.hip): rows ld apart, seg_len[n] real points in row n
-int hgp_internal_pairs_acc_ragged(const hgp_pairs_plan* p, const double* x, const double* y, int N, int ld, const int32_t* seg_len,
-                                  const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet,
-                                  int32_t* out_info, hipStream_t st);
 size_t hgp_internal_acc_bytes(int TP, int K, size_t* sizes /*[6]*/);
 
 // hgp_matlik_coop.hip: the same two terms for 128 < T <= HGP_MAX_T_COOP, one workgroup per item (factor once, packed factor in ws)
@@ -245,8 +240,56 @@ struct PairsSegArgs : PairsArgs {
 #ifdef HGP_STAMPS
 extern unsigned long long* hgp_internal_stamp_dev;
 #endif
-int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t st);
-int hgp_internal_pairs_fast_ragged(const PairsRagArgs& a, int NB, bool coop, hipStream_t st);
-// the mask-driven kernel alone, on the segments that a band kernel launched before it has put on the list a.fb (NB = 6, 8)
+
+// What a caller of hgp_loglik_pairs_f64, hgp_loglik_pairs_ragged_f64 or hgp_loglik_pairs_segops_f64 passes
+struct PairsCall {
+  const double* x;
+  const double* y;
+  int N, ld;                  // rows of x and y lie ld apart
+  const int32_t* seg_len;     // [N] or NULL: every row has ld points
+  const double* first_noise;
+  const int32_t* sel;
+  double* out_quad;
+  double* out_logdet;
+  int32_t* out_info;
+};
+// HGP_PAIRS_GENERIC=1: the mask-driven sweeps for every segment (A/B runs and tests)
+static inline bool pairs_generic_forced() { return env_on("HGP_PAIRS_GENERIC"); }
+
+// The arguments of segments [off, off + n) of a batch, given those of the whole batch: everything per segment moves
+template <class Args> static inline Args pairs_slice(Args a, int off, int n) {
+  const size_t oo = a.sel ? (size_t)off : (size_t)off * a.K;
+  a.N = n;
+  a.x += (size_t)off * a.Ts;
+  a.y += (size_t)off * a.Ts;
+  if (a.first_noise) a.first_noise += oo;
+  if (a.sel) a.sel += off;
+  a.out_quad += oo;
+  if (a.out_logdet) a.out_logdet += oo;
+  if (a.out_info) a.out_info += oo;
+  if constexpr (pairs_ragged<Args>) a.seg_len += off;
+  return a;
+}
+
+// The one driver behind the three entries (hgp_plan.hip): every launch of a call, in order.  store: the caller's segment-operator
+// store, checked by the entry, or NULL: the band kernel builds its own prologue.  Sizes that no kernel serves: -2.
+int hgp_internal_pairs_score(const hgp_pairs_plan* p, const PairsCall& c, void* store, hipStream_t st);
+
+// What the driver launches, one function per launch step and one overload per argument type: hgp_pairs.hip defines those of
+// PairsArgs, hgp_pairs_ragged.hip those of PairsRagArgs.  a.N segments, one workgroup each (cooperative: one per pair).
+// - every segment by one kernel, no list: the cooperative kernel, or the mask-driven one (NB < 6, generic forced)
+int hgp_internal_pairs_all(const PairsArgs& a, int NB, bool coop, hipStream_t st);
+int hgp_internal_pairs_all(const PairsRagArgs& a, int NB, bool coop, hipStream_t st);
+// - the band kernel (NB = 6, 8): segments that are not of the static pattern go on the list a.fb
+int hgp_internal_pairs_band(const PairsArgs& a, int NB, hipStream_t st);
+int hgp_internal_pairs_band(const PairsRagArgs& a, int NB, hipStream_t st);
+// - the mask-driven kernel on the segments that the band step before it has put on the list a.fb; it hands the list back empty
 int hgp_internal_pairs_listed(const PairsArgs& a, int NB, hipStream_t st);
-int hgp_internal_pairs_listed_ragged(const PairsRagArgs& a, int NB, hipStream_t st);
+int hgp_internal_pairs_listed(const PairsRagArgs& a, int NB, hipStream_t st);
+// - the band step from the store (hgp_segops.hip): k_segops brings the records of a's segments up to date, k_pairs_seg streams
+//   them.  Record `first` of the store ([length-scale group][segment]) is that of a's first segment; seg_len belongs to a's
+//   segments too, or is NULL.
+int hgp_internal_pairs_streamed(const PairsArgs& a, const int32_t* seg_len, void* store, size_t first, int NB, hipStream_t st);
+// - the solve-based kernel over the whole batch (hgp_pairs_acc.hip; std::true_type: its ragged form, hgp_pairs_acc_ragged.hip)
+int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const PairsCall& c, std::false_type, hipStream_t st);
+int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const PairsCall& c, std::true_type, hipStream_t st);

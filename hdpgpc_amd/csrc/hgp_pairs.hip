@@ -1,11 +1,17 @@
 // a2 + a5, the per-pair kernels of hgp_loglik_pairs_f64 (explicit-operator evaluation of cov_f): k_pairs<NB> (T <= 128, one
 // wavefront per pair) and k_pairs_cooph<NB> (NB/2 waves per pair) for 128 < T <= 256.  (The 4-wave cooperative kernel of round 1,
 // k_pairs_coop, 1.28x slower, was removed in round 3.)
-// The plan (per-cluster operators) and the C-ABI live in hgp_plan.hip; the solve-based kernel in hgp_pairs_acc.hip.
-// This text is compiled twice.  As hgp_pairs.hip it gives the rectangular kernels (KArgs = PairsArgs: every row of x / y has Ts
-// points).  hgp_pairs_ragged.hip includes it with HGP_PAIRS_RAGGED_TU defined and the kernels renamed k_pairs_rag /
-// k_pairs_cooph_rag: KArgs = PairsRagArgs, a length per segment (hgp_loglik_pairs_ragged_f64).  The few places where the two
-// differ go through the PAIRS_* macros above k_pairs; for PairsArgs they expand to what stood there before.
+// The plan (per-cluster operators), the C-ABI and the driver that states a call's launches and their order
+// (hgp_internal_pairs_score) live in hgp_plan.hip; the solve-based kernel in hgp_pairs_acc.hip.
+// This text is compiled three times.  As hgp_pairs.hip it gives the rectangular kernels (KArgs = PairsArgs: every row of x / y has
+// Ts points).  hgp_pairs_ragged.hip includes it with HGP_PAIRS_RAGGED_TU defined and the kernels renamed k_pairs_rag /
+// k_pairs_cooph_rag: KArgs = PairsRagArgs, a length per segment (hgp_loglik_pairs_ragged_f64).  hgp_segops.hip includes it with
+// HGP_PAIRS_SEGOPS_TU defined and the kernel renamed k_pairs_seg: KArgs = PairsSegArgs, the band kernel with its prologue
+// streamed from the segment-operator store.  The few places where the kernels differ go through the PAIRS_* macros above
+// k_pairs; for PairsArgs they expand to what stood there before.
+// Host side, a unit holds one launcher per launch step and nothing else: hgp_internal_pairs_all / _band / _listed at the end of
+// this text are overloads on the unit's own KArgs, each ONE launch of the a.N segments it is handed.  Which steps a call takes,
+// and the walk over a batch in slices of PAIRS_FB_CAP segments, is the driver's business.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -325,7 +331,8 @@ constexpr int PAIRS_OCC2_NB = 4;   // largest NB built for two workgroups per CU
 // the iso log-determinant, the score offset - takes it from PAIRS_SEG_LEN, so a ragged row has the bits of a rectangular call of
 // its length.  (Macros and not helper templates over the argument struct: handing `a` to a function by reference, though inlined,
 // left the rectangular generic kernels with other code than before - DESIGN 4.4e.  pairs_bad_len below is such a helper, but only
-// the ragged unit instantiates it.)
+// the ragged unit instantiates it.)  The macros are device text only: the host moves the lengths with the other per-segment
+// pointers in pairs_slice (hgp_internal.hpp), for every argument type.
 #if defined(HGP_PAIRS_SEGOPS_TU)
 // The streamed band kernel (hgp_segops.hip: this text a third time, k_pairs renamed k_pairs_seg, only <NB, true> instantiated):
 // the segment's length comes from its record of the segment-operator store, like everything else of the prologue.
@@ -333,18 +340,15 @@ using KArgs = PairsSegArgs;
 #define PAIRS_SEG_REC(a, n) ((a).store + (size_t)(n) * SegOps<NB>::REC)
 #define PAIRS_SEG_LEN(a, n, ld) \
   __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(PAIRS_SEG_REC(a, n) + SegOps<NB>::WORDS)[SegOps<NB>::W_LEN])
-#define PAIRS_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * 1.8378770664093453)   // as the ragged kernels
-#define PAIRS_SKIP_SEGMENTS(a, off) (void)0
+#define PAIRS_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * LOG_2PI)   // as the ragged kernels
 #elif defined(HGP_PAIRS_RAGGED_TU)
 using KArgs = PairsRagArgs;
 #define PAIRS_SEG_LEN(a, n, ld) __builtin_amdgcn_readfirstlane((a).seg_len[n])
-#define PAIRS_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * 1.8378770664093453)   // -0.5 Ts log(2 pi), the host's expression
-#define PAIRS_SKIP_SEGMENTS(a, off) (a).seg_len += (off)                      // launch_pairs: the lengths move with the other per-segment pointers
+#define PAIRS_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * LOG_2PI)   // the host's expression (pairs_args, hgp_plan.hip)
 #else
 using KArgs = PairsArgs;
 #define PAIRS_SEG_LEN(a, n, ld) (ld)
 #define PAIRS_SCORE_ADD(a, Ts) (a).score_add
-#define PAIRS_SKIP_SEGMENTS(a, off) (void)0
 #endif
 // a length outside [1, ld]: nothing of the row is read, its pair reports NaN / info = -1
 template <class Args>
@@ -1254,18 +1258,17 @@ __global__ __launch_bounds__(64 * CoopH<NB>::NW, (NB <= 8) ? 2 : 1) void k_pairs
 #endif
 }
 
-#ifdef HGP_PAIRS_SEGOPS_TU
-// the streamed band kernel alone, one workgroup per segment of the launch: hgp_segops.hip chains it with k_segops and the generic kernel
-template <int NB>
-int launch_pairs_seg(const KArgs& a, hipStream_t st) {
-  constexpr int PWB = pairs_waves<NB, true>();
-  const size_t ldsb = PairsLds<NB, PWB>::BYTES;
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, true>), ldsb)) return rc_;
-  hipLaunchKernelGGL((k_pairs<NB, true>), dim3(a.N), dim3(64 * PWB), ldsb, st, a);
+// one launch of k_pairs<NB, BAND>: a workgroup per segment of a
+template <int NB, bool BAND>
+int launch_pairs(const KArgs& a, hipStream_t st) {
+  constexpr int PW = pairs_waves<NB, BAND>();
+  const size_t lds = PairsLds<NB, PW>::BYTES;
+  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, BAND>), lds)) return rc_;
+  hipLaunchKernelGGL((k_pairs<NB, BAND>), dim3(a.N), dim3(64 * PW), lds, st, a);
   return launch_status();
 }
-}  // namespace
-#else
+
+#ifndef HGP_PAIRS_SEGOPS_TU   // (hgp_segops.hip goes on with its own launcher, hgp_internal_pairs_streamed)
 template <int NB>
 int launch_pairs_cooph(const KArgs& a, hipStream_t st) {
   const size_t lds = PairsCoop<NB>::BYTES;
@@ -1274,72 +1277,26 @@ int launch_pairs_cooph(const KArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_pairs_cooph<NB>, dim3(blocks), dim3(64 * CoopH<NB>::NW), lds, st, a);
   return launch_status();
 }
-
-template <int NB>
-int launch_pairs(const KArgs& a0, hipStream_t st) {
-  const size_t lds = PairsLds<NB, pairs_waves<NB, false>()>::BYTES;
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, false>), lds)) return rc_;
-  if (NB < 6 || (a0.flags & 1) || !a0.fb) {   // mask-driven sweeps for every segment
-    KArgs a = a0;
-    a.fb = nullptr;
-    hipLaunchKernelGGL((k_pairs<NB, false>), dim3(a.N), dim3(64 * WAVES), lds, st, a);
-    return launch_status();
-  }
-  constexpr int PWB = pairs_waves<NB, true>();
-  const size_t ldsb = PairsLds<NB, PWB>::BYTES;
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, true>), ldsb)) return rc_;
-  for (int off = 0; off < a0.N; off += PAIRS_FB_CAP) {   // the fall-back list holds PAIRS_FB_CAP segments
-    KArgs a = a0;
-    a.N = std::min(PAIRS_FB_CAP, a0.N - off);
-    const size_t oo = a.sel ? (size_t)off : (size_t)off * a.K;
-    a.x += (size_t)off * a.Ts;
-    a.y += (size_t)off * a.Ts;
-    PAIRS_SKIP_SEGMENTS(a, off);
-    if (a.first_noise) a.first_noise += oo;
-    if (a.sel) a.sel += off;
-    a.out_quad += oo;
-    if (a.out_logdet) a.out_logdet += oo;
-    if (a.out_info) a.out_info += oo;
-    hipLaunchKernelGGL((k_pairs<NB, true>), dim3(a.N), dim3(64 * PWB), ldsb, st, a);
-    const int rc1 = launch_status();
-    hipLaunchKernelGGL((k_pairs<NB, false>), dim3(a.N), dim3(64 * WAVES), lds, st, a);
-    const int rc2 = launch_status();
-    if (rc1 || rc2) {   // the generic kernel hands the list back empty; if either launch failed, do it here
-      (void)hipMemsetAsync(a.fb, 0, sizeof(int32_t), st);
-      (void)hipMemsetAsync(a.fb + 1 + PAIRS_FB_CAP, 0, sizeof(int32_t), st);
-      return rc1 ? rc1 : rc2;
-    }
-  }
-  return 0;
-}
-
-// k_pairs<NB, false> alone on the list a.fb that a band kernel of another unit (hgp_segops.hip) has filled on this stream
-template <int NB>
-int launch_pairs_listed(const KArgs& a, hipStream_t st) {
-  const size_t lds = PairsLds<NB, pairs_waves<NB, false>()>::BYTES;
-  if (int rc_ = hgp_internal_ensure_dynamic_lds(reinterpret_cast<const void*>(&k_pairs<NB, false>), lds)) return rc_;
-  hipLaunchKernelGGL((k_pairs<NB, false>), dim3(a.N), dim3(64 * WAVES), lds, st, a);
-  return launch_status();
-}
+#endif
 
 }  // namespace
 
-#ifdef HGP_PAIRS_RAGGED_TU
-int hgp_internal_pairs_listed_ragged(const PairsRagArgs& a, int NB, hipStream_t st) {
-#else
-int hgp_internal_pairs_listed(const PairsArgs& a, int NB, hipStream_t st) {
-#endif
-  if (!a.fb) return -1;
-  return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs_listed<decltype(nb)::value>(a, st); });
+#ifndef HGP_PAIRS_SEGOPS_TU
+// The launch steps of hgp_internal_pairs_score for this unit's KArgs (hgp_internal.hpp), dispatched by padded size
+int hgp_internal_pairs_all(const KArgs& a0, int NB, bool coop, hipStream_t st) {
+  if (coop) return dispatch_nb_coop(16 * NB, [&](auto nb) { return launch_pairs_cooph<decltype(nb)::value>(a0, st); });   // NB/2 waves per pair (CoopH)
+  KArgs a = a0;
+  a.fb = nullptr;   // mask-driven sweeps for every segment
+  return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs<decltype(nb)::value, false>(a, st); });
 }
 
-// dispatch by padded size / kernel family (see hgp_loglik_pairs_f64)
-#ifdef HGP_PAIRS_RAGGED_TU
-int hgp_internal_pairs_fast_ragged(const PairsRagArgs& a, int NB, bool coop, hipStream_t st) {
-#else
-int hgp_internal_pairs_fast(const PairsArgs& a, int NB, bool coop, hipStream_t st) {
-#endif
-  if (coop) return dispatch_nb_coop(16 * NB, [&](auto nb) { return launch_pairs_cooph<decltype(nb)::value>(a, st); });   // NB/2 waves per pair (CoopH)
-  return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs<decltype(nb)::value>(a, st); });
+int hgp_internal_pairs_band(const KArgs& a, int NB, hipStream_t st) {
+  if (!a.fb) return -1;
+  return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs<decltype(nb)::value, true>(a, st); });
+}
+
+int hgp_internal_pairs_listed(const KArgs& a, int NB, hipStream_t st) {
+  if (!a.fb) return -1;
+  return dispatch_nb_wave(16 * NB, [&](auto nb) { return launch_pairs<decltype(nb)::value, false>(a, st); });
 }
 #endif   // HGP_PAIRS_SEGOPS_TU

@@ -206,7 +206,7 @@ template <class Args> constexpr bool acc_ragged = std::is_base_of<AccRagArgs, Ar
 #ifdef HGP_PAIRS_RAGGED_TU   // (macros, as in hgp_pairs.hip)
 using KArgs = AccRagArgs;
 #define ACC_SEG_LEN(a, n, ld) __builtin_amdgcn_readfirstlane((a).seg_len[n])
-#define ACC_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * 1.8378770664093453)   // -0.5 Ts log(2 pi), the host's expression
+#define ACC_SCORE_ADD(a, Ts) (-0.5 * (double)(Ts) * LOG_2PI)   // the host's expression (acc_args)
 #else
 using KArgs = AccArgs;
 #define ACC_SEG_LEN(a, n, ld) (ld)
@@ -462,23 +462,29 @@ int launch_pairs_acc(const KArgs& a, hipStream_t st) {
   return launch_status();
 }
 
-AccArgs acc_args(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts, const double* first_noise, const int32_t* sel,
-                 double* out_quad, double* out_logdet, int32_t* out_info) {
-  return AccArgs{x, y, N, Ts, p->d_xb, p->T, p->d_scal, p->d_mu, p->d_Lop, p->d_LTop, p->d_Dop, p->d_Sop, p->d_acc_list,
-                 first_noise, sel, p->K, out_quad, out_logdet, out_info, p->d_sscr, -0.5 * (double)Ts * 1.8378770664093453, p->score_out};
+// the only place that names the fields of AccArgs / AccRagArgs
+template <class Args>
+Args acc_args(const hgp_pairs_plan* p, const PairsCall& c) {
+  Args a{};
+  a.x = c.x; a.y = c.y; a.N = c.N; a.Ts = c.ld; a.first_noise = c.first_noise; a.sel = c.sel;   // the call
+  a.out_quad = c.out_quad; a.out_logdet = c.out_logdet; a.out_info = c.out_info;
+  a.xb = p->d_xb; a.T = p->T; a.K = p->K; a.scal = p->d_scal; a.mu = p->d_mu; a.acc_list = p->d_acc_list;   // the plan
+  a.Lop = p->d_Lop; a.LTop = p->d_LTop; a.Dop = p->d_Dop; a.Sop = p->d_Sop; a.sscr = p->d_sscr;
+  a.score_add = -0.5 * (double)c.ld * LOG_2PI; a.score_on = p->score_out;
+  if constexpr (acc_ragged<Args>) a.seg_len = c.seg_len;
+  return a;
 }
 
 }  // namespace
 
-#ifdef HGP_PAIRS_RAGGED_TU
-int hgp_internal_pairs_acc_ragged(const hgp_pairs_plan* p, const double* x, const double* y, int N, int ld, const int32_t* seg_len,
-                                  const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet,
-                                  int32_t* out_info, hipStream_t st) {
+// the solve-based kernel over the whole batch: this unit's form (std::true_type: ragged)
+int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const PairsCall& c, std::bool_constant<acc_ragged<KArgs>>, hipStream_t st) {
   if (p->acc_tol < 0.0) return 0;
-  const AccRagArgs a{acc_args(p, x, y, N, ld, first_noise, sel, out_quad, out_logdet, out_info), seg_len};
+  const KArgs a = acc_args<KArgs>(p, c);
   return dispatch_nb(p->NB, [&](auto nb) { return launch_pairs_acc<decltype(nb)::value>(a, st); });
 }
-#else
+
+#ifndef HGP_PAIRS_RAGGED_TU   // the plan's preparation belongs to the rectangular unit alone
 // sizes[0..5]: Lop, LTop, Dop, Sop, mu, sscr (bytes)
 size_t hgp_internal_acc_bytes(int TP, int K, size_t* sizes) {
   const int NB = TP / 16;
@@ -509,12 +515,5 @@ int hgp_internal_acc_prep(hgp_pairs_plan* p, const double* mean, bool flags_done
   AccPrepArgs a{p->d_A, p->d_S, mean, p->d_scal, p->T, TP, NB, p->d_Lop, p->d_LTop, p->d_Dop, p->d_Sop, p->d_mu};
   hipLaunchKernelGGL(k_acc_prep, dim3(K, 8), dim3(256), 0, st, a);
   return launch_status();
-}
-
-int hgp_internal_pairs_acc(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts, const double* first_noise,
-                           const int32_t* sel, double* out_quad, double* out_logdet, int32_t* out_info, hipStream_t st) {
-  if (p->acc_tol < 0.0) return 0;
-  const AccArgs a = acc_args(p, x, y, N, Ts, first_noise, sel, out_quad, out_logdet, out_info);
-  return dispatch_nb(p->NB, [&](auto nb) { return launch_pairs_acc<decltype(nb)::value>(a, st); });
 }
 #endif  // HGP_PAIRS_RAGGED_TU

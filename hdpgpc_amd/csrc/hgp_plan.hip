@@ -1,5 +1,6 @@
 // The pairs plan: the per-cluster operators of the explicit-operator pair kernels (hgp_pairs.hip) and of the solve-based kernel
-// (hgp_pairs_acc.hip), the layout of the plan's device buffer, and the C-ABI of the plan and of hgp_loglik_pairs_f64.
+// (hgp_pairs_acc.hip), the layout of the plan's device buffer, the C-ABI of the plan and of hgp_loglik_pairs_f64 / hgp_loglik_pairs_ragged_f64, and the one driver of a pair-scoring call
+// (hgp_internal_pairs_score: kernel arguments, launch order, the walk in slices of PAIRS_FB_CAP segments) behind every entry.
 //
 // hgp_pairs_plan_update, TP <= 128:  k_prep_build (K~, S, scalars) -> inverse factor Z = L^-1 (hgp_inverse.hip) -> k_plan_ops<NB>
 // (M', a', ||K~^-1||_inf and the routing flags in ONE launch: every workgroup recomputes from Z the strips of Kinv = Z^T Z,
@@ -534,6 +535,69 @@ size_t plan_layout(hgp_pairs_plan* p, int T, int Ts_max, int K, char* base) {
 unsigned long long* hgp_internal_stamp_dev = nullptr;   // host-side handle of the diagnostic counters (8 x u64)
 #endif
 
+// ------------------------------------------------------------------------------------------------ one pair-scoring call
+// The kernel arguments of call c for length-scale group gi of the plan, whole batch: the only place that names the fields of
+// PairsArgs.  The ragged and the streamed kernels take the same with one pointer behind it (PairsRagArgs, PairsSegArgs).
+static PairsArgs pairs_args(const hgp_pairs_plan* p, size_t gi, const PairsCall& c, bool generic) {
+  PairsArgs a{};
+  a.x = c.x; a.y = c.y; a.N = c.N; a.Ts = c.ld; a.first_noise = c.first_noise; a.sel = c.sel;   // the call
+  a.out_quad = c.out_quad; a.out_logdet = c.out_logdet; a.out_info = c.out_info;
+  a.xb = p->d_xb; a.T = p->T; a.K = p->K; a.Mp = p->d_Mp; a.ap = p->d_ap; a.scal = p->d_scal; a.perm = p->d_perm;   // the plan
+  a.kbeg = p->grp_beg[gi]; a.kend = p->grp_end[gi]; a.ell = p->grp_ell[gi];                         // the group
+  a.escr = p->d_escr; a.eflags = p->d_eflags; a.nscr = p->nscr; a.escr_stride = p->escr_stride; a.fb = p->d_fb;
+  a.flags = generic ? 1 : 0;
+  a.score_add = -0.5 * (double)c.ld * LOG_2PI; a.score_on = p->score_out;
+#ifdef HGP_STAMPS
+  a.stamps = hgp_internal_stamp_dev;
+#endif
+  return a;
+}
+
+// The generic kernel hands the fall-back list back empty; after a launch that failed, the host does
+static void pairs_reset_list(int32_t* fb, hipStream_t st) {
+  (void)hipMemsetAsync(fb, 0, sizeof(int32_t), st);
+  (void)hipMemsetAsync(fb + 1 + PAIRS_FB_CAP, 0, sizeof(int32_t), st);
+}
+
+// KA = PairsArgs (every row has c.ld points) or PairsRagArgs (c.seg_len)
+template <class KA>
+static int pairs_score_as(const hgp_pairs_plan* p, const PairsCall& c, void* store, hipStream_t st) {
+  const bool generic = pairs_generic_forced();
+  const int NB = p->NB;
+  for (size_t gi = 0; gi < p->grp_beg.size(); ++gi) {
+    KA a{pairs_args(p, gi, c, generic)};
+    if constexpr (pairs_ragged<KA>) a.seg_len = c.seg_len;
+    if (p->coop || NB < 6 || generic) {   // one kernel takes every segment: no list, no slices
+      if (int rc = hgp_internal_pairs_all(a, NB, p->coop, st)) return rc;
+      continue;
+    }
+    for (int off = 0; off < c.N; off += PAIRS_FB_CAP) {   // the fall-back list holds PAIRS_FB_CAP segments
+      const KA s = pairs_slice(a, off, std::min(PAIRS_FB_CAP, c.N - off));
+      const int32_t* len = nullptr;
+      if constexpr (pairs_ragged<KA>) len = s.seg_len;
+      const int rc1 = store ? hgp_internal_pairs_streamed(s, len, store, gi * (size_t)c.N + off, NB, st)   // k_segops, k_pairs_seg
+                            : hgp_internal_pairs_band(s, NB, st);
+      const int rc2 = hgp_internal_pairs_listed(s, NB, st);
+      if (rc1 || rc2) {
+        pairs_reset_list(p->d_fb, st);
+        return rc1 ? rc1 : rc2;
+      }
+    }
+  }
+  return hgp_internal_pairs_acc(p, c, std::bool_constant<pairs_ragged<KA>>{}, st);
+}
+
+int hgp_internal_pairs_score(const hgp_pairs_plan* p, const PairsCall& c, void* store, hipStream_t st) {
+  if (c.ld > HGP_MAX_T_COOP) return -2;
+  if (c.ld > p->TP) return -2;   // plan was created with a smaller Ts_max
+  // the hand-out flags of the overflow areas start every call at "free": a launch that was killed mid-flight cannot leave the
+  // next one spinning (a plan serves ONE stream at a time; see the header)
+  if (p->coop && p->d_eflags && p->nscr > 0 &&
+      hipMemsetAsync(p->d_eflags, 0, (p->nscr + 1) * sizeof(int32_t), st) != hipSuccess)
+    return launch_status();
+  return c.seg_len ? pairs_score_as<PairsRagArgs>(p, c, store, st) : pairs_score_as<PairsArgs>(p, c, store, st);
+}
+
 extern "C" {
 
 size_t hgp_pairs_plan_device_bytes(int T, int Ts_max, int K) {
@@ -652,43 +716,13 @@ int hgp_pairs_plan_set_score_output(hgp_pairs_plan* p, int on) {
   return 0;
 }
 
-// hgp_loglik_pairs_f64 (seg_len == nullptr: every row has ld points) and hgp_loglik_pairs_ragged_f64 (seg_len[n] points in row n)
-static int loglik_pairs(const hgp_pairs_plan* p, const double* x, const double* y, int N, int ld, const int32_t* seg_len,
-                        const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet, int32_t* out_info,
-                        void* stream) {
-  const int Ts = ld;
-  if (Ts > HGP_MAX_T_COOP) return -2;
-  if (Ts > p->TP) return -2;   // plan was created with a smaller Ts_max
-  hipStream_t st = (hipStream_t)stream;
-  int rc = 0;
-  // the hand-out flags of the overflow areas start every call at "free": a launch that was killed mid-flight cannot leave the
-  // next one spinning (a plan serves ONE stream at a time; see the header)
-  if (p->coop && p->d_eflags && p->nscr > 0 &&
-      hipMemsetAsync(p->d_eflags, 0, (p->nscr + 1) * sizeof(int32_t), st) != hipSuccess)
-    return launch_status();
-  for (size_t gi = 0; gi < p->grp_beg.size() && rc == 0; ++gi) {
-    PairsArgs a{x, y, N, Ts, p->d_xb, p->T, p->d_Mp, p->d_ap, p->d_scal, p->d_perm, p->grp_beg[gi], p->grp_end[gi],
-                p->grp_ell[gi], first_noise, sel,
-#ifdef HGP_STAMPS
-                hgp_internal_stamp_dev,
-#endif
-                p->K, out_quad, out_logdet, out_info, p->d_escr, p->d_eflags, p->nscr, p->escr_stride,
-                env_on("HGP_PAIRS_GENERIC") ? 1 : 0, -0.5 * (double)Ts * 1.8378770664093453, p->score_out, p->d_fb};
-    rc = seg_len ? hgp_internal_pairs_fast_ragged(PairsRagArgs{a, seg_len}, p->NB, p->coop, st)
-                 : hgp_internal_pairs_fast(a, p->NB, p->coop, st);
-  }
-  if (rc == 0)
-    rc = seg_len ? hgp_internal_pairs_acc_ragged(p, x, y, N, ld, seg_len, first_noise, sel, out_quad, out_logdet, out_info, st)
-                 : hgp_internal_pairs_acc(p, x, y, N, Ts, first_noise, sel, out_quad, out_logdet, out_info, st);
-  return rc;
-}
-
 int hgp_loglik_pairs_f64(const hgp_pairs_plan* p, const double* x, const double* y, int N, int Ts,
                          const double* first_noise, const int32_t* sel, double* out_quad, double* out_logdet,
                          int32_t* out_info, void* stream) {
   if (N == 0) return 0;   // an empty batch is a no-op (its pointers may legitimately be null)
   if (!p || !x || !y || !out_quad || N < 0 || Ts <= 0) return -1;
-  return loglik_pairs(p, x, y, N, Ts, nullptr, first_noise, sel, out_quad, out_logdet, out_info, stream);
+  return hgp_internal_pairs_score(p, PairsCall{x, y, N, Ts, nullptr, first_noise, sel, out_quad, out_logdet, out_info}, nullptr,
+                                  (hipStream_t)stream);
 }
 
 int hgp_loglik_pairs_ragged_f64(const hgp_pairs_plan* p, const double* x, const double* y, int N, int ld, const int32_t* seg_len,
@@ -696,7 +730,8 @@ int hgp_loglik_pairs_ragged_f64(const hgp_pairs_plan* p, const double* x, const 
                                 int32_t* out_info, void* stream) {
   if (N == 0) return 0;
   if (!p || !x || !y || !seg_len || !out_quad || N < 0 || ld <= 0) return -1;
-  return loglik_pairs(p, x, y, N, ld, seg_len, first_noise, sel, out_quad, out_logdet, out_info, stream);
+  return hgp_internal_pairs_score(p, PairsCall{x, y, N, ld, seg_len, first_noise, sel, out_quad, out_logdet, out_info}, nullptr,
+                                  (hipStream_t)stream);
 }
 
 #ifdef HGP_STAMPS

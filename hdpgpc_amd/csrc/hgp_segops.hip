@@ -6,8 +6,9 @@
 //    record's tiles into LDS.  k_pairs, k_pairs_rag and their cooperative forms stay the code they were, in their own units.
 //  * segments that are not of the band pattern go to the plan's fall-back list and the mask-driven kernel of hgp_pairs.hip /
 //    hgp_pairs_ragged.hip, which builds its own E as ever; flagged clusters go to the solve-based kernel as ever.
+// The unit's part of a call is one launch step, hgp_internal_pairs_streamed (k_segops, then k_pairs_seg, on one slice of the
+// batch); the driver hgp_internal_pairs_score (hgp_plan.hip) takes it in place of the band kernel when the entry hands it a store.
 #include "hgp_segops.hpp"
-#include "../../include/hdpgpc_hip_ragged.h"
 #include "../../include/hdpgpc_hip_segops.h"
 
 #define HGP_PAIRS_SEGOPS_TU 1
@@ -177,10 +178,18 @@ template <class F> inline auto dispatch_nb_band(int NB, F&& f) {   // the sizes 
   return NB == 6 ? f(std::integral_constant<int, 6>{}) : f(std::integral_constant<int, 8>{});
 }
 
-inline bool segops_serves(const hgp_pairs_plan* p) { return !p->coop && (p->NB == 6 || p->NB == 8) && !env_on("HGP_PAIRS_GENERIC"); }
+inline bool segops_serves(const hgp_pairs_plan* p) { return !p->coop && (p->NB == 6 || p->NB == 8) && !pairs_generic_forced(); }
 inline size_t segops_rec_bytes(int NB) { return NB == 6 ? SegOps<6>::BYTES : SegOps<8>::BYTES; }
 
 }  // namespace
+
+int hgp_internal_pairs_streamed(const PairsArgs& a, const int32_t* seg_len, void* store, size_t first, int NB, hipStream_t st) {
+  if (!a.fb) return -1;
+  double* rec0 = static_cast<double*>(store) + first * (segops_rec_bytes(NB) / sizeof(double));
+  const SegOpsArgs sa{a.x, seg_len, a.N, a.Ts, a.xb, a.T, a.ell, rec0};
+  if (int rc = dispatch_nb_band(NB, [&](auto nb) { return launch_segops<decltype(nb)::value>(sa, st); })) return rc;
+  return dispatch_nb_band(NB, [&](auto nb) { return launch_pairs<decltype(nb)::value, true>(PairsSegArgs{a, rec0}, st); });
+}
 
 extern "C" {
 
@@ -189,57 +198,16 @@ size_t hgp_pairs_segops_bytes(const hgp_pairs_plan* p, int N, int ld) {
   return p->grp_beg.size() * (size_t)N * segops_rec_bytes(p->NB);
 }
 
+// Where no band kernel serves the plan the size function says 0: the call is that of the entries without a store
 int hgp_loglik_pairs_segops_f64(const hgp_pairs_plan* p, void* segops, size_t segops_bytes, const double* x, const double* y, int N,
                                 int ld, const int32_t* seg_len, const double* first_noise, const int32_t* sel, double* out_quad,
                                 double* out_logdet, int32_t* out_info, void* stream) {
   if (N == 0) return 0;
   if (!p || !x || !y || !out_quad || N < 0 || ld <= 0) return -1;
   const size_t need = hgp_pairs_segops_bytes(p, N, ld);
-  if (need == 0)
-    return seg_len ? hgp_loglik_pairs_ragged_f64(p, x, y, N, ld, seg_len, first_noise, sel, out_quad, out_logdet, out_info, stream)
-                   : hgp_loglik_pairs_f64(p, x, y, N, ld, first_noise, sel, out_quad, out_logdet, out_info, stream);
-  if (!segops || ((uintptr_t)segops & 15) || segops_bytes < need) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t rec = segops_rec_bytes(p->NB) / sizeof(double);
-  int rc = 0;
-  for (size_t gi = 0; gi < p->grp_beg.size() && rc == 0; ++gi) {
-    double* store = static_cast<double*>(segops) + gi * (size_t)N * rec;
-    const PairsArgs a0{x, y, N, ld, p->d_xb, p->T, p->d_Mp, p->d_ap, p->d_scal, p->d_perm, p->grp_beg[gi], p->grp_end[gi],
-                       p->grp_ell[gi], first_noise, sel,
-#ifdef HGP_STAMPS
-                       hgp_internal_stamp_dev,
-#endif
-                       p->K, out_quad, out_logdet, out_info, p->d_escr, p->d_eflags, p->nscr, p->escr_stride, 0,
-                       -0.5 * (double)ld * 1.8378770664093453, p->score_out, p->d_fb};
-    for (int off = 0; off < N && rc == 0; off += PAIRS_FB_CAP) {   // the fall-back list holds PAIRS_FB_CAP segments
-      PairsArgs a = a0;
-      a.N = std::min(PAIRS_FB_CAP, N - off);
-      const size_t oo = sel ? (size_t)off : (size_t)off * a.K;
-      a.x += (size_t)off * ld;
-      a.y += (size_t)off * ld;
-      if (a.first_noise) a.first_noise += oo;
-      if (a.sel) a.sel += off;
-      a.out_quad += oo;
-      if (a.out_logdet) a.out_logdet += oo;
-      if (a.out_info) a.out_info += oo;
-      const int32_t* len = seg_len ? seg_len + off : nullptr;
-      double* st0 = store + (size_t)off * rec;
-      const SegOpsArgs sa{a.x, len, a.N, ld, p->d_xb, p->T, p->grp_ell[gi], st0};
-      rc = dispatch_nb_band(p->NB, [&](auto nb) { return launch_segops<decltype(nb)::value>(sa, st); });
-      if (rc) break;
-      const int rc1 = dispatch_nb_band(p->NB, [&](auto nb) { return launch_pairs_seg<decltype(nb)::value>(PairsSegArgs{a, st0}, st); });
-      const int rc2 = len ? hgp_internal_pairs_listed_ragged(PairsRagArgs{a, len}, p->NB, st) : hgp_internal_pairs_listed(a, p->NB, st);
-      if (rc1 || rc2) {   // the generic kernel hands the list back empty; if either launch failed, do it here
-        (void)hipMemsetAsync(a.fb, 0, sizeof(int32_t), st);
-        (void)hipMemsetAsync(a.fb + 1 + PAIRS_FB_CAP, 0, sizeof(int32_t), st);
-        rc = rc1 ? rc1 : rc2;
-      }
-    }
-  }
-  if (rc == 0)
-    rc = seg_len ? hgp_internal_pairs_acc_ragged(p, x, y, N, ld, seg_len, first_noise, sel, out_quad, out_logdet, out_info, st)
-                 : hgp_internal_pairs_acc(p, x, y, N, ld, first_noise, sel, out_quad, out_logdet, out_info, st);
-  return rc;
+  if (need && (!segops || ((uintptr_t)segops & 15) || segops_bytes < need)) return -1;
+  return hgp_internal_pairs_score(p, PairsCall{x, y, N, ld, seg_len, first_noise, sel, out_quad, out_logdet, out_info},
+                                  need ? segops : nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -247,6 +247,59 @@ def test_pairs_plan_keeps_one_store_and_follows_n(T):
     plan.close()
 
 
+FB_CAP = 65536   # PAIRS_FB_CAP of csrc/hgp_internal.hpp: segments per slice of a call (capacity of the fall-back list)
+
+
+def test_streamed_route_beyond_the_fall_back_list():
+    """PAIRS_FB_CAP + 5 segments through the store (T = 90, ld = 96, two clusters of one length-scale, sorted jittered unit grids,
+    lengths cycling through 40 values in 60 ... 96 - shorter than 81 is not the band pattern): the second slice starts at segment
+    65 536 and must use ITS rows, lengths, selection, first_noise, outputs and records of the store.  The rows around the boundary
+    have reversed grids and go through the fall-back list on both sides of it.  Rows on both sides against the same rows scored
+    alone, through a store of their own and by the in-kernel route, on the bits; ragged, with sel and first_noise, and rectangular."""
+    T, ld, N, K2, base = 90, 96, FB_CAP + 5, 2, 40
+    rng = np.random.default_rng(11)
+    sb = orc.synthetic_batch(4, K2, T, seed=2)
+    theta = sb["theta"].copy()
+    theta[:, 1] = 1.2
+    lens_b = np.array([60 + (7 * n) % 37 for n in range(base)], dtype=np.int32)
+    assert lens_b.min() == 60 and lens_b.max() == ld and FB_CAP % base != 0   # out of step with the slice: an unshifted pointer shows
+    Xb = np.arange(ld) + rng.uniform(-0.3, 0.3, (base, ld))
+    Yb = np.stack([np.interp(Xb[n], sb["xb"], sb["mean"][n % K2]) for n in range(base)]) + rng.normal(0.0, 3.0, (base, ld))
+    reps = N // base + 1
+    Xh, Yh = np.tile(Xb, (reps, 1))[:N], np.tile(Yb, (reps, 1))[:N]
+    listed = [FB_CAP - 1, FB_CAP, FB_CAP + 1]
+    Xh[listed], Yh[listed] = Xh[listed, ::-1], Yh[listed, ::-1]
+    X, Y, lens = dev(Xh), dev(Yh), idev(np.tile(lens_b, reps)[:N])
+    sel, fn = idev(np.arange(N) % K2), dev(np.linspace(0.0, 0.5, N))
+    plan = ops.PairsPlan(T, ld, theta, device=DEV).update(dev(sb["xb"]), dev(sb["mean"]), dev(sb["Sigma"]))
+    need = _ffi.lib.hgp_pairs_segops_bytes(plan._h, N, ld)
+    assert need == N * 56960 > 1 << 31   # 3.7 GB
+
+    def cut(t, lo, hi):
+        return None if t is None else t[lo:hi].contiguous()
+
+    variants = (dict(lengths=lens), dict(lengths=lens, sel=sel, first_noise=fn), dict())
+    plan.SEGOPS_MAX_BYTES = 1 << 33   # instance attribute: this plan alone
+    whole = []
+    for kw in variants:   # every whole batch first: they share the one large store
+        r = plan.loglik(X, Y, **kw)
+        assert plan._segops.numel() == need and plan._segops_key[0] == N
+        assert int(r[2].abs().max()) == 0
+        assert same_bits(plan.loglik(X, Y, **kw), r)   # warm
+        assert (flags(plan._segops, T, N)[0, listed] == VALID).all()   # not the band pattern: the fall-back list
+        whole.append(r)
+    for kw, r in zip(variants, whole):
+        for lo, hi in ((0, 12), (FB_CAP - 7, FB_CAP), (FB_CAP, N), (FB_CAP - 3, FB_CAP + 3)):
+            kw_w = {k: cut(v, lo, hi) for k, v in kw.items()}
+            want = tuple(t[lo:hi] for t in r)
+            plan.SEGOPS_MAX_BYTES = 1 << 33   # alone through a store
+            got = plan.loglik(cut(X, lo, hi), cut(Y, lo, hi), **kw_w)
+            assert plan._segops_key[0] == hi - lo and same_bits(got, want), (sorted(kw), lo, hi)
+            plan.SEGOPS_MAX_BYTES = 0         # alone, the prologue built in the kernel
+            assert same_bits(plan.loglik(cut(X, lo, hi), cut(Y, lo, hi), **kw_w), want), (sorted(kw), lo, hi)
+    plan.close()
+
+
 def test_sizes_and_argument_errors():
     """hgp_pairs_segops_bytes is 0 where no band kernel serves the plan and the record size times groups times N where one does;
     a store that is too small, missing or misaligned is -1 and nothing is launched."""
