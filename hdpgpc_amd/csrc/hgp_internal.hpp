@@ -51,8 +51,10 @@ static inline bool env_on(const char* name) {
 
 // Entries of E = exp(-h) and of K** / c with h > PAIRS_CUT (value < 2^-80 = 8.3e-25) are exact zeros, and a 16x16 block (k_pairs'
 // static sweeps: a 4-row k-step of a block) whose entries are ALL below that is neither built nor multiplied.  What is dropped
-// changes a covariance entry by less than 2 T max|M'| 2^-80 - below one ulp of the entry for every cluster the explicit-operator
-// kernels score (the plan routes c^2 |K~^-1|^2 > 1e7 to the solve-based kernel).  With the reference's length-scale 1.2 on a
+// changes a covariance entry by less than 2 T max|M'| 2^-80 in absolute terms: at most 2e-15 for a cluster the explicit-operator
+// kernels score (the plan routes eps c^2 |K~^-1|^2 > 1e-9 to the solve-based kernel), about one ulp of the covariance's diagonal
+// and six orders below the rounding error eps c^2 |K~^-1|^2 of the explicit operator itself.  Against 40-digit truth the cut is
+// not visible on either side of that threshold (tests/test_gpu_pairs_truth.py).  With the reference's length-scale 1.2 on a
 // unit-spaced grid the band is |k - j| <= 12 points: only the blocks |Kt - J| <= 1 survive (~60 % of the MFMA work at T = 128 gone)
 // and, of their 12 k-steps per column panel, 10.  (Rounds 1-3 cut at 1e-36: |k - j| <= 15, no dead k-step.)  The decision is taken
 // from the data (any grid), never from an assumed band structure.
